@@ -22,15 +22,23 @@ ranks filtered / max-over-ranks time.
 The product path uses no PyTorch; the ranks rendezvous through a file
 (sk_dsp_comm_amd.sharding.FileRendezvous) and barrier / max-reduce through RCCL.
 
-Rank 0 prints ONE JSON line on stdout, the LAST thing it writes and kept under FINAL_LINE_MAX_BYTES
-(final_line(); tests/test_host_cpu.py checks the bound on a recorded run and on the worst case): the
-driver contract's fields + "roofline" + "cpu_baseline" (the C port of the reference's arithmetic) +
-"cpu_baseline_scipy" (literally the reference's scipy.signal call) + "rows" (one compact entry per
-other workload timed in the same process behind the headline: BASELINE.json configs 3, 4, the
-127-tap shape, the SURVEY 8(a) rate rows) + for N > 1 the RCCL rank count, the halo form used, the
-per-rank parity and the config-5 leg.  Everything longer (each other workload's full record, the
-provenance of the PMC traffic, the device-copy reference) goes to stderr, one JSON line per workload
-prefixed "bench.py detail: ", and to gpurun_out/bench_detail_n<N>.json -- never to stdout.
+A plain run does only what the headline figure needs: set up, settle the clock, W warm-up steps, K timed
+steps, the outputs of the last timed step to --dump-outputs DIR when given (dump_outputs()), and ONE JSON
+line on stdout: the result fields (metric, value, unit, ms_per_step, ...) + "roofline" (from the timed
+steps' HIP events and the committed PMC traffic) + for N > 1 the RCCL rank count and the per-rank times.
+
+--full adds everything else the bench measures or checks: the head of the result against the oracle,
+board power / clock and the device-copy reference, "cpu_baseline" (the C port of the reference's
+arithmetic) + "cpu_baseline_scipy" (literally the reference's scipy.signal call) + "rows" (one compact
+entry per other workload timed in the same process behind the headline: BASELINE.json configs 3, 4, the
+127-tap shape, the SURVEY 8(a) rate rows) + for N > 1 the halo form used, the per-rank parity (the run
+exits 3 above the tolerance) and the config-5 leg.
+
+Rank 0's line is the LAST thing it writes and is kept under FINAL_LINE_MAX_BYTES (final_line();
+tests/test_host_cpu.py checks the bound on a recorded run and on the worst case).  Everything longer
+(each other workload's full record, the provenance of the PMC traffic, the device-copy reference) goes
+to stderr, one JSON line per workload prefixed "bench.py detail: ", and with --full to a side file
+(emit()) -- never to stdout.
 --workload updn43|iir8|fir127 runs one of the other configs as the main line instead.
 """
 import argparse
@@ -477,6 +485,33 @@ def free_workload(w):
             d.free()
 
 
+# --dump-outputs: at most this many bytes over all ranks (outputs larger than a rank's share are sampled in blocks at seeded positions)
+DUMP_BYTES_MAX = 32 << 20
+DUMP_BLOCK = 4096
+DUMP_SEED = 2026
+
+
+def dump_outputs(w, out_dir, rank, world):
+    """What the timed path computed in its last step -- w.yd, the array a caller of the path receives -- as DIR/y.npy (DIR/y_rank<r>.npy
+    for N > 1), float32 or float64, complex samples as [re, im] rows.  An output larger than its rank's share of DUMP_BYTES_MAX is written as
+    a fixed sample in index order: the first and the last block of DUMP_BLOCK samples and blocks at DUMP_SEED-drawn positions between them.
+    The inputs are counter-based noise keyed by seed and global index, so the same arguments give the same samples from run to run and
+    two builds can be compared output for output."""
+    y = w.yd
+    budget = max(2 * DUMP_BLOCK, DUMP_BYTES_MAX // world // y.dtype.itemsize)     # samples this rank may write
+    if y.n <= budget:
+        data = y.to_host()
+    else:
+        nb = -(-y.n // DUMP_BLOCK)
+        mid = np.random.default_rng(DUMP_SEED).choice(np.arange(1, nb - 1), size=budget // DUMP_BLOCK - 2, replace=False)
+        blocks = np.concatenate(([0], np.sort(mid), [nb - 1]))
+        data = np.concatenate([y.to_host(b * DUMP_BLOCK, min(DUMP_BLOCK, y.n - b * DUMP_BLOCK)) for b in blocks])
+    if np.iscomplexobj(data):
+        data = data.view(data.real.dtype).reshape(-1, 2)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "y.npy" if world == 1 else "y_rank%d.npy" % rank), data)
+
+
 def timed_steps(w, K, W, settle_s, tr, _ffi):
     """Settle the clock, W warm-up passes, then K timed passes bracketed by barrier + sync.
     -> (wall seconds max over ranks, HIP-event ms max over ranks, this rank's (wall, event ms))."""
@@ -651,6 +686,7 @@ def dp_pipe_of(w, ev_ms, K, compute_units):
 # ------------------------------------------------------------------------------ what rank 0 prints
 FINAL_LINE_MAX_BYTES = 8000   # the driver parses the LAST stdout line out of a bounded tail (a 22.9 KB line was not kept: BENCH_r05.json)
 ROWS_WHAT = "per workload (2^26 samples): kernel ms, fraction of 8 TB/s, PMC traffic / algorithmic bytes, head error vs the oracle, board W, shader MHz"
+DETAIL_DIR = "bench_out"      # a --full run's whole record: <repository>/bench_out/bench_detail_n<N>.json
 
 
 def _clip(v, n):
@@ -740,23 +776,24 @@ def final_line(out):
     return fl
 
 
-def emit(out):
-    """Rank 0, once: the long records to stderr and to a side file, then the one line on stdout."""
+def emit(out, side_file=True):
+    """Rank 0, once: the long records to stderr and (side_file: a --full run) to a side file, then the one line on stdout."""
     n = out.get("n_gpus", 1)
     for name, o in (out.get("other_configs") or {}).items():
         print("bench.py detail: " + json.dumps(dict(o, name=name)), file=sys.stderr)
     rest = {k: v for k, v in out.items() if k not in ("other_configs", "rows", "rows_what")}
     print("bench.py detail: " + json.dumps(dict(rest, name="headline")), file=sys.stderr)
     sys.stderr.flush()
-    try:   # gpurun merges gpurun_out/ back; elsewhere the file simply stays beside the repo's other scratch
-        d = os.path.join(ROOT, "gpurun_out")
-        os.makedirs(d, exist_ok=True)
-        path = os.path.join(d, "bench_detail_n%d.json" % n)
-        with open(path, "w") as f:
-            json.dump(out, f)
-        out["detail"] = os.path.relpath(path, ROOT)
-    except OSError:
-        pass
+    if side_file:
+        try:   # (the whole record, beside the repository's other build and run products)
+            d = os.path.join(ROOT, DETAIL_DIR)
+            os.makedirs(d, exist_ok=True)
+            path = os.path.join(d, "bench_detail_n%d.json" % n)
+            with open(path, "w") as f:
+                json.dump(out, f)
+            out["detail"] = os.path.relpath(path, ROOT)
+        except OSError:
+            pass
     # (what libraries left in C stdio buffers -- librccl's announcement -- leaves NOW, on stderr, so that the line is also the LAST thing a reader of both streams sees)
     flush_library_text()
     print(json.dumps(final_line(out)), file=_RESULT_STREAM or sys.stdout, flush=True)
@@ -810,7 +847,14 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=4.0, help="target CPU time of each baseline sample")
     ap.add_argument("--launch-timeout", type=float, default=1500.0)
     ap.add_argument("--board-seconds", type=float, default=1.5, help="0: skip the power / clock reading and the device-copy reference")
+    ap.add_argument("--full", action="store_true",
+                    help="also the checks and side measurements behind the headline: oracle parity, board power / clock, device copy, "
+                         "CPU baselines, the other workloads' rows, the N > 1 parity and config-5 leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/*.npy (float32 / float64, at most 32 MiB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))
@@ -835,9 +879,11 @@ def main():
 
     w = make_workload(args.workload, n, rank, world, tr, _ffi, sharding)
     elapsed, ev_ms, mine = timed_steps(w, K, W, args.settle_seconds, tr, _ffi)
+    if args.dump_outputs:   # (before anything else runs on the outputs: the device-copy reference of --full overwrites them)
+        dump_outputs(w, args.dump_outputs, rank, world)
 
     board = copy_ref = None
-    if world == 1 and args.board_seconds > 0:   # (before anything else touches the outputs: the parity check reads them first)
+    if args.full and world == 1 and args.board_seconds > 0:   # (before anything else touches the outputs: the parity check reads them first)
         try:
             board = board_state_of(w, args.board_seconds, _ffi)
         except Exception as e:
@@ -852,11 +898,11 @@ def main():
     n_comm = tr.comm_count()
 
     # quick parity spot check of what was just computed (oracle = checker only)
-    check = w.check() if (rank == 0 and w.check is not None) else None
+    check = w.check() if (args.full and rank == 0 and w.check is not None) else None
     # N > 1: EVERY rank checks the outputs that consumed its neighbour's halo / state and one interior window; the line
     # carries the maximum over ranks and the run fails (exit code 3) above the tolerance
     parity = None
-    if world > 1 and w.shard is not None:
+    if args.full and world > 1 and w.shard is not None:
         kind, coeffs, seed = w.shard
 
         def get_x(g0, count):
@@ -918,7 +964,7 @@ def main():
                                   "window vs the CPU oracle on inputs regenerated by global index; max over ranks; tolerance %g"
                                   % ("Ntaps-1 halo" if w.shard[0] == "fir" else "handed-over filter state", PARITY_TOL))
 
-    if rank == 0 and world == 1 and args.board_seconds > 0:   # (after the parity check: the copy overwrites the outputs)
+    if args.full and rank == 0 and world == 1 and args.board_seconds > 0:   # (after the parity check: the copy overwrites the outputs)
         try:
             copy_ref = device_copy_of(w, _ffi)
             out["device_copy"] = copy_ref
@@ -929,14 +975,14 @@ def main():
             out["device_copy"] = {"skipped": "%s: %s" % (type(e).__name__, e)}
 
     # ------------------------------------------- CPU baselines (rank 0 of a 1-GPU run only)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_port(args, w)
         out["cpu_baseline_scipy"] = cpu_baseline_scipy(args, w)
     elif rank == 0:
         out["cpu_baseline"] = None
 
     # ------------------------------------------- the other BASELINE.json configs, same process
-    if world == 1 and args.workload == "fir1024" and not args.no_other_configs and args.scaling == "weak":
+    if args.full and world == 1 and args.workload == "fir1024" and not args.no_other_configs and args.scaling == "weak":
         free_workload(w)
         others = {}
         for name in ("updn43", "iir8", "fir127", "iir8tp", "iir8cas", "iirlp8", "iir8c64", "fir1024c128") + OTHER_RATE_WORKLOADS:
@@ -976,7 +1022,7 @@ def main():
 
     # ------------------------------------------- N > 1: BASELINE config 5 (2^30 samples in total, strong scaling) behind the weak-scaling line
     c5_ok = True
-    if world > 1 and args.workload == "fir1024" and args.scaling == "weak" and not args.no_config5:
+    if args.full and world > 1 and args.workload == "fir1024" and args.scaling == "weak" and not args.no_config5:
         free_workload(w)
         try:
             rec, c5_ok = config5_leg(args, rank, world, tr, _ffi, sharding)
@@ -986,7 +1032,7 @@ def main():
             out["config5"] = rec
 
     if rank == 0:
-        emit(out)
+        emit(out, side_file=args.full)
     tr.close()
     if (parity is not None and not parity[3]) or not c5_ok:
         sys.exit(3)   # a wrong halo / state hand-off must not look like a result

@@ -41,7 +41,7 @@ class Rank0Of2(Base):
         return np.tile(tab, (2, 1))
 
 sharding.RcclTransport = Rank0Of2
-sys.argv = ['bench.py', '--gpus', '2', '--steps', '6', '--warmup', '3'] + sys.argv[1:]
+sys.argv = ['bench.py', '--gpus', '2', '--steps', '6', '--warmup', '3', '--full'] + sys.argv[1:]
 bench.main()
 """
 
@@ -75,3 +75,36 @@ def test_bench_main_as_rank_0_of_2(workload):
     c5 = d["config5"]
     assert "error" not in c5 and "skipped" not in c5, c5
     assert c5["parity_ok"] is True and c5["n_gpus"] == 2 and c5["total_samples"] == 1 << 30
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_steps_asked_for_and_dumps_the_last_one(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`, the headline workload: one line with the result fields and none of --full's
+    members, and DIR/y.npy = what the last timed step computed (a seeded sample of the 2^26 outputs, the head block first) -- checked
+    against the oracle on the same counter-based input."""
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    lines = [ln for ln in r.stdout.decode().split("\n") if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["n_gpus"] == 1 and d["unit"] == "MSamples/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "c64" and d["metric"].startswith("complex64 MSamples/s (FIR-1024 tap, 2^26")
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 2 ** 26 / (d["ms_per_step"] * 1e3)) < 1e-6 * d["value"]
+    assert d["roofline"]["frac"] > 0.4
+    for k in ("rows", "cpu_baseline_scipy", "board", "device_copy", "parity_spot_check_max_err", "detail"):
+        assert k not in d, k
+    assert d["cpu_baseline"] is None and os.listdir(str(tmp_path)) == ["y.npy"]
+    y = np.load(str(tmp_path / "y.npy"))
+    assert y.dtype == np.float32 and y.ndim == 2 and y.shape[1] == 2 and 1 << 20 <= y.nbytes <= 64 << 20
+    sys.path.insert(0, ROOT)
+    import bench
+    from sk_dsp_comm_amd import _ffi
+    from oracle import oracle as orc
+    _ffi.init(0)
+    m = bench.DUMP_BLOCK
+    x = _ffi.DeviceArray(m, np.complex64).fill_noise(2026).to_host()
+    ref = orc.fir_filter(bench.firwin_lowpass(1024, 0.2), x)
+    got = y[:m, 0] + 1j * y[:m, 1]
+    assert np.max(np.abs(got - ref)) / np.max(np.abs(ref)) < 1e-6

@@ -21,7 +21,7 @@ def _device_count():
 
 def _bench(n_ranks, extra, env=None):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n_ranks), "--steps", "6", "--warmup", "2",
-           "--settle-seconds", "0.05", "--launch-timeout", "400", "--no-cpu-baseline"] + extra
+           "--settle-seconds", "0.05", "--launch-timeout", "400", "--full", "--no-cpu-baseline"] + extra
     e = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     e.pop("WORLD_SIZE", None)
     e.pop("RANK", None)

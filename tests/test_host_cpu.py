@@ -468,12 +468,73 @@ def test_bench_emit_prints_exactly_one_stdout_line(tmp_path, monkeypatch, capsys
     lines = cap.out.strip().split("\n")
     assert len(lines) == 1 and len(lines[0]) <= bench.FINAL_LINE_MAX_BYTES
     out = json.loads(lines[0])
-    assert out["roofline"]["frac"] > 0.5 and out["cpu_baseline"]["value"] > 1.0 and out["detail"] == os.path.join("gpurun_out", "bench_detail_n1.json")
+    assert out["roofline"]["frac"] > 0.5 and out["cpu_baseline"]["value"] > 1.0 and out["detail"] == os.path.join("bench_out", "bench_detail_n1.json")
     side = json.load(open(os.path.join(str(tmp_path), out["detail"])))
     assert "other_configs" in side and len(side["other_configs"]) == 18                   # the long record is kept -- beside stdout
     detail = [ln for ln in cap.err.split("\n") if ln.startswith("bench.py detail: ")]
     assert len(detail) == 19 and all(json.loads(ln[len("bench.py detail: "):]) for ln in detail)
     assert not any(ln.lstrip().startswith("{") for ln in cap.err.split("\n"))            # nothing on stderr can be taken for the line
+
+
+def test_bench_emit_of_a_plain_run_writes_no_side_file(tmp_path, monkeypatch, capsys):
+    """A plain run (no --full) prints the same one line and leaves no file behind."""
+    bench = _bench_module()
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path))
+    rec = _recorded_full_record()
+    bench.emit(rec, side_file=False)
+    lines = capsys.readouterr().out.strip().split("\n")
+    assert len(lines) == 1 and len(lines[0]) <= bench.FINAL_LINE_MAX_BYTES
+    out = json.loads(lines[0])
+    assert out["value"] == rec["value"] and out["ms_per_step"] == rec["ms_per_step"] and "detail" not in out
+    assert os.listdir(str(tmp_path)) == []
+
+
+class _HostOutput:
+    """Stands in for a DeviceArray holding a path's output (to_host as the binding has it)."""
+
+    def __init__(self, a):
+        self.a, self.n, self.dtype = a, a.size, a.dtype
+
+    def to_host(self, start=0, count=None):
+        count = self.n - start if count is None else count
+        assert 0 <= start and start + count <= self.n
+        return self.a[start:start + count].copy()
+
+
+@pytest.mark.parametrize("dtype", [np.complex64, np.float32, np.complex128])
+def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch, dtype):
+    """--dump-outputs: a small output is written whole; a large one as the same seeded blocks every time (first and last block
+    included, in index order), within the byte bound; float32 / float64 only, complex as [re, im] rows."""
+    import types
+    bench = _bench_module()
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 4 << 20)                                    # (every sample index stays exact in float32)
+    real = np.float64 if dtype == np.complex128 else np.float32
+    rng = np.random.default_rng(5)
+    small = rng.standard_normal(10_000).astype(dtype) if np.dtype(dtype).kind == "f" else \
+        (rng.standard_normal(10_000) + 1j * rng.standard_normal(10_000)).astype(dtype)
+    bench.dump_outputs(types.SimpleNamespace(yd=_HostOutput(small)), str(tmp_path / "a"), 0, 1)
+    got = np.load(str(tmp_path / "a" / "y.npy"))
+    assert got.dtype == real
+    assert np.array_equal(got[:, 0] + 1j * got[:, 1] if np.dtype(dtype).kind == "c" else got, small)
+
+    n = (bench.DUMP_BYTES_MAX // np.dtype(dtype).itemsize) * 3 + 1001                        # larger than the bound, ragged last block
+    big = np.arange(n, dtype=np.float64)                                                      # each sample is its own index
+    big = (big + 1j * big).astype(dtype) if np.dtype(dtype).kind == "c" else big.astype(dtype)
+    for d in ("b", "c"):
+        bench.dump_outputs(types.SimpleNamespace(yd=_HostOutput(big)), str(tmp_path / d), 0, 1)
+    b, c = np.load(str(tmp_path / "b" / "y.npy")), np.load(str(tmp_path / "c" / "y.npy"))
+    assert b.dtype == real and np.array_equal(b, c)                                          # the same sample from run to run
+    assert b.nbytes <= bench.DUMP_BYTES_MAX
+    idx = (b[:, 0] if b.ndim == 2 else b).astype(np.int64)
+    assert np.all(np.diff(idx) > 0)                                                           # distinct samples in index order
+    B = bench.DUMP_BLOCK
+    assert np.array_equal(idx[:B], np.arange(B)) and idx[-1] == n - 1 and (n - 1) % B == 1000   # head, ragged tail
+    k = bench.DUMP_BYTES_MAX // np.dtype(dtype).itemsize // B
+    assert idx.size == (k - 1) * B + 1001                                                     # k blocks: k - 1 whole ones and the tail
+    starts = idx[np.r_[0, np.flatnonzero(np.diff(idx) > 1) + 1]]
+    assert np.all(starts % B == 0) and idx[-1002] > n // 2                                   # whole blocks, spread over the output
+    if b.ndim == 2:
+        assert np.array_equal(b[:, 0], b[:, 1])
 
 
 def test_bench_descriptor_1_carries_the_line_and_nothing_else(tmp_path):

@@ -42,18 +42,18 @@ done
 cd $ROOT
 if [ -n "$ONLY" ]; then
   for w in $ONLY; do
-    if [ $w = fir1024 ]; then python bench.py > $OUT/bench_fir1024.json 2>$OUT/bench_fir1024.err
-    else python bench.py --workload $w --no-other-configs --no-cpu-baseline > $OUT/bench_$w.json 2>/dev/null; fi
+    if [ $w = fir1024 ]; then python bench.py --full > $OUT/bench_fir1024.json 2>$OUT/bench_fir1024.err
+    else python bench.py --full --workload $w --no-other-configs --no-cpu-baseline > $OUT/bench_$w.json 2>/dev/null; fi
   done
   ls -la $OUT | tail -5; exit 0
 fi
 [ -n "$PMC_ONLY" ] && { ls -la $OUT | tail -5; exit 0; }
 if [ -z "$TABLES_ONLY" ]; then
-python bench.py > $OUT/bench_fir1024.json 2>$OUT/bench_fir1024.err
+python bench.py --full > $OUT/bench_fir1024.json 2>$OUT/bench_fir1024.err
 for w in updn43 iir8 fir127 iir8tp iir8cas iirlp8 iir8c64 fir1024c128 $RATE; do
-  python bench.py --workload $w --no-other-configs --no-cpu-baseline > $OUT/bench_$w.json 2>/dev/null
+  python bench.py --full --workload $w --no-other-configs --no-cpu-baseline > $OUT/bench_$w.json 2>/dev/null
 done
-python bench.py --scaling strong --total-log2n 30 --steps 50 --warmup 10 --no-cpu-baseline > $OUT/bench_fir1024_2p30_one_gpu.json 2>/dev/null
+python bench.py --full --scaling strong --total-log2n 30 --steps 50 --warmup 10 --no-cpu-baseline > $OUT/bench_fir1024_2p30_one_gpu.json 2>/dev/null
 [ -n "$BENCH_ONLY" ] && { ls -la $OUT | tail -3; exit 0; }
 fi
 python tools/power_probe.py idle copy fir1024 fir1024f32 fir1024f64 fir1024c128 updn43 fir127 iir8 iir8cas iir8c64 iirlp8 > $OUT/power_probe.txt 2>&1
