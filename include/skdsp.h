@@ -192,6 +192,19 @@ int skdsp_upsample_dev(const void *x_dev, int64_t n, int L, int dtype, double sc
 /* downsample: y[k] = x[k*M+p], k < n/M, 0 <= p < M (sigsys.py:3078-3083). */
 int skdsp_downsample(const void *x, int64_t n, int M, int p, int dtype, void *y);
 int skdsp_downsample_dev(const void *x_dev, int64_t n, int M, int p, int dtype, void *y_dev);
+/* farrow: arbitrary-ratio Farrow resampler, digitalcom.farrow_resample(x, fs_old, fs_new, i_ord, alpha)
+ * (digitalcom.py:53-235), with Ts_old = 1/fs_old, Ts_new = 1/fs_new.  Output j (0 <= j < n_out) is a 4-tap FIR of x around
+ * n_old(j) + 1 whose taps are polynomials of order i_ord (1, 2 or 3; alpha shapes i_ord 2) in the fractional delay mu(j).
+ * skdsp_farrow_len: n_out = len(np.arange(0, Ts_old*(n-3) + Ts_old, Ts_new)); host-only, needs no device.
+ * skdsp_farrow_dev: outputs [n0, n0 + count) of the whole result into y_dev[0 .. count).
+ * wide: bit 0 (SKDSP_FARROW_WIDE) float64 / complex128 results from a float32 / complex64 input, bit 1 (SKDSP_FARROW_F64)
+ * float64 arithmetic for such an input (float64 / complex128 inputs always run in float64 and ignore both bits). */
+#define SKDSP_FARROW_WIDE 1
+#define SKDSP_FARROW_F64 2
+int skdsp_farrow_len(int64_t n, double Ts_old, double Ts_new, int64_t *n_out);
+int skdsp_farrow_dev(const void *x_dev, int64_t n, int dtype, double Ts_old, double Ts_new, int i_ord, double alpha, int64_t n0,
+                     int64_t count, int wide, void *y_dev);
+int skdsp_farrow(const void *x, int64_t n, int dtype, double Ts_old, double Ts_new, int i_ord, double alpha, int wide, void *y);
 
 /* Host-pointer entry points of a float32/complex64 handle deliver y as float64/complex128 (the
  * reference's result dtype, multirate_helper.py:108 etc.): widened on the device before the copy

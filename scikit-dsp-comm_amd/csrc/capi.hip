@@ -2152,6 +2152,32 @@ int skdsp_downsample(const void *x, int64_t n, int M, int p, int dtype, void *y)
     return stage_out(y, y_dev, (size_t)n_out * esz);
 }
 
+// ---------------------------------------------------------------- Farrow resampler
+int skdsp_farrow_len(int64_t n, double Ts_old, double Ts_new, int64_t *n_out) { return farrow_len(n, Ts_old, Ts_new, n_out); }
+
+int skdsp_farrow_dev(const void *x_dev, int64_t n, int dtype, double Ts_old, double Ts_new, int i_ord, double alpha, int64_t n0,
+                     int64_t count, int wide, void *y_dev)
+{
+    API_BEGIN;
+    return farrow_launch(x_dev, n, dtype, Ts_old, Ts_new, i_ord, alpha, n0, count, wide, y_dev, ctx().stream);
+}
+
+int skdsp_farrow(const void *x, int64_t n, int dtype, double Ts_old, double Ts_new, int i_ord, double alpha, int wide, void *y)
+{
+    API_BEGIN;
+    SK_CHECK(dtype_valid(dtype) && n >= 0, SKDSP_ERR_BADARG, "farrow: bad arguments");
+    SK_CHECK(i_ord >= 1 && i_ord <= 3, SKDSP_ERR_BADARG, "farrow: i_ord must be 1, 2 or 3 (got %d)", i_ord);
+    int64_t n_out = 0;
+    int rc = farrow_len(n, Ts_old, Ts_new, &n_out);
+    if (rc || n_out == 0) return rc;
+    const size_t esz_out = dtype_size(dtype) * (!dtype_double(dtype) && (wide & SKDSP_FARROW_WIDE) ? 2 : 1);
+    void *x_dev = nullptr, *y_dev = nullptr;
+    if ((rc = stage_in(x, (size_t)n * dtype_size(dtype), &x_dev))) return rc;
+    if ((rc = ws_reserve(1, (size_t)n_out * esz_out + 256, &y_dev))) return rc;
+    if ((rc = farrow_launch(x_dev, n, dtype, Ts_old, Ts_new, i_ord, alpha, 0, n_out, wide, y_dev, ctx().stream))) return rc;
+    return stage_out(y, y_dev, (size_t)n_out * esz_out);
+}
+
 int skdsp_set_option(const char *name, int value)
 {
     SK_CHECK(name, SKDSP_ERR_BADARG, "set_option: null name");

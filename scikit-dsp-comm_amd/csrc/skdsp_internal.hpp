@@ -318,4 +318,9 @@ int convert_launch(const void *src_dev, void *dst_dev, int64_t nscalars, bool to
 int accumulate_launch(void *y_dev, const void *t_dev, int64_t nscalars, bool dbl, hipStream_t s);  // y += t
 int fill_noise_launch(void *x_dev, int64_t n, int dtype, uint64_t seed, int64_t first, hipStream_t s);
 
+// ---- Farrow resampler (farrow.hip) -----------------------------------------
+int farrow_len(int64_t n, double ts_old, double ts_new, int64_t *n_out);   // host-only
+int farrow_launch(const void *x_dev, int64_t n, int dtype, double ts_old, double ts_new, int i_ord, double alpha, int64_t n0,
+                  int64_t count, int flags, void *y_dev, hipStream_t s);   // outputs [n0, n0 + count) into y_dev
+
 }  // namespace skdsp

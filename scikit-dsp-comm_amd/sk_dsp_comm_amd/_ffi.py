@@ -34,6 +34,7 @@ SYMBOLS = [
     "skdsp_iir_filter_rows", "skdsp_iir_filter_rows_dev", "skdsp_sos_par_info", "skdsp_iir_sequential",
     "skdsp_sos_filter", "skdsp_sos_up", "skdsp_sos_dn",
     "skdsp_upsample", "skdsp_upsample_dev", "skdsp_downsample", "skdsp_downsample_dev", "skdsp_set_wide_output", "skdsp_destroy",
+    "skdsp_farrow_len", "skdsp_farrow_dev", "skdsp_farrow",
     "skdsp_dist_unique_id", "skdsp_dist_init", "skdsp_dist_shutdown", "skdsp_dist_comm_count", "skdsp_dist_barrier",
     "skdsp_dist_allreduce_max", "skdsp_dist_allreduce_sum", "skdsp_dist_sendrecv", "skdsp_dist_allgather", "skdsp_dist_halo_exchange", "skdsp_fir_filter_shard_dev",
 ]
@@ -124,6 +125,11 @@ def load():
         L.skdsp_downsample.argtypes = [vp, i64, ci, ci, ci, vp]
         L.skdsp_downsample_dev.argtypes = [vp, i64, ci, ci, ci, vp]
         L.skdsp_destroy.argtypes = [vp]
+        if hasattr(L, "skdsp_farrow"):
+            dbl = ctypes.c_double
+            L.skdsp_farrow_len.argtypes = [i64, dbl, dbl, p64]
+            L.skdsp_farrow_dev.argtypes = [vp, i64, ci, dbl, dbl, ci, dbl, i64, i64, ci, vp]
+            L.skdsp_farrow.argtypes = [vp, i64, ci, dbl, dbl, ci, dbl, ci, vp]
         L.skdsp_dist_unique_id.argtypes = [vp]
         L.skdsp_dist_init.argtypes = [ci, ci, vp]
         L.skdsp_dist_comm_count.argtypes = [ctypes.POINTER(ci)]
@@ -673,6 +679,41 @@ def upsample(x, L):
     y = np.empty(x.size * L, dtype=x.dtype)
     check(load().skdsp_upsample(_ptr(x), x.size, int(L), code_of(x.dtype), _ptr(y)))
     return y
+
+
+FARROW_WIDE, FARROW_F64 = 1, 2   # the `wide` flags of skdsp_farrow / skdsp_farrow_dev (include/skdsp.h)
+
+
+def farrow_len(n, Ts_old, Ts_new):
+    """Output count of the Farrow resampler, len(np.arange(0, Ts_old*(n-3) + Ts_old, Ts_new)); host only."""
+    v = ctypes.c_int64(0)
+    check(load().skdsp_farrow_len(int(n), float(Ts_old), float(Ts_new), ctypes.byref(v)))
+    return v.value
+
+
+def _farrow_flags(wide, f64):
+    return (FARROW_WIDE if wide else 0) | (FARROW_F64 if f64 else 0)
+
+
+def farrow(x, Ts_old, Ts_new, i_ord, alpha=0.5, wide=False, f64=False):
+    """digitalcom.farrow_resample on a host vector: wide=True gives float64 / complex128 results for a float32 / complex64 x,
+    f64=True runs such an x in float64 arithmetic."""
+    n_out = farrow_len(x.size, Ts_old, Ts_new)
+    y = np.empty(n_out, dtype=_WIDE.get(x.dtype, x.dtype) if wide else x.dtype)
+    check(load().skdsp_farrow(_ptr(x), x.size, code_of(x.dtype), float(Ts_old), float(Ts_new), int(i_ord), float(alpha),
+                              _farrow_flags(wide, f64), _ptr(y)))
+    return y
+
+
+def farrow_dev(xd, yd, Ts_old, Ts_new, i_ord, alpha=0.5, n0=0, count=None, wide=False, f64=False):
+    """Outputs [n0, n0 + count) of the Farrow resampler of device array xd into yd[0 .. count) (default: all from n0 on)."""
+    if count is None:
+        count = farrow_len(xd.n, Ts_old, Ts_new) - int(n0)
+    out_dt = _WIDE.get(xd.dtype, xd.dtype) if wide else xd.dtype
+    if yd.dtype != out_dt or yd.n < int(count):
+        raise ValueError("farrow_dev: y holds %d samples of %s, the call writes %d of %s" % (yd.n, yd.dtype, int(count), out_dt))
+    check(load().skdsp_farrow_dev(ctypes.c_void_p(xd.ptr), xd.n, xd.code, float(Ts_old), float(Ts_new), int(i_ord), float(alpha),
+                                  int(n0), int(count), _farrow_flags(wide, f64), ctypes.c_void_p(yd.ptr)))
 
 
 def downsample(x, M, p):

@@ -6,10 +6,61 @@ the GPU (sigsys.pulse_shape -> multirate_FIR.up -> fir_direct.hip / fir_ols.hip)
   qam_gray_encode_bb(n_symb, ns, mod, pulse, alpha, m_span, ext_data)   digitalcom.py:1584-1681
   mpsk_gray_encode_bb(n_symb, ns, mod, pulse, alpha, m_span, ext_data)  digitalcom.py:1742-1826
   qam_bb, mpsk_bb, gmsk_bb, rz_bits, time_delay (constant delay)         digitalcom.py:418-492, 613-667, 585-610, 998-1048, 1089-1131
+  farrow_resample(x, fs_old, fs_new, i_ord, alpha)                       digitalcom.py:53-235
+
+farrow_resample, the arbitrary-ratio resampler, is its own engine (csrc/farrow.hip): each output is a 4-tap FIR whose taps
+are polynomials in a fractional delay, evaluated on the GPU for all outputs at once (the reference loops over them in Python).
 """
+import math
+
 import numpy as np
 
+from . import _ffi, config
+
 from .sigsys import upsample, downsample, cic, rc_imp, sqrt_rc_imp, pulse_shape, _pulse  # noqa: F401  (re-exported like digitalcom.py:40-47)
+
+
+def _farrow_len(n, Ts_old, Ts_new):
+    """len(np.arange(0, Ts_old*(n-3) + Ts_old, Ts_new)) without the arange (what csrc/farrow_core.hpp's out_len computes)."""
+    if Ts_new == 0:
+        raise ZeroDivisionError("float division by zero")
+    q = (Ts_old * (n - 3) + Ts_old) / Ts_new
+    if math.isnan(q):
+        raise ValueError("arange: cannot compute length")
+    if math.isinf(q):
+        raise ValueError("Maximum allowed size exceeded")
+    return max(0, math.ceil(q))
+
+
+def farrow_resample(x, fs_old, fs_new, i_ord=3, alpha=1 / 2):
+    """Resample x from fs_old to fs_new, any ratio, with a Farrow interpolator of order i_ord (digitalcom.py:53-235).
+
+    Output j sits at t = j / fs_new; with n_old = floor(t fs_old) and mu its fractional part (both float64, rounded as the
+    reference rounds them) it is a cubic (i_ord=3), parabolic (i_ord=2, shaped by alpha) or linear (i_ord=1) interpolation
+    of x[n_old-2 .. n_old+1] -- one GPU kernel for all outputs (csrc/farrow.hip).  len(y) = len(np.arange(0, (len(x)-2)/fs_old,
+    1/fs_new)).  The result is float64 / complex128 like the reference's (float32 / complex64 inputs keep their own width
+    with config.strict_dtype = False); float32 / complex64 inputs are interpolated in float32 unless config.precision is
+    "double", float64 / complex128 ones always in float64.  Conventions beyond the reference's: integer arrays run as
+    float64 (the reference's lfilter rejects them), and x must be one-dimensional (ValueError otherwise)."""
+    if i_ord not in (1, 2, 3):
+        raise ValueError('Error: I_ord must 1, 2, or 3')
+    if np.size(x) == 0:
+        raise ValueError("v cannot be empty")   # (what the reference's lfilter -> np.convolve raises)
+    Ts_old = 1 / float(fs_old)
+    Ts_new = 1 / float(fs_new)
+    n_out = _farrow_len(len(x), Ts_old, Ts_new)
+    if not hasattr(x, "dtype"):
+        raise AttributeError("'%s' object has no attribute 'dtype'" % type(x).__name__)
+    if x.ndim != 1:
+        raise ValueError("farrow_resample: x must be one-dimensional (got shape %r)" % (x.shape,))
+    from .sigsys import _gpu_dtype
+    xg = np.ascontiguousarray(_gpu_dtype(x))
+    wide = bool(config.strict_dtype)
+    out_dt = np.result_type(xg.dtype, np.float64) if wide else xg.dtype
+    if n_out == 0:
+        return np.zeros(0, dtype=out_dt)
+    a = float(alpha) if i_ord == 2 else 0.5
+    return _ffi.farrow(xg, Ts_old, Ts_new, int(i_ord), a, wide=wide, f64=config.precision == "double")
 
 
 def _word_values(data, width):
