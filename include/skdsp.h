@@ -205,6 +205,14 @@ int skdsp_farrow_len(int64_t n, double Ts_old, double Ts_new, int64_t *n_out);
 int skdsp_farrow_dev(const void *x_dev, int64_t n, int dtype, double Ts_old, double Ts_new, int i_ord, double alpha, int64_t n0,
                      int64_t count, int wide, void *y_dev);
 int skdsp_farrow(const void *x, int64_t n, int dtype, double Ts_old, double Ts_new, int i_ord, double alpha, int wide, void *y);
+/* psd: the Welch primitive of sigsys.psd / my_psd / simple_sa (sigsys.py:2497-2585, 2457-2494, 1008-1084):
+ *   S[k] = sum_{i < nseg} | sum_{m < ns} window[m] x[i step + m] exp(-2 pi j k m / n_fft) |^2,   k = 0 .. n_fft-1, float64
+ * window: HOST array of ns doubles (used in float64 for every dtype, like the twiddles).  SKDSP_ERR_BADARG unless n_fft is a power of
+ * two in 64 ... 4096, 1 <= ns <= n_fft, step >= 1, nseg >= 1 and (nseg-1) step + ns <= n.  Samples behind the last segment
+ * are not used; the result is bit-identical from call to call. */
+int skdsp_psd_dev(const void *x_dev, int64_t n, int dtype, const double *window, int ns, int n_fft, int64_t step, int64_t nseg,
+                  double *S_dev);
+int skdsp_psd(const void *x, int64_t n, int dtype, const double *window, int ns, int n_fft, int64_t step, int64_t nseg, double *S);
 
 /* Host-pointer entry points of a float32/complex64 handle deliver y as float64/complex128 (the
  * reference's result dtype, multirate_helper.py:108 etc.): widened on the device before the copy

@@ -109,7 +109,7 @@ const OptEntry kOptTable[] = {
     {"device", &Options::device}, {"fir_algo", &Options::fir_algo}, {"dn_no_ols", &Options::dn_no_ols},
     {"fir_mm", &Options::fir_mm}, {"fir_bx", &Options::fir_bx}, 
     
-    {"ols_reserve", &Options::ols_reserve}, {"fir_bx_t16", &Options::fir_bx_t16}, {"ols_keep_overlap", &Options::ols_keep_overlap}, {"fir_dn_fold", &Options::fir_dn_fold}, {"fir_up_rep", &Options::fir_up_rep}, {"iir_seq", &Options::iir_seq}, {"iir_up_jump", &Options::iir_up_jump}, {"iir_dn_t96", &Options::iir_dn_t96}, {"iir_up_lean", &Options::iir_up_lean}, {"iir_planar", &Options::iir_planar}, 
+    {"ols_reserve", &Options::ols_reserve}, {"fir_bx_t16", &Options::fir_bx_t16}, {"ols_keep_overlap", &Options::ols_keep_overlap}, {"fir_dn_fold", &Options::fir_dn_fold}, {"fir_up_rep", &Options::fir_up_rep}, {"iir_seq", &Options::iir_seq}, {"psd_f32_image", &Options::psd_f32_image}, {"iir_up_jump", &Options::iir_up_jump}, {"iir_dn_t96", &Options::iir_dn_t96}, {"iir_up_lean", &Options::iir_up_lean}, {"iir_planar", &Options::iir_planar}, 
     {"iir_dn_full", &Options::iir_dn_full}, {"iir_no_mfma", &Options::iir_no_mfma}, 
     {"iir_two_pass", &Options::iir_two_pass}, {"iir_par", &Options::iir_par}, {"iir_par_v32", &Options::iir_par_v32}, {"iir_up_fused", &Options::iir_up_fused}, {"fir_up_ols_min", &Options::fir_up_ols_min}, {"fir_updn_fused", &Options::fir_updn_fused}, {"fir_up4k", &Options::fir_up4k}, {"fir_up4k_group", &Options::fir_up4k_group}, {"fir_up4k_staged", &Options::fir_up4k_staged}, {"fir_up2k", &Options::fir_up2k}, {"fir_dn4k", &Options::fir_dn4k}, {"fir_up_pair", &Options::fir_up_pair}, {"fir_up_rows_min", &Options::fir_up_rows_min}, {"iir_dn_compact", &Options::iir_dn_compact}, 
     {"shard_two_launches", &Options::shard_two_launches}, {"shard_probe", &Options::shard_probe}, {"shard_halo_state", &Options::shard_halo_state},
@@ -2176,6 +2176,30 @@ int skdsp_farrow(const void *x, int64_t n, int dtype, double Ts_old, double Ts_n
     if ((rc = ws_reserve(1, (size_t)n_out * esz_out + 256, &y_dev))) return rc;
     if ((rc = farrow_launch(x_dev, n, dtype, Ts_old, Ts_new, i_ord, alpha, 0, n_out, wide, y_dev, ctx().stream))) return rc;
     return stage_out(y, y_dev, (size_t)n_out * esz_out);
+}
+
+// ---------------------------------------------------------------- Welch primitive (sigsys.psd, my_psd, simple_sa)
+int skdsp_psd_dev(const void *x_dev, int64_t n, int dtype, const double *window, int ns, int n_fft, int64_t step, int64_t nseg,
+                  double *S_dev)
+{
+    int rc = psd_check(n, dtype, window, ns, n_fft, step, nseg);   // (argument errors need no device)
+    if (rc) return rc;
+    API_BEGIN;
+    return psd_launch(x_dev, n, dtype, window, ns, n_fft, step, nseg, S_dev, ctx().stream);
+}
+
+int skdsp_psd(const void *x, int64_t n, int dtype, const double *window, int ns, int n_fft, int64_t step, int64_t nseg, double *S)
+{
+    int rc = psd_check(n, dtype, window, ns, n_fft, step, nseg);
+    if (rc) return rc;
+    SK_CHECK(x && S, SKDSP_ERR_BADARG, "psd: null pointer");
+    API_BEGIN;
+    const int64_t used = (nseg - 1) * step + ns;   // samples behind the last segment are not even copied
+    void *x_dev = nullptr, *S_dev = nullptr;
+    if ((rc = stage_in(x, (size_t)used * dtype_size(dtype), &x_dev))) return rc;
+    if ((rc = ws_reserve(1, (size_t)n_fft * sizeof(double) + 256, &S_dev))) return rc;
+    if ((rc = psd_launch(x_dev, used, dtype, window, ns, n_fft, step, nseg, (double *)S_dev, ctx().stream))) return rc;
+    return stage_out(S, S_dev, (size_t)n_fft * sizeof(double));
 }
 
 int skdsp_set_option(const char *name, int value)

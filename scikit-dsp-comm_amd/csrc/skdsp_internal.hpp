@@ -82,6 +82,8 @@ struct Options {
     int dist_force_comm = 0;  // build an RCCL communicator for a 1-rank job too (exercises the plumbing on one GPU)
     int host_chunk_log2 = 22; // host-pointer entry points: samples per pipelined chunk (pinned double buffers)
     int host_pipeline = 1;    // 0: single staged copy in / kernel / copy out
+    int psd_f32_image = 0;    // the Welch primitive (psd.hip) on float32 / complex64 signals: 1 keeps the transform's LDS image in float32 (each pass
+                              // still computed in float64 and rounded once at its store): the 1e-6 contract only, not the per-bin one
     int host_multi_slot = 1;  // 0: host-pointer FIR calls stay on the caller's slot even when several are bound
 };
 Options &opt();
@@ -322,5 +324,11 @@ int fill_noise_launch(void *x_dev, int64_t n, int dtype, uint64_t seed, int64_t 
 int farrow_len(int64_t n, double ts_old, double ts_new, int64_t *n_out);   // host-only
 int farrow_launch(const void *x_dev, int64_t n, int dtype, double ts_old, double ts_new, int i_ord, double alpha, int64_t n0,
                   int64_t count, int flags, void *y_dev, hipStream_t s);   // outputs [n0, n0 + count) into y_dev
+
+// ---- Welch primitive (psd.hip) ----------------------------------------------
+// S_dev[k] = sum_{i < nseg} |FFT_{n_fft}(window * x[i step .. i step + ns))[k]|^2, float64; window is a host array of ns doubles
+int psd_check(int64_t n, int dtype, const double *window, int ns, int n_fft, int64_t step, int64_t nseg);   // host-only: the argument rules
+int psd_launch(const void *x_dev, int64_t n, int dtype, const double *window, int ns, int n_fft, int64_t step, int64_t nseg,
+               double *S_dev, hipStream_t s);
 
 }  // namespace skdsp

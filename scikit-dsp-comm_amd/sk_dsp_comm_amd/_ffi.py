@@ -34,7 +34,7 @@ SYMBOLS = [
     "skdsp_iir_filter_rows", "skdsp_iir_filter_rows_dev", "skdsp_sos_par_info", "skdsp_iir_sequential",
     "skdsp_sos_filter", "skdsp_sos_up", "skdsp_sos_dn",
     "skdsp_upsample", "skdsp_upsample_dev", "skdsp_downsample", "skdsp_downsample_dev", "skdsp_set_wide_output", "skdsp_destroy",
-    "skdsp_farrow_len", "skdsp_farrow_dev", "skdsp_farrow",
+    "skdsp_farrow_len", "skdsp_farrow_dev", "skdsp_farrow", "skdsp_psd_dev", "skdsp_psd",
     "skdsp_dist_unique_id", "skdsp_dist_init", "skdsp_dist_shutdown", "skdsp_dist_comm_count", "skdsp_dist_barrier",
     "skdsp_dist_allreduce_max", "skdsp_dist_allreduce_sum", "skdsp_dist_sendrecv", "skdsp_dist_allgather", "skdsp_dist_halo_exchange", "skdsp_fir_filter_shard_dev",
 ]
@@ -130,6 +130,10 @@ def load():
             L.skdsp_farrow_len.argtypes = [i64, dbl, dbl, p64]
             L.skdsp_farrow_dev.argtypes = [vp, i64, ci, dbl, dbl, ci, dbl, i64, i64, ci, vp]
             L.skdsp_farrow.argtypes = [vp, i64, ci, dbl, dbl, ci, dbl, ci, vp]
+        if hasattr(L, "skdsp_psd"):
+            pd = ctypes.POINTER(ctypes.c_double)
+            L.skdsp_psd_dev.argtypes = [vp, i64, ci, pd, ci, ci, i64, i64, vp]
+            L.skdsp_psd.argtypes = [vp, i64, ci, pd, ci, ci, i64, i64, vp]
         L.skdsp_dist_unique_id.argtypes = [vp]
         L.skdsp_dist_init.argtypes = [ci, ci, vp]
         L.skdsp_dist_comm_count.argtypes = [ctypes.POINTER(ci)]
@@ -714,6 +718,31 @@ def farrow_dev(xd, yd, Ts_old, Ts_new, i_ord, alpha=0.5, n0=0, count=None, wide=
         raise ValueError("farrow_dev: y holds %d samples of %s, the call writes %d of %s" % (yd.n, yd.dtype, int(count), out_dt))
     check(load().skdsp_farrow_dev(ctypes.c_void_p(xd.ptr), xd.n, xd.code, float(Ts_old), float(Ts_new), int(i_ord), float(alpha),
                                   int(n0), int(count), _farrow_flags(wide, f64), ctypes.c_void_p(yd.ptr)))
+
+
+def _psd_window(window):
+    w = np.ascontiguousarray(window, dtype=np.float64)
+    if w.ndim != 1:
+        raise ValueError("psd: the window must be one-dimensional")
+    return w, w.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+
+def psd_accum(x, window, n_fft, step, nseg):
+    """The Welch primitive on a host vector (csrc/psd.hip):
+    S[k] = sum_{i < nseg} |FFT_{n_fft}(window * x[i step : i step + len(window)])[k]|^2, k < n_fft, float64."""
+    w, wp = _psd_window(window)
+    S = np.empty(int(n_fft), dtype=np.float64)
+    check(load().skdsp_psd(_ptr(x), x.size, code_of(x.dtype), wp, w.size, int(n_fft), int(step), int(nseg), _ptr(S)))
+    return S
+
+
+def psd_accum_dev(xd, Sd, window, n_fft, step, nseg):
+    """The same from device array xd into the first n_fft float64 of device array Sd."""
+    w, wp = _psd_window(window)
+    if Sd.dtype != np.float64 or Sd.n < int(n_fft):
+        raise ValueError("psd_accum_dev: S holds %d samples of %s, the call writes %d of float64" % (Sd.n, Sd.dtype, int(n_fft)))
+    check(load().skdsp_psd_dev(ctypes.c_void_p(xd.ptr), xd.n, xd.code, wp, w.size, int(n_fft), int(step), int(nseg),
+                               ctypes.c_void_p(Sd.ptr)))
 
 
 def downsample(x, M, p):

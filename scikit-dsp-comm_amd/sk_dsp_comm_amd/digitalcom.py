@@ -7,6 +7,7 @@ the GPU (sigsys.pulse_shape -> multirate_FIR.up -> fir_direct.hip / fir_ols.hip)
   mpsk_gray_encode_bb(n_symb, ns, mod, pulse, alpha, m_span, ext_data)  digitalcom.py:1742-1826
   qam_bb, mpsk_bb, gmsk_bb, rz_bits, time_delay (constant delay)         digitalcom.py:418-492, 613-667, 585-610, 998-1048, 1089-1131
   farrow_resample(x, fs_old, fs_new, i_ord, alpha)                       digitalcom.py:53-235
+  my_psd(x, NFFT, Fs)                                                    digitalcom.py:1051-1086  (sigsys.my_psd: csrc/psd.hip)
 
 farrow_resample, the arbitrary-ratio resampler, is its own engine (csrc/farrow.hip): each output is a 4-tap FIR whose taps
 are polynomials in a fractional delay, evaluated on the GPU for all outputs at once (the reference loops over them in Python).
@@ -61,6 +62,13 @@ def farrow_resample(x, fs_old, fs_new, i_ord=3, alpha=1 / 2):
         return np.zeros(0, dtype=out_dt)
     a = float(alpha) if i_ord == 2 else 0.5
     return _ffi.farrow(xg, Ts_old, Ts_new, int(i_ord), a, wide=wide, f64=config.precision == "double")
+
+
+def my_psd(x, NFFT=2 ** 10, Fs=1):
+    """matplotlib.mlab.psd(x, NFFT, Fs) as two arrays (digitalcom.py:1051-1086): sigsys.my_psd under the reference's
+    parameter names.  Returns (Px, f)."""
+    from .sigsys import my_psd as _my_psd
+    return _my_psd(x, NFFT, Fs)
 
 
 def _word_values(data, width):

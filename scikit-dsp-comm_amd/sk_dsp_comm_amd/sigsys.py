@@ -15,6 +15,11 @@ Callers around the hot path, same signatures, the filtering on the
   nrz_bits / nrz_bits2            sigsys.py:2120-2211   lfilter(b, 1, zero-stuffed data) -> polyphase .up
   fft_filt_bank(x, h, ...)        sigsys.py:2588-2694   (8f-4) one FIR per band with frequency-shifted taps
 
+Spectrum estimation, one GPU primitive (csrc/psd.hip: windowed overlapping FFTs in LDS, |X|^2 summed in float64):
+  psd(x, n_fft, fs, overlap_percent, scale_noise)  sigsys.py:2497-2585   Welch, Hann window -> (Px, f)
+  my_psd(x, n_fft, fs)                             sigsys.py:2457-2494   mlab.psd defaults -> (Px, f)
+  simple_sa(x, NS, NFFT, fs, NAVG, window)         sigsys.py:1008-1084   zero-padded subrecords -> (f, Sx)
+
 upsample/downsample run on the GPU (resample.hip) and are bit-exact index moves; cic
 is host-side coefficient generation (a few dozen float64 taps) and stays in NumPy.
 Error conventions follow the reference (tests/golden/g10_conventions.json).
@@ -396,3 +401,167 @@ def fft_filt_bank(x_in, h_filt, n_fft2=512, n_bands2=0, bs=0.2, fs=1.0, n_band_o
         freq_axis = np.arange(-(2 * n_bands2 - 1) * step, n_bands2 * step + 2 * (step + 1), 2 * step) * fs / 2 / n_fft2
         freq_axis_desired = np.rint(freq_axis / (bs / 2)) * (bs / 2)
     return y, freq_axis, freq_axis_desired
+
+
+# ---- spectrum estimation: psd, my_psd, simple_sa (sigsys.py:2497-2585, 2457-2494, 1008-1084) -------------------------------
+def _psd_served(n_fft):
+    """What csrc/psd.hip serves: powers of two from 64 to 4096."""
+    return 64 <= n_fft <= 4096 and n_fft & (n_fft - 1) == 0
+
+
+def psd_accum_host(x, window, n_fft, step, nseg):
+    """Host float64 restatement of the Welch primitive (vectorised NumPy, any n_fft >= len(window)):
+    S[k] = sum_{i < nseg} |FFT_{n_fft}(window * x[i step : i step + len(window)])[k]|^2,  k < n_fft."""
+    w = np.asarray(window, dtype=np.float64)
+    ns = w.size
+    xd = np.ascontiguousarray(x, dtype=np.complex128 if np.iscomplexobj(x) else np.float64)
+    if nseg < 1 or step < 1 or (nseg - 1) * step + ns > xd.size or not 1 <= ns <= n_fft:
+        raise ValueError("psd: %d segments of %d samples, %d apart, do not fit %d samples" % (nseg, ns, step, xd.size))
+    S = np.zeros(n_fft)
+    it = xd.itemsize
+    blk = max(1, (1 << 21) // n_fft)
+    for i0 in range(0, nseg, blk):
+        k = min(blk, nseg - i0)
+        seg = np.lib.stride_tricks.as_strided(xd[i0 * step:], shape=(k, ns), strides=(step * it, it), writeable=False)
+        X = np.fft.fft(seg * w, n_fft, axis=1)
+        S += (X.real ** 2 + X.imag ** 2).sum(axis=0)
+    return S
+
+
+def _psd_accum(x, window, n_fft, step, nseg):
+    """The primitive for a one-dimensional array: on the GPU where csrc/psd.hip serves n_fft, else the host restatement."""
+    if not _psd_served(n_fft):
+        log.info("psd: n_fft = %d is not a power of two in 64 ... 4096: host float64 path", n_fft)
+        return psd_accum_host(x, window, n_fft, step, nseg)
+    xg = _gpu_dtype(x)
+    if config.precision == "double" and xg.dtype in (np.float32, np.complex64):
+        xg = xg.astype(np.result_type(xg.dtype, np.float64))
+    elif config.precision == "single" and xg.dtype in (np.float64, np.complex128):
+        xg = xg.astype(np.float32 if xg.dtype == np.float64 else np.complex64)
+    used = (nseg - 1) * step + len(window)
+    xg = np.ascontiguousarray(xg[:used])
+    if config.precision == "single":   # float32 LDS image: the 1e-6 contract, faster for long transforms
+        with _ffi.option("psd_f32_image", 1):
+            return _ffi.psd_accum(xg, window, n_fft, step, nseg)
+    return _ffi.psd_accum(xg, window, n_fft, step, nseg)
+
+
+def _psd_input(x, name):
+    """The input as a one-dimensional array (deliberate: the reference's behaviour for other shapes is an accident of
+    broadcasting, tests/golden/g16_conventions.json)."""
+    x = np.asarray(x)
+    if x.ndim != 1:
+        raise ValueError("%s: x must be one-dimensional (got shape %r)" % (name, x.shape))
+    if x.dtype.kind not in "biufc":
+        raise TypeError("%s: x must be numeric (got dtype %s)" % (name, x.dtype))
+    return x
+
+
+def _psd_segments(Q, n_fft, overlap_percent):
+    """(step, K) of psd: the hop n_fft - round(overlap_percent/100 n_fft) and the number of passes of the reference's loop
+    `while i*step + 1 + n_fft <= Q` (sigsys.py:2570)."""
+    step = n_fft - int(np.round(overlap_percent / 100 * n_fft))
+    if n_fft < 1 or step <= 0:
+        raise ValueError("psd: overlap_percent = %r leaves no positive hop for n_fft = %d" % (overlap_percent, n_fft))
+    return step, ((Q - 1 - n_fft) // step + 1 if Q > n_fft else 0)
+
+
+def psd(x, n_fft, fs=1, overlap_percent=50, scale_noise=True):
+    """Averaged periodogram (Welch) power spectral density estimate with a Hann window (sigsys.py:2497-2585).
+
+    K = number of segments of n_fft samples, n_fft - round(overlap_percent/100 n_fft) apart, that the reference's loop
+    condition i*step + 1 + n_fft <= len(x) admits (a record of exactly n_fft samples gives K = 0 and, like the reference,
+    an all-nan result).  scale_noise=True scales by 1/(K U n_fft) (white noise reads its variance), False by
+    1/(K n_fft^2 U2^2) (a bin-centred sinusoid reads its power).  Real x: n_fft//2 + 1 bins from 0 to fs/2; complex x:
+    n_fft bins from -fs/2.  Returns (Px, f), float64.  The segment transforms and their sum run on the GPU (csrc/psd.hip)
+    for n_fft a power of two in 64 ... 4096, else in the host restatement (psd_accum_host; logged at INFO).
+    Deliberate differences: an overlap_percent that leaves no positive hop raises ValueError (the reference never
+    terminates), and x must be one-dimensional."""
+    from scipy.signal import windows
+    n_fft = int(n_fft)
+    step, _ = _psd_segments(0, n_fft, overlap_percent)
+    x = _psd_input(x, "psd")
+    Q = len(x)
+    real = np.isrealobj(x)
+    w = windows.hann(n_fft)
+    U = sum(w ** 2) / n_fft
+    U2 = sum(w) / n_fft
+    K = _psd_segments(Q, n_fft, overlap_percent)[1]
+    S = _psd_accum(x, w, n_fft, step, K) if K > 0 else np.zeros(n_fft)
+    if real:
+        Px = S[:int(n_fft / 2) + 1].copy()
+        f = fs * np.arange(0, int(n_fft / 2 + 1)) / n_fft
+    else:
+        Px = np.hstack((S[int(n_fft / 2):], S[0:int(n_fft / 2)]))
+        f = fs * np.arange(-int(n_fft / 2), int(n_fft / 2)) / n_fft
+    if scale_noise:
+        Px /= (K * U * n_fft)
+    else:
+        Px /= (K * n_fft ** 2 * U2 ** 2)
+    return Px, f
+
+
+def my_psd(x, n_fft=2 ** 10, fs=1):
+    """matplotlib.mlab.psd(x, n_fft, fs) with its defaults, as two arrays (sigsys.py:2457-2494): np.hanning window, no
+    overlap, K = len(x)//n_fft segments (a shorter x is zero-padded to n_fft), the mean over segments divided by
+    fs sum(w^2); real x one-sided with every bin but DC (and Nyquist, n_fft even) doubled, complex x two-sided from -fs/2.
+    Returns (Px, f), float64; GPU / host split as in psd."""
+    n_fft = int(n_fft)
+    if n_fft < 1:
+        raise ValueError("my_psd: n_fft must be positive")
+    x = _psd_input(x, "my_psd")
+    if len(x) < n_fft:
+        x = np.concatenate([_gpu_dtype(x), np.zeros(n_fft - len(x), dtype=_gpu_dtype(x[:0]).dtype)])
+    real = np.isrealobj(x)
+    w = np.hanning(n_fft)
+    K = len(x) // n_fft
+    S = _psd_accum(x, w, n_fft, n_fft, K) / K
+    if real:
+        nf = (n_fft + 1) // 2 if n_fft % 2 else n_fft // 2 + 1
+        Px = S[:nf].copy()
+        f = np.fft.fftfreq(n_fft, 1 / fs)[:nf]
+        Px[1:-1 if n_fft % 2 == 0 else None] *= 2.
+        if n_fft % 2 == 0:
+            f[-1] *= -1
+    else:
+        c = (n_fft - 1) // 2 + 1 if n_fft % 2 else n_fft // 2
+        Px = np.roll(S, -c)
+        f = np.roll(np.fft.fftfreq(n_fft, 1 / fs), -c)
+    Px /= fs
+    Px /= (w ** 2).sum()
+    return Px, f
+
+
+def simple_sa(x, NS, NFFT, fs, NAVG=1, window='boxcar'):
+    """Averaged periodogram of NAVG windowed subrecords of NS samples, each zero-padded to NFFT (sigsys.py:1008-1084):
+    Sx = mean |FFT_NFFT(w x_k)|^2 / NFFT^2 with w = scipy.signal.get_window(window, NS, fftbins=False).  Only complex128
+    input is two-sided (NFFT bins from -fs/2); every other dtype, complex64 included, takes the one-sided branch
+    (NFFT//2 bins) as in the reference.  NAVG > len(x)//NS warns and returns (0, 0).  Returns (f, Sx), float64.
+    The reference's malformed log.info('K = ', K) is not reproduced."""
+    import warnings
+    from scipy.signal import get_window
+    if not hasattr(x, "dtype"):
+        raise AttributeError("'%s' object has no attribute 'dtype'" % type(x).__name__)
+    x = _psd_input(x, "simple_sa")
+    Nx = len(x)
+    K = int(Nx / NS)
+    if NAVG > K:
+        warnings.warn('NAVG exceeds number of available subrecords')
+        return 0, 0
+    NS, NFFT, NAVG = int(NS), int(NFFT), int(NAVG)
+    if NAVG < 1:
+        raise ZeroDivisionError("float division by zero")
+    if NS > NFFT:
+        raise ValueError("simple_sa: NS = %d exceeds NFFT = %d" % (NS, NFFT))
+    w = get_window(window, NS, fftbins=False)
+    Sx = _psd_accum(x, w, NFFT, NS, NAVG)
+    Sx /= float(NAVG)
+    Sx /= float(NFFT ** 2)
+    NFFTby2 = int(NFFT / 2)
+    if x.dtype != 'complex128':
+        f = fs * np.arange(NFFTby2) / float(NFFT)
+        Sx = Sx[0:NFFTby2]
+    else:
+        f = fs * np.hstack((np.arange(-NFFTby2, 0), np.arange(NFFTby2))) / float(NFFT)
+        Sx = np.hstack((Sx[NFFTby2:], Sx[0:NFFTby2]))
+    return f, Sx
