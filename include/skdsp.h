@@ -130,6 +130,20 @@ int skdsp_fir_dn_dev(skdsp_handle h, const void *x_dev, int64_t n, int64_t n_his
 int skdsp_fir_updn(skdsp_handle h, const void *x, int64_t n, int L, int M, void *y);
 int skdsp_fir_updn_dev(skdsp_handle h, const void *x_dev, int64_t n, int64_t n_hist, int L, int M, void *y_dev);
 
+/* ---- FIR bank: sigsys.fft_caf (sigsys.py:2696-2781) ------------------------ */
+/* nbands frequency-shifted copies of ONE FIR over ONE input, all from one pass over the input (csrc/fir_bank.hip):
+ *   band j:  g_j[n] = taps[n] * exp(2 pi i ((shifts[j] * n) mod period) / period),   n < ntaps
+ * (the reference rolls the 2 n_fft2-point spectrum of the taps by shifts[j] bins: period = 2 n_fft2; the phase is reduced in
+ * integers before any sine or cosine).  taps: ntaps float64 (taps_complex = 0) or complex128 (1).  dtype: SKDSP_F32 or
+ * SKDSP_C64, the SIGNAL's type; every output row is complex64.  SKDSP_ERR_BADARG unless 1 <= ntaps <= 2049, nbands >= 1,
+ * period >= 1 and the band tables (nbands x 32 KiB of transfer functions + nbands x ntaps x 16 bytes of float64 taps for the
+ * exact path of non-finite samples) stay within 256 MiB.  The handle is freed by skdsp_destroy. */
+int skdsp_fir_bank_create(const void *taps, int ntaps, int taps_complex, const int64_t *shifts, int nbands, int period, int dtype,
+                          skdsp_handle *out);
+/* y[j * row_stride + m] = sum_{k < ntaps} g_j[k] x[m - k],  x[< 0] = 0,  m < n, j < nbands; row_stride >= n in complex64
+ * elements; elements [n, row_stride) of a row are not written. */
+int skdsp_fir_bank_dev(skdsp_handle h, const void *x_dev, int64_t n, void *y_dev, int64_t row_stride);
+
 /* Is this cascade one that runs the reference's own recursion, sample by sample (csrc/iir_seq.hip)?  scipy.signal.sosfilt
  * (multirate_helper.py:173) evaluates a cascade section after section in float64; for ill-conditioned designs (a 40th-order Chebyshev)
  * that result is itself good to ~1e-6 only, and a scan would add to it.  skdsp_sos_create probes every cascade of more than 8 sections

@@ -109,7 +109,7 @@ const OptEntry kOptTable[] = {
     {"device", &Options::device}, {"fir_algo", &Options::fir_algo}, {"dn_no_ols", &Options::dn_no_ols},
     {"fir_mm", &Options::fir_mm}, {"fir_bx", &Options::fir_bx}, 
     
-    {"ols_reserve", &Options::ols_reserve}, {"fir_bx_t16", &Options::fir_bx_t16}, {"ols_keep_overlap", &Options::ols_keep_overlap}, {"fir_dn_fold", &Options::fir_dn_fold}, {"fir_up_rep", &Options::fir_up_rep}, {"iir_seq", &Options::iir_seq}, {"psd_f32_image", &Options::psd_f32_image}, {"iir_up_jump", &Options::iir_up_jump}, {"iir_dn_t96", &Options::iir_dn_t96}, {"iir_up_lean", &Options::iir_up_lean}, {"iir_planar", &Options::iir_planar}, 
+    {"ols_reserve", &Options::ols_reserve}, {"fir_bx_t16", &Options::fir_bx_t16}, {"fir_bank_per", &Options::fir_bank_per}, {"ols_keep_overlap", &Options::ols_keep_overlap}, {"fir_dn_fold", &Options::fir_dn_fold}, {"fir_up_rep", &Options::fir_up_rep}, {"iir_seq", &Options::iir_seq}, {"psd_f32_image", &Options::psd_f32_image}, {"iir_up_jump", &Options::iir_up_jump}, {"iir_dn_t96", &Options::iir_dn_t96}, {"iir_up_lean", &Options::iir_up_lean}, {"iir_planar", &Options::iir_planar}, 
     {"iir_dn_full", &Options::iir_dn_full}, {"iir_no_mfma", &Options::iir_no_mfma}, 
     {"iir_two_pass", &Options::iir_two_pass}, {"iir_par", &Options::iir_par}, {"iir_par_v32", &Options::iir_par_v32}, {"iir_up_fused", &Options::iir_up_fused}, {"fir_up_ols_min", &Options::fir_up_ols_min}, {"fir_updn_fused", &Options::fir_updn_fused}, {"fir_up4k", &Options::fir_up4k}, {"fir_up4k_group", &Options::fir_up4k_group}, {"fir_up4k_staged", &Options::fir_up4k_staged}, {"fir_up2k", &Options::fir_up2k}, {"fir_dn4k", &Options::fir_dn4k}, {"fir_up_pair", &Options::fir_up_pair}, {"fir_up_rows_min", &Options::fir_up_rows_min}, {"iir_dn_compact", &Options::iir_dn_compact}, 
     {"shard_two_launches", &Options::shard_two_launches}, {"shard_probe", &Options::shard_probe}, {"shard_halo_state", &Options::shard_halo_state},
@@ -1489,6 +1489,30 @@ int skdsp_fir_filter_dev(skdsp_handle hh, const void *x_dev, int64_t n, int64_t 
     SK_CHECK(n >= 0 && n_hist >= 0, SKDSP_ERR_BADARG, "fir_filter: negative length");
     std::lock_guard<std::mutex> lk(h->mu);
     return fir_filter_any(h, x_dev, n, n_hist, y_dev);
+}
+
+// FIR bank (fir_bank.hip): argument errors need no device
+int skdsp_fir_bank_create(const void *taps, int ntaps, int taps_complex, const int64_t *shifts, int nbands, int period, int dtype,
+                          skdsp_handle *out)
+{
+    SK_CHECK(out, SKDSP_ERR_BADARG, "fir_bank_create: null out");
+    HandleBase *h = nullptr;
+    int rc = fir_bank_create(taps, ntaps, taps_complex, shifts, nbands, period, dtype, &h);
+    if (rc) return rc;
+    *out = h;
+    return SKDSP_OK;
+}
+
+int skdsp_fir_bank_dev(skdsp_handle hh, const void *x_dev, int64_t n, void *y_dev, int64_t row_stride)
+{
+    HandleBase *h = as_handle<HandleBase>(hh, H_FIRBANK);
+    SK_CHECK(h, SKDSP_ERR_BADARG, "fir_bank: not a FIR bank handle");
+    SK_CHECK(n >= 0 && row_stride >= n, SKDSP_ERR_BADARG, "fir_bank: need 0 <= n <= row_stride (got n = %lld, row_stride = %lld)", (long long)n, (long long)row_stride);
+    if (n == 0) return SKDSP_OK;
+    SK_CHECK(x_dev && y_dev, SKDSP_ERR_BADARG, "fir_bank: null pointer");
+    API_BEGIN;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return fir_bank_launch(h, x_dev, n, y_dev, row_stride, ctx().stream);
 }
 
 int skdsp_fir_up_dev(skdsp_handle hh, const void *x_dev, int64_t n, int64_t n_hist, int L, void *y_dev)

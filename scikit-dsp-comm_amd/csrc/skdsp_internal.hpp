@@ -69,6 +69,7 @@ struct Options {
     int fir_dn4k = 1;         // multirate_FIR.dn through the frequency-domain decimator (fir_dn4k.hip): 1 where the cost model prefers it, 2 wherever it applies, 0 never (A/B switch)
     int fir_up4k_group = 4;   // phases (float32: pairs of phases) whose results a thread of that kernel holds before it stores: 4 (32 bytes per lane) or 2 (A/B switch)
     int fir_up4k_staged = 1;  // 0: four-pass groups of that kernel store each lane's own 32 bytes (A/B switch)
+    int fir_bank_per = 0;     // FIR bank (fir_bank.hip): bands per group; 0: the cost rule of bank_bands_per_group, k > 0: k per group (A/B switch; k >= the bands: one group)
     int fir_updn_fused = 1;   // 0: L / M through the overlap-save walk writes all n L outputs to scratch and copies every M-th (A/B switch)
     int iir_up_fused = 1;     // 0: multirate_IIR.up / rate_change.up write the zero-stuffed signal first (A/B switch)
     int shard_two_launches = 0; // sharded FIR: tile 0 as its own launch behind the halo event (instead of the in-kernel flag wait)
@@ -138,7 +139,7 @@ inline bool dtype_valid(int dt) { return dt >= 0 && dt <= 3; }
 constexpr int64_t kHeadroomBytes = 65536;
 
 // ------------------------------------------------------------------ handles
-enum HandleKind { H_FIR = 1, H_IIR = 2 };
+enum HandleKind { H_FIR = 1, H_IIR = 2, H_FIRBANK = 3 };
 
 struct HandleBase {
     int kind;
@@ -251,6 +252,12 @@ void fir_ols64_free(Ols64Plan *p);
 bool fir_ols64_up_supported(const FirHandle *h, int L);
 bool fir_ols64_up_pairs(const FirHandle *h, int L, int dec, const void *y_dev);
 int fir_ols64_up_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, int L, void *y_dev, hipStream_t s, int dec = 1, int64_t rows_pitch = 0, int paired = 0);
+
+// ---- FIR bank (fir_bank.hip): B frequency-shifted copies of one FIR over ONE input, sigsys.fft_caf (sigsys.py:2696-2781) --------------
+// band j = taps[n] exp(2 pi i ((shifts[j] n) mod period) / period); float32 / complex64 signals, complex64 rows; at most 2049 taps.
+// The handle (a HandleBase of kind H_FIRBANK) owns its tables; skdsp_destroy frees it.
+int fir_bank_create(const void *taps, int ntaps, int taps_complex, const int64_t *shifts, int nbands, int period, int dtype, HandleBase **out);
+int fir_bank_launch(HandleBase *h, const void *x_dev, int64_t n, void *y_dev, int64_t row_stride, hipStream_t s);   // row j at y + j row_stride, n outputs each, from rest
 
 // ---- IIR -----------------------------------------------------------------
 struct IirPlan;  // iir_scan.hip

@@ -27,7 +27,7 @@ SYMBOLS = [
     "skdsp_host_alloc", "skdsp_host_free", "skdsp_malloc", "skdsp_free", "skdsp_memcpy_h2d", "skdsp_memcpy_d2h", "skdsp_memcpy_d2d", "skdsp_memset",
     "skdsp_sync", "skdsp_timer_start", "skdsp_timer_stop", "skdsp_last_kernel_ms", "skdsp_fill_noise_dev",
     "skdsp_fir_create", "skdsp_fir_set_algo", "skdsp_fir_get_algo", "skdsp_fir_filter", "skdsp_fir_filter_dev",
-    "skdsp_fir_filter_rows", "skdsp_fir_filter_rows_dev", "skdsp_fir_filter_sharded",
+    "skdsp_fir_filter_rows", "skdsp_fir_filter_rows_dev", "skdsp_fir_filter_sharded", "skdsp_fir_bank_create", "skdsp_fir_bank_dev",
     "skdsp_fir_up", "skdsp_fir_up_dev", "skdsp_fir_dn", "skdsp_fir_dn_dev", "skdsp_fir_updn", "skdsp_fir_updn_dev",
     "skdsp_sos_create", "skdsp_tf_create", "skdsp_tf2sos", "skdsp_iir_filter", "skdsp_iir_filter_dev", "skdsp_iir_up",
     "skdsp_iir_up_dev", "skdsp_iir_dn", "skdsp_iir_dn_dev", "skdsp_iir_state_len", "skdsp_iir_filter_state_dev",
@@ -134,6 +134,9 @@ def load():
             pd = ctypes.POINTER(ctypes.c_double)
             L.skdsp_psd_dev.argtypes = [vp, i64, ci, pd, ci, ci, i64, i64, vp]
             L.skdsp_psd.argtypes = [vp, i64, ci, pd, ci, ci, i64, i64, vp]
+        if hasattr(L, "skdsp_fir_bank_create"):
+            L.skdsp_fir_bank_create.argtypes = [vp, ci, ci, p64, ci, ci, ci, pvp]
+            L.skdsp_fir_bank_dev.argtypes = [vp, vp, i64, vp, i64]
         L.skdsp_dist_unique_id.argtypes = [vp]
         L.skdsp_dist_init.argtypes = [ci, ci, vp]
         L.skdsp_dist_comm_count.argtypes = [ctypes.POINTER(ci)]
@@ -560,6 +563,38 @@ class FirKernel(_HostCalls):
     def filter_shard_dev(self, xd, yd, n=None):
         n = xd.n if n is None else n
         check(load().skdsp_fir_filter_shard_dev(ctypes.c_void_p(self.h), ctypes.c_void_p(xd.ptr), n, ctypes.c_void_p(yd.ptr)))
+
+
+class FirBank:
+    """A bank of frequency-shifted copies of one FIR over ONE float32 / complex64 signal (csrc/fir_bank.hip):
+    band j = taps[n] * exp(2j pi ((shifts[j] n) mod period) / period); every output row is complex64."""
+
+    def __init__(self, taps, shifts, period, dtype):
+        L = load()
+        taps = np.asarray(taps)
+        self.taps_complex = bool(np.iscomplexobj(taps))
+        t = np.ascontiguousarray(taps, dtype=np.complex128 if self.taps_complex else np.float64)
+        sh = np.ascontiguousarray(shifts, dtype=np.int64)
+        if t.ndim != 1 or sh.ndim != 1:
+            raise ValueError("FirBank: taps and shifts must be one-dimensional")
+        self.ntaps, self.nbands = int(t.size), int(sh.size)
+        self.dtype = np.dtype(dtype)
+        self.code = code_of(self.dtype)
+        h = ctypes.c_void_p(0)
+        check(L.skdsp_fir_bank_create(_ptr(t), self.ntaps, int(self.taps_complex), sh.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                      self.nbands, int(period), self.code, ctypes.byref(h)))
+        self.h = h.value
+        self._fin = weakref.finalize(self, _destroy, self.h)
+
+    def filter_dev(self, xd, yd, row_stride=None, n=None):
+        """Row j of the result at yd[j * row_stride : j * row_stride + n] (complex64), from rest; row_stride defaults to n."""
+        n = xd.n if n is None else int(n)
+        row_stride = n if row_stride is None else int(row_stride)
+        if xd.dtype != self.dtype or yd.dtype != np.complex64:
+            raise ValueError("FirBank: the signal must be %s and the rows complex64" % self.dtype)
+        if n < 0 or n > xd.n or row_stride < n or (self.nbands - 1) * row_stride + n > yd.n:
+            raise ValueError("FirBank: %d rows of %d samples, %d apart, do not fit the arrays" % (self.nbands, n, row_stride))
+        check(load().skdsp_fir_bank_dev(ctypes.c_void_p(self.h), ctypes.c_void_p(xd.ptr), n, ctypes.c_void_p(yd.ptr), row_stride))
 
 
 class IirKernel(_HostCalls):

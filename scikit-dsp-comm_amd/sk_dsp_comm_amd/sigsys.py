@@ -14,6 +14,8 @@ Callers around the hot path, same signatures, the filtering on the
   rc_imp / sqrt_rc_imp            sigsys.py:1847-1945   (host pulse design)
   nrz_bits / nrz_bits2            sigsys.py:2120-2211   lfilter(b, 1, zero-stuffed data) -> polyphase .up
   fft_filt_bank(x, h, ...)        sigsys.py:2588-2694   (8f-4) one FIR per band with frequency-shifted taps
+  fft_caf(x, h_ref, ...)          sigsys.py:2696-2781   streaming cross-ambiguity function: all frequency slices from ONE pass
+                                                        over the input (csrc/fir_bank.hip); fft_caf_host: its float64 host restatement
 
 Spectrum estimation, one GPU primitive (csrc/psd.hip: windowed overlapping FFTs in LDS, |X|^2 summed in float64):
   psd(x, n_fft, fs, overlap_percent, scale_noise)  sigsys.py:2497-2585   Welch, Hann window -> (Px, f)
@@ -350,6 +352,25 @@ def am_rx(x192):
     return m_rx8, t8, m_rx192, x_edet192
 
 
+def _band_walk(x_use, cdt, band_taps, n_tot, y):
+    """Rows y[j, :len(x_use)] = lfilter(band_taps(j), 1, x_use), j < n_tot: one complex-tap FIR handle and one pass of the existing
+    engines (fir_ols.hip / fir_ols64.hip / fir_direct.hip) per band over ONE device-resident input of dtype cdt; the bands in
+    batches of rows of one device block (2 GiB at most), one copy back per batch."""
+    n_use = len(x_use)
+    xd = _ffi.DeviceArray.from_host(np.ascontiguousarray(x_use, dtype=cdt))
+    per = max(1, min(n_tot, (2 << 30) // max(n_use * np.dtype(cdt).itemsize, 1)))
+    yd = _ffi.DeviceArray(n_use * per, cdt)
+    try:
+        for j0 in range(0, n_tot, per):
+            rows = min(per, n_tot - j0)
+            for j in range(rows):
+                _ffi.FirKernel(band_taps(j0 + j), _ffi.code_of(cdt)).filter_dev(xd, yd.window(j * n_use, n_use))
+            y[j0:j0 + rows, :n_use] = yd.to_host(0, rows * n_use).reshape(rows, n_use)
+    finally:
+        xd.free()
+        yd.free()
+
+
 def fft_filt_bank(x_in, h_filt, n_fft2=512, n_bands2=0, bs=0.2, fs=1.0, n_band_odd=True):
     """Streaming filter bank of 2*n_bands2+1 (or 2*n_bands2) bands spaced by ~bs Hz
     (sigsys.py:2588-2694).  The reference overlap-saves with a 2*n_fft2 FFT and rolls H by whole
@@ -378,22 +399,9 @@ def fft_filt_bank(x_in, h_filt, n_fft2=512, n_bands2=0, bs=0.2, fs=1.0, n_band_o
     n_use = (n_x // n_fft2) * n_fft2
     if n_use and n_tot:
         single = x_in.dtype in (np.float32, np.complex64) and not config.strict_dtype
-        cdt = np.complex64 if single else np.complex128
-        # one device-resident input; the bands in batches of rows of ONE device block (2 GiB at most), one copy back per batch
-        xd = _ffi.DeviceArray.from_host(np.ascontiguousarray(x_in[:n_use], dtype=cdt))
-        per = max(1, min(n_tot, (2 << 30) // max(n_use * np.dtype(cdt).itemsize, 1)))
-        yd = _ffi.DeviceArray(n_use * per, cdt)
-        try:
-            n = np.arange(len(h_filt))
-            for j0 in range(0, n_tot, per):
-                rows = min(per, n_tot - j0)
-                for j in range(rows):
-                    taps = h_filt * np.exp(2j * np.pi * shifts[j0 + j] * n / (2 * n_fft2))
-                    _ffi.FirKernel(taps, _ffi.code_of(cdt)).filter_dev(xd, yd.window(j * n_use, n_use))
-                y[j0:j0 + rows, :n_use] = yd.to_host(0, rows * n_use).reshape(rows, n_use)
-        finally:
-            xd.free()
-            yd.free()
+        n = np.arange(len(h_filt))
+        _band_walk(x_in[:n_use], np.complex64 if single else np.complex128,
+                   lambda j: h_filt * np.exp(2j * np.pi * shifts[j] * n / (2 * n_fft2)), n_tot, y)
     if n_band_odd:
         freq_axis = np.arange(-n_bands2 * step, n_bands2 * step + step, step) * fs / 2 / n_fft2
         freq_axis_desired = np.rint(freq_axis / bs) * bs
@@ -401,6 +409,111 @@ def fft_filt_bank(x_in, h_filt, n_fft2=512, n_bands2=0, bs=0.2, fs=1.0, n_band_o
         freq_axis = np.arange(-(2 * n_bands2 - 1) * step, n_bands2 * step + 2 * (step + 1), 2 * step) * fs / 2 / n_fft2
         freq_axis_desired = np.rint(freq_axis / (bs / 2)) * (bs / 2)
     return y, freq_axis, freq_axis_desired
+
+
+# ---- streaming cross-ambiguity function (sigsys.py:2696-2781) ---------------------------------------------------------------
+_CAF_BANK_MAX_TAPS = 2049          # csrc/fir_bank.hip: half a 4096-point tile of overlap
+_CAF_BANK_TABLE_CAP = 256 << 20    # bytes of band tables one bank handle may hold (skdsp_fir_bank_create)
+
+
+def _caf_band_taps(g, shift, period):
+    """g[n] exp(2j pi shift n / period) with the phase reduced in integers, (shift n) mod period, before any sine or cosine:
+    the filter whose period-point spectrum is np.roll(np.fft.fft(g, period), shift), for any integer shift."""
+    r = (int(shift) % int(period)) * np.arange(len(g), dtype=np.int64) % int(period)
+    return np.asarray(g) * np.exp(2j * np.pi * r / int(period))
+
+
+def _caf_setup(x_in, h_ref, n_fft2, n_slice2, bs, fs):
+    """The reference's checks, prints and integer parameters: (x, g, shifts, n_use, freq_axis, time_axis)."""
+    if len(h_ref) > n_fft2:
+        raise ValueError('Error: Must have Nfft2 = %d >= %d = len(h_ref)' % (n_fft2, len(h_ref)))
+    n_x = len(x_in)
+    n_tot = 2 * n_slice2 + 1
+    step = round(bs * 2 * n_fft2 / fs)
+    bs_actual = step * fs / (2 * n_fft2)
+    print('N_slice_step = %d and BS_Hz_actual = %3.2fHz' % (step, bs_actual))
+    print('N_slice_tot = %d and span_Hz = +/- %3.2fHz' % (n_tot, n_slice2 * bs_actual))
+    n_use = (n_x // n_fft2) * n_fft2
+    if n_use and not isinstance(x_in, np.ndarray):
+        x_in = x_in + 0j          # the reference's own statement inside its block loop: a list or tuple raises TypeError here
+    x = np.asarray(x_in)
+    if x.ndim != 1:
+        raise ValueError("fft_caf: x_in must be one-dimensional (got shape %r)" % (x.shape,))
+    g = np.conj(np.asarray(h_ref)[::-1])      # conjugate and reverse: correlation
+    shifts = [(j - n_slice2) * step for j in range(n_tot)]
+    freq_axis = np.arange(-n_slice2 * step, n_slice2 * step + step, step) * fs / 2 / n_fft2
+    time_axis = np.arange(0, n_x) / fs
+    return x, g, shifts, n_use, freq_axis, time_axis
+
+
+def _caf_rows(x_use, g, shifts, period, y):
+    """The device work of fft_caf: y[j, :len(x_use)] = lfilter(_caf_band_taps(g, shifts[j], period), 1, x_use) for every slice j.
+
+    float32 / complex64 signals (config.strict_dtype off), and every signal under config.precision == "single", with at most
+    2049 reference samples: the fused bank kernel (csrc/fir_bank.hip) -- the input is read and transformed once per tile for all
+    slices.  Everything else (float64 / complex128 signals, longer references, precision "double", strict_dtype): one pass of the
+    existing FIR engines per slice (_band_walk), in complex64 for float32 / complex64 signals with strict_dtype off, else complex128."""
+    n_use, n_tot, P = len(x_use), len(shifts), len(g)
+    single_in = x_use.dtype in (np.float32, np.complex64)
+    bank = P <= _CAF_BANK_MAX_TAPS and config.precision != "double" and ((single_in and not config.strict_dtype) or config.precision == "single")
+    if not bank:
+        cdt = np.complex64 if single_in and not config.strict_dtype and config.precision != "double" else np.complex128
+        log.info("fft_caf: %d slices of %d taps over %s input through one FIR pass per slice (%s)", n_tot, P, x_use.dtype, np.dtype(cdt))
+        _band_walk(x_use, cdt, lambda j: _caf_band_taps(g, shifts[j], period), n_tot, y)
+        return
+    sdt = np.complex64 if np.iscomplexobj(x_use) else np.float32
+    xd = _ffi.DeviceArray.from_host(np.ascontiguousarray(x_use, dtype=sdt))
+    # the slices in batches of rows of ONE device block (2 GiB at most) and one handle's table budget, one copy back per batch
+    per = max(1, min(n_tot, (2 << 30) // (n_use * 8), _CAF_BANK_TABLE_CAP // (32768 + 16 * P)))
+    yd = _ffi.DeviceArray(n_use * per, np.complex64)
+    try:
+        for j0 in range(0, n_tot, per):
+            rows = min(per, n_tot - j0)
+            _ffi.FirBank(g, shifts[j0:j0 + rows], period, sdt).filter_dev(xd, yd, n_use)
+            y[j0:j0 + rows, :n_use] = yd.to_host(0, rows * n_use).reshape(rows, n_use)
+    finally:
+        xd.free()
+        yd.free()
+
+
+def fft_caf(x_in, h_ref, n_fft2=1024, n_slice2=0, bs=0.1, fs=1.0):
+    """Streaming cross-ambiguity function with 2*n_slice2+1 frequency slices centred on f = 0 (sigsys.py:2696-2781).
+
+    The reference overlap-saves with a 2*n_fft2 FFT and rolls the spectrum of g = conj(h_ref[::-1]) by s_j = (j - n_slice2) * step
+    bins per slice, step = round(bs*2*n_fft2/fs).  Rolling by s_j bins IS the filter g_j[n] = g[n] exp(2j pi s_j n / (2 n_fft2)), and
+    the kept half of each block holds no circular wrap because len(h_ref) <= n_fft2, so
+        y[j, m] = sum_{n < len(h_ref)} g_j[n] x[m - n],  x[< 0] = 0,  m < (len(x) // n_fft2) * n_fft2;   y[j, m] = 0 beyond
+    which is what runs here: all slices off ONE pass over the device-resident input (csrc/fir_bank.hip) for float32 / complex64
+    signals with config.strict_dtype off and for every signal under config.precision == "single" (within 1e-6 of each row's peak);
+    one FIR pass per slice on the existing engines otherwise (float64 / complex128 signals: 1e-12; logged at INFO).
+    Returns (y_caf_stream[2*n_slice2+1, len(x_in)] complex128, freq_axis, time_axis) and prints the reference's two lines.
+    Deliberate differences: a non-finite sample stays inside the len(h_ref) outputs per row that multiply it (the reference's
+    FFT form spreads it over the whole 2*n_fft2 block of every slice), and x_in must be one-dimensional (the reference returns a
+    meaningless (slices, 2) array for 2-D input): tests/golden/g17_conventions.json."""
+    x, g, shifts, n_use, freq_axis, time_axis = _caf_setup(x_in, h_ref, n_fft2, n_slice2, bs, fs)
+    y = np.zeros((len(shifts), len(x)), dtype=complex)
+    if n_use and len(g):
+        _caf_rows(_gpu_dtype(x[:n_use]), g, shifts, 2 * n_fft2, y)
+    return y, freq_axis, time_axis
+
+
+def fft_caf_host(x_in, h_ref, n_fft2=1024, n_slice2=0, bs=0.1, fs=1.0):
+    """Host float64 restatement of fft_caf: the reference's block-FFT form (sigsys.py:2752-2777) with all blocks of a slice in one
+    batched transform -- overlap-save on blocks of 2*n_fft2 samples, the spectrum of conj(h_ref[::-1]) rolled by whole bins per slice,
+    the upper half of every block kept.  Same arguments, checks, printed lines and return value as fft_caf."""
+    x, g, shifts, n_use, freq_axis, time_axis = _caf_setup(x_in, h_ref, n_fft2, n_slice2, bs, fs)
+    y = np.zeros((len(shifts), len(x)), dtype=complex)
+    if n_use and len(g):
+        F = int(n_fft2)
+        K = n_use // F
+        xp = np.concatenate([np.zeros(F, dtype=complex), x[:n_use].astype(complex)])
+        it = xp.itemsize
+        blocks = np.lib.stride_tricks.as_strided(xp, shape=(K, 2 * F), strides=(F * it, it), writeable=False)
+        X = np.fft.fft(blocks, axis=1)
+        H = np.fft.fft(g, 2 * F)
+        for j, s in enumerate(shifts):
+            y[j, :n_use] = np.fft.ifft(np.roll(H, s) * X, axis=1)[:, F:].reshape(n_use)
+    return y, freq_axis, time_axis
 
 
 # ---- spectrum estimation: psd, my_psd, simple_sa (sigsys.py:2497-2585, 2457-2494, 1008-1084) -------------------------------
