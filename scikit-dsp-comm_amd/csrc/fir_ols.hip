@@ -44,7 +44,8 @@ struct OlsArgs {
     int ov, V, a0;  // a0 = ov / 512: first stored 512-block
     // The first a0 and the last a0 512-sample blocks of a tile are what it shares with its neighbours (the overlap it reads from the previous tile's range, and
     // the range the next tile will read as ITS overlap).  keep = a0: those blocks are requested with ordinary loads, so that the lines stay in the XCD's L2 for the
-    // neighbour (a nontemporal line is the first to be evicted); the blocks in between stay nontemporal.  0: every load nontemporal (round 5).
+    // neighbour (a nontemporal line is the first to be evicted); the blocks in between stay nontemporal.  0: every load nontemporal (round 5); 8: every
+    // load ordinary.  (load_tile: the complex64 tiles of .filter, .dn and .up; the float32 forms request everything nontemporal.)
     int keep;
     int aligned;    // x and y element-aligned (8 bytes complex64, 4 bytes float32)
     int64_t ntiles;
@@ -95,6 +96,13 @@ __device__ __forceinline__ void wait_halo(const OlsArgs &A)
     __syncthreads();
 }
 
+// OlsArgs::keep from the option ols_keep_overlap: 0 all nontemporal, 1 the shared blocks ordinary, 2 all ordinary
+static inline int ols_keep_blocks(int a0)
+{
+    const int o = opt().ols_keep_overlap;
+    return o == 0 ? 0 : (o == 1 ? a0 : 8);
+}
+
 // volatile 16-byte load: keeps the request at its program position (the scheduler would
 // otherwise sink a prefetch down to its first use to save registers)
 __device__ __forceinline__ float4 vld(const volatile float4 *p)
@@ -104,25 +112,47 @@ __device__ __forceinline__ float4 vld(const volatile float4 *p)
     return r;
 }
 
+// The 16 requests of an interior tile with the cache policy as a compile-time constant: blocks a < KEEP and a >= 16 - KEEP with ordinary loads, the
+// others nontemporal.  Block index AND policy are template arguments, so that each request is one load from the start: written as
+// `if (a < keep || a >= 16 - keep) nv = *src; else nv = __builtin_nontemporal_load(src);` in a loop over a -- with a run-time keep, and just the
+// same with a constant one, since the loop is unrolled later -- hipcc first merges the two loads of one address into ONE ordinary load: no x load
+// has carried the hint since round 6, whatever the option said.
+template <int KEEP, int A> __device__ __forceinline__ void load_tile_block(const v4f_t *src, cf *v)
+{
+    v4f_t nv;
+    if constexpr (A < KEEP || A >= 16 - KEEP) nv = src[A * 256];   // (a block a neighbouring tile reads too)
+    else nv = __builtin_nontemporal_load(src + A * 256);
+    const float4 f = make_float4(nv.x, nv.y, nv.z, nv.w);
+    v[2 * A] = lo(f);
+    v[2 * A + 1] = hi(f);
+    if constexpr (A < 15) load_tile_block<KEEP, A + 1>(src, v);
+}
+template <int KEEP> __device__ __forceinline__ void load_tile_blocks(const cf *x0, int t, cf *v)
+{
+    // opaque copy of t: stops LICM from hoisting 16 loop-invariant 64-bit addresses (which
+    // were then spilled and reloaded in front of every load)
+    int tt = t;
+    asm volatile("" : "+v"(tt));
+    load_tile_block<KEEP, 0>(reinterpret_cast<const v4f_t *>(x0) + (unsigned)tt, v);
+}
+
 // x[in0 + 512 a + 2 t + e] -> v[2a+e]; zero outside [-n_hist, n)
 __device__ __forceinline__ void load_tile(const OlsArgs &A, int64_t tile, int t, cf *v)
 {
     const int64_t in0 = tile * A.V - A.ov;
     const bool interior = A.aligned && in0 >= -A.n_hist && in0 + kN <= A.n;
     if (interior) {
-        // opaque copy of t: stops LICM from hoisting 16 loop-invariant 64-bit addresses (which
-        // were then spilled and reloaded in front of every load)
-        int tt = t;
-        asm volatile("" : "+v"(tt));
-#pragma unroll
-        for (int a = 0; a < 16; ++a) {
-            const v4f_t *src = reinterpret_cast<const v4f_t *>(A.x + in0) + (unsigned)(a * 256 + tt);
-            v4f_t nv;
-            if (a < A.keep || a >= 16 - A.keep) nv = *src;   // (wave-uniform: the blocks a neighbouring tile reads too)
-            else nv = __builtin_nontemporal_load(src);
-            const float4 f = make_float4(nv.x, nv.y, nv.z, nv.w);
-            v[2 * a] = lo(f);
-            v[2 * a + 1] = hi(f);
+        // one copy of the 16 loads per value of keep a plan can produce (wave-uniform switch, as for the stores of store_tile)
+        switch (A.keep) {
+            case 0: load_tile_blocks<0>(A.x + in0, t, v); break;
+            case 1: load_tile_blocks<1>(A.x + in0, t, v); break;
+            case 2: load_tile_blocks<2>(A.x + in0, t, v); break;
+            case 3: load_tile_blocks<3>(A.x + in0, t, v); break;
+            case 4: load_tile_blocks<4>(A.x + in0, t, v); break;
+            case 5: load_tile_blocks<5>(A.x + in0, t, v); break;
+            case 6: load_tile_blocks<6>(A.x + in0, t, v); break;
+            case 7: load_tile_blocks<7>(A.x + in0, t, v); break;
+            default: load_tile_blocks<8>(A.x + in0, t, v); break;   // (8: every block is shared -- or ols_keep_overlap = 2 -- all ordinary)
         }
     } else {
         int tt = t;   // (opaque copy: the 64-bit lane offset of this edge-tile path is not kept -- spilled -- across the tile loop)
@@ -1094,7 +1124,7 @@ int fir_ols_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, void 
     A.n = n;
     A.n_hist = n_hist;
     A.T1 = p->T1; A.T2 = p->T2; A.Hp = p->Hp;
-    A.ov = p->ov; A.V = p->V; A.a0 = p->ov / 512; A.keep = opt().ols_keep_overlap ? A.a0 : 0;
+    A.ov = p->ov; A.V = p->V; A.a0 = p->ov / 512; A.keep = ols_keep_blocks(A.a0);
     const bool real = h->dtype == SKDSP_F32;
     // element alignment is all the vector accesses need: tile starts are odd multiples of the
     // element size anyway (V = 8192 - (Ntaps-1) is odd for even tap counts)
@@ -1193,7 +1223,7 @@ static int up_walk(FirHandle *h, int kind, const void *x, int64_t n, int64_t n_h
     A.n = n;
     A.n_hist = n_hist;
     A.T1 = p->T1; A.T2 = p->T2; A.Hp = p->Hp;
-    A.ov = p->ov; A.V = p->V; A.a0 = p->ov / 512; A.keep = opt().ols_keep_overlap ? A.a0 : 0;
+    A.ov = p->ov; A.V = p->V; A.a0 = p->ov / 512; A.keep = ols_keep_blocks(A.a0);
     const int esz = h->dtype == SKDSP_F32 ? 4 : 8;
     A.aligned = xr ? (((uintptr_t)x & 3) == 0 && ((uintptr_t)y & (L % 2 ? 3 : 7)) == 0) : ((((uintptr_t)x) | ((uintptr_t)y)) & (real ? 3 : 7)) == 0;
     int64_t ntiles = (n + p->V - 1) / p->V;
@@ -1255,7 +1285,7 @@ int fir_ols_rep_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, i
     A.n = n * L;                  // (the rate the tiles live at)
     A.n_hist = n_hist * L;
     A.T1 = p->T1; A.T2 = p->T2; A.Hp = p->Hp;
-    A.ov = p->ov; A.V = p->V; A.a0 = p->ov / 512; A.keep = opt().ols_keep_overlap ? A.a0 : 0;
+    A.ov = p->ov; A.V = p->V; A.a0 = p->ov / 512; A.keep = ols_keep_blocks(A.a0);
     A.aligned = ((((uintptr_t)x) | ((uintptr_t)y)) & (real ? 3 : 7)) == 0;
     int64_t ntiles = (A.n + p->V - 1) / p->V;
     if (real) ntiles = (ntiles + 1) / 2;
