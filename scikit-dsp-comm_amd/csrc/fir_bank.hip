@@ -15,7 +15,7 @@
 // its loop, recomputes the outputs it stored for it by the direct sum in float64 over that band's modulated taps.
 #include "skdsp_internal.hpp"
 #include "ols4k_tables.hpp"
-#include <memory>
+#include "tile_walk.hpp"
 
 namespace skdsp {
 
@@ -27,16 +27,9 @@ constexpr int64_t kBankTableCap = (int64_t)256 << 20;   // bytes of band tables 
 struct FirBankHandle : HandleBase {
     int ntaps = 0, nbands = 0, ov = 0, V = 0;
     bool xr = false;             // float32 signal
-    float2 *tw = nullptr, *T2 = nullptr;
-    float4 *Hp = nullptr;        // nbands x 2048 float4
-    double *g64 = nullptr;       // nbands x ntaps complex128 (interleaved): the bands' taps as the careful path reads them
-    ~FirBankHandle() override
-    {
-        if (tw) (void)hipFree(tw);
-        if (T2) (void)hipFree(T2);
-        if (Hp) (void)hipFree(Hp);
-        if (g64) (void)hipFree(g64);
-    }
+    DevTable<float2> tw, T2;
+    DevTable<float4> Hp;         // nbands x 2048 float4
+    DevTable<double> g64;        // nbands x ntaps complex128 (interleaved): the bands' taps as the careful path reads them
 };
 
 struct BankArgs {
@@ -138,13 +131,7 @@ template <bool XR> __global__ __launch_bounds__(256, 2) void bank4k_kernel(BankA
     __shared__ unsigned long long noted_word;   // poisoned items, by walk step (careful.hpp)
     const int t = threadIdx.x;
     if (t == 0) noted_word = 0;
-    {
-        const cf w = A.T2[t];
-        T2f[t] = w;
-        T2t[(t & 15) * 16 + (t >> 4)] = w;
-#pragma unroll
-        for (int k = 0; k < 15; ++k) twl[k * 256 + t] = A.tw[k * 256 + t];
-    }
+    walk::twiddles_4k(t, A.T2, A.tw, T2f, T2t, twl);
     __syncthreads();
     int64_t step = 0;
     for (int64_t item = blockIdx.x; item < A.items; item += gridDim.x, ++step) {
@@ -269,16 +256,11 @@ int fir_bank_create(const void *taps, int ntaps, int taps_complex, const int64_t
     std::vector<float2> tw, T2;
     make_tw(tw);
     make_T2(T2);
-    hipError_t e;
-    if ((e = hipMalloc((void **)&h->tw, tw.size() * sizeof(float2))) != hipSuccess ||
-        (e = hipMalloc((void **)&h->T2, T2.size() * sizeof(float2))) != hipSuccess ||
-        (e = hipMalloc((void **)&h->Hp, Hp.size() * sizeof(float4))) != hipSuccess ||
-        (e = hipMalloc((void **)&h->g64, g.size() * sizeof(cd))) != hipSuccess ||
-        (e = hipMemcpy(h->tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(h->T2, T2.data(), T2.size() * sizeof(float2), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(h->Hp, Hp.data(), Hp.size() * sizeof(float4), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(h->g64, g.data(), g.size() * sizeof(cd), hipMemcpyHostToDevice)) != hipSuccess)
-        return hip_fail(e, "fir_bank tables", __FILE__, __LINE__);
+    int rc = h->tw.upload(tw);
+    if (!rc) rc = h->T2.upload(T2);
+    if (!rc) rc = h->Hp.upload(Hp);
+    if (!rc) rc = h->g64.upload(reinterpret_cast<const double *>(g.data()), 2 * g.size());
+    if (rc) return rc;
     *out = h.release();
     return SKDSP_OK;
 }
@@ -292,7 +274,7 @@ int fir_bank_launch(HandleBase *hb, const void *x, int64_t n, void *y, int64_t r
     SK_CHECK((((uintptr_t)x) & (h->xr ? 3 : 7)) == 0 && (((uintptr_t)y) & 7) == 0, SKDSP_ERR_BADARG, "fir_bank: x / y not element-aligned");
     BankArgs A;
     A.x = x; A.y = static_cast<cf *>(y); A.n = n; A.row_stride = row_stride;
-    A.tw = h->tw; A.T2 = h->T2; A.Hp = h->Hp; A.g64 = h->g64;
+    A.tw = h->tw.dev; A.T2 = h->T2.dev; A.Hp = h->Hp.dev; A.g64 = h->g64.dev;
     A.ntaps = h->ntaps; A.nbands = h->nbands;
     A.ov = h->ov; A.V = h->V; A.a0 = h->ov / 256;
     A.ntiles = (n + h->V - 1) / h->V;

@@ -14,6 +14,7 @@
 // Algorithmic bytes: 8 B x (n + n / M) complex64, 4 B x (n + n / M) float32.
 #include "skdsp_internal.hpp"
 #include "ols4k_tables.hpp"
+#include "tile_walk.hpp"
 
 namespace skdsp {
 
@@ -21,10 +22,10 @@ using namespace ols4k;
 typedef float v4f_t __attribute__((ext_vector_type(4)));
 typedef float v2f_t __attribute__((ext_vector_type(2)));
 
-struct Dn4kPlan {
-    int M = 0, T = 0, ov = 0, V = 0;
-    float2 *tw = nullptr, *T2 = nullptr;
-    float4 *Hp = nullptr;
+struct Dn4kPlan : TilePlan {   // key = M
+    int ov = 0, V = 0;
+    DevTable<float2> tw, T2;
+    DevTable<float4> Hp;
 };
 
 struct Dn4kArgs {
@@ -122,37 +123,6 @@ template <bool REAL> __device__ __noinline__ void dn4k_load_edge(const void *x, 
     }
 }
 
-__device__ __forceinline__ float4 dn4k_vld(const volatile float4 *p)
-{
-    float4 r;
-    r.x = p->x; r.y = p->y; r.z = p->z; r.w = p->w;
-    return r;
-}
-__device__ __forceinline__ void dn4k_load_H(const Dn4kArgs &A, int r, int t, float4 *hh)
-{
-    int tt = t;
-    asm volatile("" : "+v"(tt));
-    const volatile float4 *hp = reinterpret_cast<const volatile float4 *>(A.Hp) + (size_t)r * 2048;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) hh[k] = dn4k_vld(hp + (unsigned)(k * 256 + tt));
-}
-__device__ __forceinline__ void dn4k_settle(const float4 *hh)
-{
-#pragma unroll
-    for (int k = 0; k < 8; k += 4)
-        asm volatile("" ::"v"(hh[k].x), "v"(hh[k].y), "v"(hh[k].z), "v"(hh[k].w), "v"(hh[k + 1].x), "v"(hh[k + 1].y), "v"(hh[k + 1].z), "v"(hh[k + 1].w),
-                     "v"(hh[k + 2].x), "v"(hh[k + 2].y), "v"(hh[k + 2].z), "v"(hh[k + 2].w), "v"(hh[k + 3].x), "v"(hh[k + 3].y), "v"(hh[k + 3].z), "v"(hh[k + 3].w)
-                     : "memory");
-}
-// "these values, in these registers, now" (see fir_up2k.hip: hipcc otherwise carries a finished transform in a form of its own)
-__device__ __forceinline__ void dn4k_pin(cf *v)
-{
-#pragma unroll
-    for (int i = 0; i < 16; i += 8)
-        asm volatile("" : "+v"(v[i].x), "+v"(v[i].y), "+v"(v[i + 1].x), "+v"(v[i + 1].y), "+v"(v[i + 2].x), "+v"(v[i + 2].y), "+v"(v[i + 3].x), "+v"(v[i + 3].y),
-                     "+v"(v[i + 4].x), "+v"(v[i + 4].y), "+v"(v[i + 5].x), "+v"(v[i + 5].y), "+v"(v[i + 6].x), "+v"(v[i + 6].y), "+v"(v[i + 7].x), "+v"(v[i + 7].y));
-}
-
 // y[out0 + 256 (a - a0) + t] = v[a] for a >= a0 (float32: tile A from the real parts, tile B from the imaginary parts)
 template <bool REAL> __device__ __forceinline__ void dn4k_store(const Dn4kArgs &A, int64_t tile, int t, const cf *v)
 {
@@ -177,20 +147,6 @@ template <bool REAL> __device__ __forceinline__ void dn4k_store(const Dn4kArgs &
             if (whole || s < lim) __builtin_nontemporal_store(v2f_t{v[a].x, v[a].y}, yp + tt);
         }
     }
-}
-
-// pass 2 of the forward transform with the caller's registers as its working array (ols4k_core.hpp's fwd_pass2 keeps an array of its own)
-__device__ __forceinline__ void dn4k_fwd_pass2(int t, const cf *T2, cf *img, cf *w)
-{
-    const int k1 = t >> 4, c = t & 15;
-#pragma unroll
-    for (int b = 0; b < 16; ++b) w[b] = img[unit(k1, b, c)];
-    dft16_f(w);
-    img[unit(k1, 0, c)] = w[P16(0)];
-    static_for<1, 16>([&](auto kc) {
-        constexpr int k2 = decltype(kc)::value;
-        img[unit(k1, k2, c)] = cmul(w[P16(k2)], T2[k2 * 16 + c]);
-    });
 }
 
 // A poisoned tile (one inf / nan among the M x 4096 inputs of a tile makes all of its outputs non-finite, where the reference confines the
@@ -227,16 +183,9 @@ template <bool REAL, int MS> __global__ __launch_bounds__(256, 2) void dn4k_kern
     __shared__ unsigned long long dn_noted;   // poisoned tiles, by walk step (careful.hpp)
     const int t = threadIdx.x;
     if (t == 0) dn_noted = 0;
-    {
-        const cf w = A.T2[t];
-        T2f[t] = w;
-        T2t[(t & 15) * 16 + (t >> 4)] = w;
-#pragma unroll
-        for (int k = 0; k < 15; ++k) twl[k * 256 + t] = A.tw[k * 256 + t];
-    }
+    walk::twiddles_4k(t, A.T2, A.tw, T2f, T2t, twl);
     __syncthreads();
-    int64_t tile = (gridDim.x % 8 == 0) ? (int64_t)(blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8 : (int64_t)blockIdx.x;
-    auto tile_first = [&]() -> int64_t { return (gridDim.x % 8 == 0) ? (int64_t)(blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8 : (int64_t)blockIdx.x; };
+    int64_t tile = walk::first_tile();
     cf in[MS * 16];         // the phase signals of the tile; each is transformed in place
     bool have_in = false;   // `in` holds the phase signals of `tile` (requested ahead: interior tiles only)
     for (; tile < A.ntiles; tile += gridDim.x) {
@@ -259,15 +208,15 @@ template <bool REAL, int MS> __global__ __launch_bounds__(256, 2) void dn4k_kern
         static_for<0, MS>([&](auto jc) __attribute__((always_inline)) {
             constexpr int j = decltype(jc)::value;
             float4 hh[8];
-            dn4k_load_H(A, j, t, hh);
+            walk::load_H(A.Hp, j, t, hh);
             cf *Z = in + 16 * j;
             fwd_pass1(t, Z, twl, img);
             __syncthreads();
-            dn4k_fwd_pass2(t, T2f, img, Z);   // (wave-local from here to the product)
+            fwd_pass2(t, T2f, img, Z);   // (wave-local from here to the product)
             fwd_pass3(t, img, Z);
-            dn4k_pin(Z);
+            walk::pin<16>(Z);
             if (j == 0) mul_H(hh, Z, acc); else mac_H(hh, Z, acc);
-            dn4k_pin(acc);
+            walk::pin<16>(acc);
             __syncthreads();   // every wave has read the image of this transform before the next one (or the inverse) overwrites it
         });
         if (pre_next) dn4k_load_interior<REAL, MS>(A, tile + gridDim.x, 0, t, in);   // the phase signals are dead: the next tile's, with the inverse transform to arrive
@@ -276,37 +225,18 @@ template <bool REAL, int MS> __global__ __launch_bounds__(256, 2) void dn4k_kern
         __syncthreads();
         inv_pass1(t, twl, img, acc);
         __syncthreads();
-        dn4k_pin(acc);
-        if (pre_next) static_for<0, MS>([&](auto jc) __attribute__((always_inline)) { dn4k_pin(in + 16 * decltype(jc)::value); });   // (waited for in front of the stores)
+        walk::pin<16>(acc);
+        if (pre_next) static_for<0, MS>([&](auto jc) __attribute__((always_inline)) { walk::pin<16>(in + 16 * decltype(jc)::value); });   // (waited for in front of the stores)
         dn4k_store<REAL>(A, tile, t, acc);
-        if (__builtin_expect(__any(not_finite(acc[15].x) | not_finite(acc[15].y)), 0)) careful_note(&dn_noted, (tile - tile_first()) / gridDim.x);
+        if (__builtin_expect(__any(not_finite(acc[15].x) | not_finite(acc[15].y)), 0)) careful_note(&dn_noted, (tile - walk::first_tile()) / gridDim.x);
     }
     const unsigned long long noted = careful_noted(&dn_noted);
     if (__builtin_expect(noted != 0, 0)) {
         int64_t k = 0;
-        for (int64_t tl = tile_first(); tl < A.ntiles; tl += gridDim.x, ++k)
+        for (int64_t tl = walk::first_tile(); tl < A.ntiles; tl += gridDim.x, ++k)
             if (careful_step_noted(noted, k))
                 dn4k_careful_outputs<REAL>(A.x, A.y, A.n_out, A.n_hist, A.cf, A.M, tl * (REAL ? 2 : 1) * (int64_t)A.V, A.V, A.a0, t);
     }
-}
-
-struct Dn4kPlanList { std::vector<Dn4kPlan *> plans; };
-
-static void dn4k_free_plan(Dn4kPlan *p)
-{
-    if (!p) return;
-    if (p->tw) (void)hipFree(p->tw);
-    if (p->T2) (void)hipFree(p->T2);
-    if (p->Hp) (void)hipFree(p->Hp);
-    delete p;
-}
-
-void fir_dn4k_free(void *list)
-{
-    Dn4kPlanList *l = static_cast<Dn4kPlanList *>(list);
-    if (!l) return;
-    for (Dn4kPlan *p : l->plans) dn4k_free_plan(p);
-    delete l;
 }
 
 // complex64 (any taps) or float32 with real taps; per phase at most 2049 taps (half a tile of overlap)
@@ -320,34 +250,18 @@ bool fir_dn4k_supported(const FirHandle *h, int M)
 
 static int dn4k_plan(FirHandle *h, int M, Dn4kPlan **out)
 {
-    if (!h->dn4k) h->dn4k = new Dn4kPlanList();
-    Dn4kPlanList *l = static_cast<Dn4kPlanList *>(h->dn4k);
-    for (Dn4kPlan *p : l->plans)
-        if (p->M == M) { *out = p; return SKDSP_OK; }
-    Dn4kPlan *p = new Dn4kPlan();
-    p->M = M;
-    p->T = dn_taps_per_phase(h->ntaps, M);
-    p->ov = ((p->T - 1 + 255) / 256) * 256;
-    if (p->ov == 0) p->ov = 256;
-    p->V = kN - p->ov;
-    std::vector<float2> tw, T2;
-    std::vector<float4> Hp;
-    make_tw(tw);
-    make_T2(T2);
-    make_dn_tables(h->taps_host.data(), h->ntaps, h->taps_complex ? 2 : 1, M, Hp);
-    hipError_t e;
-    if ((e = hipMalloc((void **)&p->tw, tw.size() * sizeof(float2))) != hipSuccess ||
-        (e = hipMalloc((void **)&p->T2, T2.size() * sizeof(float2))) != hipSuccess ||
-        (e = hipMalloc((void **)&p->Hp, Hp.size() * sizeof(float4))) != hipSuccess ||
-        (e = hipMemcpy(p->tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(p->T2, T2.data(), T2.size() * sizeof(float2), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(p->Hp, Hp.data(), Hp.size() * sizeof(float4), hipMemcpyHostToDevice)) != hipSuccess) {
-        dn4k_free_plan(p);
-        return hip_fail(e, "dn4k tables", __FILE__, __LINE__);
-    }
-    l->plans.push_back(p);
-    *out = p;
-    return SKDSP_OK;
+    return tile_plan(h->dn4k, M, out, [&](Dn4kPlan &p) {
+        tile_overlap(dn_taps_per_phase(h->ntaps, M), 256, kN, &p.ov, &p.V);
+        std::vector<float2> tw, T2;
+        std::vector<float4> Hp;
+        make_tw(tw);
+        make_T2(T2);
+        make_dn_tables(h->taps_host.data(), h->ntaps, h->taps_complex ? 2 : 1, M, Hp);
+        int rc = p.tw.upload(tw);
+        if (!rc) rc = p.T2.upload(T2);
+        if (!rc) rc = p.Hp.upload(Hp);
+        return rc;
+    });
 }
 
 int fir_dn4k_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, int M, void *y, hipStream_t s)
@@ -363,18 +277,15 @@ int fir_dn4k_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, int 
     const int esz = real ? 4 : 8;
     Dn4kArgs A;
     A.x = x; A.y = y; A.n = n_out * M; A.n_hist = n_hist; A.n_out = n_out;
-    A.tw = p->tw; A.T2 = p->T2; A.Hp = p->Hp;
+    A.tw = p->tw.dev; A.T2 = p->T2.dev; A.Hp = p->Hp.dev;
     A.ov = p->ov; A.V = p->V; A.a0 = p->ov / 256;
     A.M = M;
-    A.aligned = ((((uintptr_t)x) | ((uintptr_t)y)) & (esz - 1)) == 0;
+    A.aligned = elem_aligned(x, y, esz);
     const int64_t per = (int64_t)p->V * (real ? 2 : 1);
     A.ntiles = (n_out + per - 1) / per;
     if ((rc = fir_careful(h, &A.cf))) return rc;
     SK_CHECK(A.ntiles < (int64_t)1 << 31, SKDSP_ERR_BADARG, "fir_dn4k: too many tiles");
-    int64_t grid = 2 * (int64_t)ctx().num_cus;
-    const int reserve_wgs = opt().ols_reserve;
-    if (reserve_wgs > 0 && grid >= 4 * (int64_t)reserve_wgs) grid -= reserve_wgs;
-    if (grid > A.ntiles) grid = A.ntiles;
+    const int64_t grid = persistent_grid(A.ntiles);
     const dim3 g((unsigned)grid), b(256);
     auto launch = [&](auto rl) {
         constexpr bool R = decltype(rl)::value;

@@ -17,6 +17,7 @@
 // Algorithmic bytes: 8 B x (n + n L) complex64, 4 B x (n + n L) float32.
 #include "skdsp_internal.hpp"
 #include "ols2k_tables.hpp"
+#include "tile_walk.hpp"
 
 namespace skdsp {
 
@@ -24,11 +25,11 @@ using namespace ols2k;
 typedef float v4f_t __attribute__((ext_vector_type(4)));
 typedef float v2f_t __attribute__((ext_vector_type(2)));
 
-struct Up2kPlan {
-    int L = 0, T = 0, ov = 0, V = 0, passes = 0;
+struct Up2kPlan : TilePlan {   // key = L
+    int ov = 0, V = 0, passes = 0;
     bool pairs = false;
-    float2 *tw1 = nullptr, *tw2 = nullptr, *tw3 = nullptr;
-    float4 *Hp = nullptr;
+    DevTable<float2> tw1, tw2, tw3;
+    DevTable<float4> Hp;
 };
 
 struct Up2kArgs {
@@ -86,28 +87,6 @@ template <bool XR> __device__ __noinline__ void up2k_load_edge(const void *x, in
         }
         v[m] = val;
     }
-}
-template <bool XR> __device__ __forceinline__ void up2k_settle_x(const cf *v)
-{
-    if constexpr (XR)
-        asm volatile("" ::"v"(v[0].x), "v"(v[1].x), "v"(v[2].x), "v"(v[3].x), "v"(v[4].x), "v"(v[5].x), "v"(v[6].x), "v"(v[7].x) : "memory");
-    else
-        asm volatile("" ::"v"(v[0].x), "v"(v[0].y), "v"(v[1].x), "v"(v[1].y), "v"(v[2].x), "v"(v[2].y), "v"(v[3].x), "v"(v[3].y), "v"(v[4].x), "v"(v[4].y),
-                     "v"(v[5].x), "v"(v[5].y), "v"(v[6].x), "v"(v[6].y), "v"(v[7].x), "v"(v[7].y)
-                     : "memory");
-}
-// "these are the results, in these registers, now": without it hipcc carries a finished pass in a form of its own (24 live registers per
-// pass instead of 16 -- 142 / 236 / 256 + 68 spilled for 4 / 8 / 12 passes per thread; with it 122 / 184 / 250 and no spill)
-__device__ __forceinline__ void up2k_pin(cf *v)
-{
-    asm volatile("" : "+v"(v[0].x), "+v"(v[0].y), "+v"(v[1].x), "+v"(v[1].y), "+v"(v[2].x), "+v"(v[2].y), "+v"(v[3].x), "+v"(v[3].y), "+v"(v[4].x), "+v"(v[4].y),
-                 "+v"(v[5].x), "+v"(v[5].y), "+v"(v[6].x), "+v"(v[6].y), "+v"(v[7].x), "+v"(v[7].y));
-}
-__device__ __forceinline__ float4 up2k_vld(const volatile float4 *p)
-{
-    float4 r;
-    r.x = p->x; r.y = p->y; r.z = p->z; r.w = p->w;
-    return r;
 }
 
 // float4 units per staged row: the row (8 bytes per pass) plus one unit of padding where the row length in units is even, so
@@ -224,8 +203,7 @@ template <bool XR, int PH, bool STAGED> __global__ __launch_bounds__(256, 2) voi
         if (t < kTw3Units) tw3l[t] = A.tw3[t];
     }
     __syncthreads();
-    int64_t tile = (gridDim.x % 8 == 0) ? (int64_t)(blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8 : (int64_t)blockIdx.x;
-    auto tile_first = [&]() -> int64_t { return (gridDim.x % 8 == 0) ? (int64_t)(blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8 : (int64_t)blockIdx.x; };
+    int64_t tile = walk::first_tile();
     cf Z[8];               // the tile's samples, then its spectrum, then (behind the last H product) the next tile's samples
     bool have_x = false;   // Z holds the samples of `tile` (requested a pass ahead: interior tiles only)
     for (; tile < A.ntiles; tile += gridDim.x) {
@@ -269,7 +247,7 @@ template <bool XR, int PH, bool STAGED> __global__ __launch_bounds__(256, 2) voi
                         asm volatile("" : "+v"(tt));
                         const volatile float4 *hp = reinterpret_cast<const volatile float4 *>(A.Hp) + (size_t)(g0 + q) * 1024;
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) hh[k] = up2k_vld(hp + (unsigned)(k * 256 + tt));
+                        for (int k = 0; k < 4; ++k) hh[k] = walk::vld(hp + (unsigned)(k * 256 + tt));
                     }
                     if constexpr (ZL) {
 #pragma unroll
@@ -286,10 +264,10 @@ template <bool XR, int PH, bool STAGED> __global__ __launch_bounds__(256, 2) voi
                     __syncthreads();
                     inv_pass1(t, tw1l, img, out + 8 * q);
                     __syncthreads();   // every wave has read the image before the next pass (or tile) overwrites it
-                    up2k_pin(out + 8 * q);
+                    walk::pin<8>(out + 8 * q);
                 }
             });
-            if (!ZL && last_group && pre_next) up2k_settle_x<XR>(Z);
+            if (!ZL && last_group && pre_next) walk::settle_x<XR, 8>(Z);
             poisoned |= not_finite(out[7].x) | not_finite(out[7].y);
             if constexpr (STAGED) {
                 up2k_store_staged<PH>(A, tile, cnt, t, out, stage + Up2kStage<PH>::kWaveUnits * (t >> 6));
@@ -300,34 +278,14 @@ template <bool XR, int PH, bool STAGED> __global__ __launch_bounds__(256, 2) voi
                 up2k_store_direct<PH, false>(A, tile, g0, cnt, t, out);
             }
         }
-        if (__builtin_expect(__any(poisoned), 0)) careful_note(&up_noted, (tile - tile_first()) / gridDim.x);
+        if (__builtin_expect(__any(poisoned), 0)) careful_note(&up_noted, (tile - walk::first_tile()) / gridDim.x);
     }
     const unsigned long long noted = careful_noted(&up_noted);
     if (__builtin_expect(noted != 0, 0)) {
         int64_t k = 0;
-        for (int64_t tl = tile_first(); tl < A.ntiles; tl += gridDim.x, ++k)
+        for (int64_t tl = walk::first_tile(); tl < A.ntiles; tl += gridDim.x, ++k)
             if (careful_step_noted(noted, k)) up2k_careful_rows<XR>(A.x, A.y, A.n, A.n_hist, A.cf, A.row_bytes / (XR ? 4 : 8), tl * A.V, A.ov, t);
     }
-}
-
-struct Up2kPlanList { std::vector<Up2kPlan *> plans; };
-
-static void up2k_free_plan(Up2kPlan *p)
-{
-    if (!p) return;
-    if (p->tw1) (void)hipFree(p->tw1);
-    if (p->tw2) (void)hipFree(p->tw2);
-    if (p->tw3) (void)hipFree(p->tw3);
-    if (p->Hp) (void)hipFree(p->Hp);
-    delete p;
-}
-
-void fir_up2k_free(void *list)
-{
-    Up2kPlanList *l = static_cast<Up2kPlanList *>(list);
-    if (!l) return;
-    for (Up2kPlan *p : l->plans) up2k_free_plan(p);
-    delete l;
 }
 
 // complex64 (any taps) or float32 with real taps; per phase at most 1025 taps (half a tile of overlap)
@@ -343,39 +301,22 @@ bool fir_up2k_supported(const FirHandle *h, int L)
 
 static int up2k_plan(FirHandle *h, int L, Up2kPlan **out)
 {
-    if (!h->up2k) h->up2k = new Up2kPlanList();
-    Up2kPlanList *l = static_cast<Up2kPlanList *>(h->up2k);
-    for (Up2kPlan *p : l->plans)
-        if (p->L == L) { *out = p; return SKDSP_OK; }
-    Up2kPlan *p = new Up2kPlan();
-    p->L = L;
-    p->pairs = h->dtype == SKDSP_F32;
-    p->T = up_taps_per_phase(h->ntaps, L);
-    p->ov = ((p->T - 1 + 63) / 64) * 64;
-    if (p->ov == 0) p->ov = 64;
-    p->V = k2N - p->ov;
-    p->passes = up_passes(L, p->pairs);
-    std::vector<float2> tw1, tw2, tw3;
-    std::vector<float4> Hp;
-    make_tw1(tw1);
-    make_tw2(tw2);
-    make_tw3(tw3);
-    make_up_tables(h->taps_host.data(), h->ntaps, h->taps_complex ? 2 : 1, L, p->pairs, Hp);
-    hipError_t e;
-    if ((e = hipMalloc((void **)&p->tw1, tw1.size() * sizeof(float2))) != hipSuccess ||
-        (e = hipMalloc((void **)&p->tw2, tw2.size() * sizeof(float2))) != hipSuccess ||
-        (e = hipMalloc((void **)&p->tw3, tw3.size() * sizeof(float2))) != hipSuccess ||
-        (e = hipMalloc((void **)&p->Hp, Hp.size() * sizeof(float4))) != hipSuccess ||
-        (e = hipMemcpy(p->tw1, tw1.data(), tw1.size() * sizeof(float2), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(p->tw2, tw2.data(), tw2.size() * sizeof(float2), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(p->tw3, tw3.data(), tw3.size() * sizeof(float2), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(p->Hp, Hp.data(), Hp.size() * sizeof(float4), hipMemcpyHostToDevice)) != hipSuccess) {
-        up2k_free_plan(p);
-        return hip_fail(e, "up2k tables", __FILE__, __LINE__);
-    }
-    l->plans.push_back(p);
-    *out = p;
-    return SKDSP_OK;
+    return tile_plan(h->up2k, L, out, [&](Up2kPlan &p) {
+        p.pairs = h->dtype == SKDSP_F32;
+        tile_overlap(up_taps_per_phase(h->ntaps, L), 64, k2N, &p.ov, &p.V);
+        p.passes = up_passes(L, p.pairs);
+        std::vector<float2> tw1, tw2, tw3;
+        std::vector<float4> Hp;
+        make_tw1(tw1);
+        make_tw2(tw2);
+        make_tw3(tw3);
+        make_up_tables(h->taps_host.data(), h->ntaps, h->taps_complex ? 2 : 1, L, p.pairs, Hp);
+        int rc = p.tw1.upload(tw1);
+        if (!rc) rc = p.tw2.upload(tw2);
+        if (!rc) rc = p.tw3.upload(tw3);
+        if (!rc) rc = p.Hp.upload(Hp);
+        return rc;
+    });
 }
 
 int fir_up2k_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, int L, void *y, hipStream_t s)
@@ -389,12 +330,12 @@ int fir_up2k_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, int 
     const int esz = h->dtype == SKDSP_F32 ? 4 : 8;
     Up2kArgs A;
     A.x = x; A.y = y; A.n = n; A.n_hist = n_hist;
-    A.tw1 = p->tw1; A.tw2 = p->tw2; A.tw3 = p->tw3; A.Hp = p->Hp;
+    A.tw1 = p->tw1.dev; A.tw2 = p->tw2.dev; A.tw3 = p->tw3.dev; A.Hp = p->Hp.dev;
     A.ov = p->ov; A.V = p->V;
     A.passes = p->passes;
     A.row_bytes = L * esz;
     A.odd_tail = p->pairs && (L & 1);
-    A.aligned = ((((uintptr_t)x) | ((uintptr_t)y)) & (esz - 1)) == 0;
+    A.aligned = elem_aligned(x, y, esz);
     A.ntiles = (n + p->V - 1) / p->V;
     if ((rc = fir_careful(h, &A.cf))) return rc;
     SK_CHECK(A.ntiles < (int64_t)1 << 31, SKDSP_ERR_BADARG, "fir_up2k: too many tiles");
@@ -408,10 +349,7 @@ int fir_up2k_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, int 
         const int upr = cnt0 / 2 > 0 ? cnt0 / 2 : 1;
         A.upr_magic = (unsigned)((65536 + upr - 1) / upr);
     }
-    int64_t grid = 2 * (int64_t)ctx().num_cus;
-    const int reserve_wgs = opt().ols_reserve;
-    if (reserve_wgs > 0 && grid >= 4 * (int64_t)reserve_wgs) grid -= reserve_wgs;
-    if (grid > A.ntiles) grid = A.ntiles;
+    const int64_t grid = persistent_grid(A.ntiles);
     const dim3 g((unsigned)grid), b(256);
     auto launch = [&](auto xr, auto ph) {
         constexpr bool X = decltype(xr)::value;

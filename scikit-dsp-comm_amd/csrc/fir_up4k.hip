@@ -14,6 +14,7 @@
 // Algorithmic bytes: 8 B x (n + n L) complex64, 4 B x (n + n L) float32.
 #include "skdsp_internal.hpp"
 #include "ols4k_tables.hpp"
+#include "tile_walk.hpp"
 
 namespace skdsp {
 
@@ -21,11 +22,11 @@ using namespace ols4k;
 typedef float v4f_t __attribute__((ext_vector_type(4)));
 typedef float v2f_t __attribute__((ext_vector_type(2)));
 
-struct Up4kPlan {
-    int L = 0, T = 0, ov = 0, V = 0, passes = 0;
+struct Up4kPlan : TilePlan {   // key = L
+    int ov = 0, V = 0, passes = 0;
     bool pairs = false;
-    float2 *tw = nullptr, *T2 = nullptr;
-    float4 *Hp = nullptr;
+    DevTable<float2> tw, T2;
+    DevTable<float4> Hp;
 };
 
 struct Up4kArgs {
@@ -169,61 +170,12 @@ __device__ __forceinline__ void up4k_store4_staged(const Up4kArgs &A, int64_t ti
     }
 }
 
-// "these are the results, in these registers, now": without it hipcc carries a finished pass in a form of its own (more live registers per
-// pass than its 32 results: fir_up2k.hip measured 24 instead of 16 for its eight)
-__device__ __forceinline__ void up4k_pin(cf *v)
-{
-#pragma unroll
-    for (int i = 0; i < 16; i += 8)
-        asm volatile("" : "+v"(v[i].x), "+v"(v[i].y), "+v"(v[i + 1].x), "+v"(v[i + 1].y), "+v"(v[i + 2].x), "+v"(v[i + 2].y), "+v"(v[i + 3].x), "+v"(v[i + 3].y),
-                     "+v"(v[i + 4].x), "+v"(v[i + 4].y), "+v"(v[i + 5].x), "+v"(v[i + 5].y), "+v"(v[i + 6].x), "+v"(v[i + 6].y), "+v"(v[i + 7].x), "+v"(v[i + 7].y));
-}
-// volatile 16-byte load: keeps the request at its program position (the scheduler would otherwise sink a prefetch to its first use)
-__device__ __forceinline__ float4 up4k_vld(const volatile float4 *p)
-{
-    float4 r;
-    r.x = p->x; r.y = p->y; r.z = p->z; r.w = p->w;
-    return r;
-}
-// this thread's 8 float4 of pass q's transfer function
-__device__ __forceinline__ void up4k_load_H(const Up4kArgs &A, int q, int t, float4 *hh)
-{
-    int tt = t;   // (opaque copy: the addresses are rebuilt where they are used)
-    asm volatile("" : "+v"(tt));
-    const volatile float4 *hp = reinterpret_cast<const volatile float4 *>(A.Hp) + (size_t)q * 2048;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) hh[k] = up4k_vld(hp + (unsigned)(k * 256 + tt));
-}
 // (a table that is NOT requested: a defined value, so that the previous one does not stay alive across the whole loop body)
 __device__ __forceinline__ void up4k_no_H(float4 *hh)
 {
 #pragma unroll
     for (int k = 0; k < 8; ++k) hh[k] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
-// "the values must be in their registers HERE": makes hipcc place its wait for a prefetch at this point
-__device__ __forceinline__ void up4k_settle(const float4 *hh)
-{
-#pragma unroll
-    for (int k = 0; k < 8; k += 4)
-        asm volatile("" ::"v"(hh[k].x), "v"(hh[k].y), "v"(hh[k].z), "v"(hh[k].w), "v"(hh[k + 1].x), "v"(hh[k + 1].y), "v"(hh[k + 1].z), "v"(hh[k + 1].w),
-                     "v"(hh[k + 2].x), "v"(hh[k + 2].y), "v"(hh[k + 2].z), "v"(hh[k + 2].w), "v"(hh[k + 3].x), "v"(hh[k + 3].y), "v"(hh[k + 3].z), "v"(hh[k + 3].w)
-                     : "memory");
-}
-template <bool XR> __device__ __forceinline__ void up4k_settle_x(const cf *v)
-{
-    if constexpr (XR) {
-#pragma unroll
-        for (int i = 0; i < 16; i += 8)
-            asm volatile("" ::"v"(v[i].x), "v"(v[i + 1].x), "v"(v[i + 2].x), "v"(v[i + 3].x), "v"(v[i + 4].x), "v"(v[i + 5].x), "v"(v[i + 6].x), "v"(v[i + 7].x) : "memory");
-    } else {
-#pragma unroll
-        for (int i = 0; i < 16; i += 8)
-            asm volatile("" ::"v"(v[i].x), "v"(v[i].y), "v"(v[i + 1].x), "v"(v[i + 1].y), "v"(v[i + 2].x), "v"(v[i + 2].y), "v"(v[i + 3].x), "v"(v[i + 3].y),
-                         "v"(v[i + 4].x), "v"(v[i + 4].y), "v"(v[i + 5].x), "v"(v[i + 5].y), "v"(v[i + 6].x), "v"(v[i + 6].y), "v"(v[i + 7].x), "v"(v[i + 7].y)
-                         : "memory");
-    }
-}
-
 // A poisoned tile (one inf / nan among its 4096 inputs makes every result of every pass non-finite, where the reference confines the sample
 // to the Ntaps outputs that multiply it): the thread recomputes the rows it stored -- samples out0 + 256 (a - a0) + t, all L phases each -- by
 // the reference's own sum (careful.hpp).  Rows are written by their own thread or, through the wave-private staging image, by its own wave,
@@ -259,21 +211,14 @@ template <bool XR, int G> __global__ __launch_bounds__(256, 2) void up4k_kernel(
     __shared__ unsigned long long up_noted;          // poisoned tiles, by walk step (careful.hpp)
     const int t = threadIdx.x;
     if (t == 0) up_noted = 0;
-    {
-        const cf w = A.T2[t];
-        T2f[t] = w;
-        T2t[(t & 15) * 16 + (t >> 4)] = w;
-#pragma unroll
-        for (int k = 0; k < 15; ++k) twl[k * 256 + t] = A.tw[k * 256 + t];
-    }
+    walk::twiddles_4k(t, A.T2, A.tw, T2f, T2t, twl);
     __syncthreads();
-    int64_t tile = (gridDim.x % 8 == 0) ? (int64_t)(blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8 : (int64_t)blockIdx.x;
-    auto tile_first = [&]() -> int64_t { return (gridDim.x % 8 == 0) ? (int64_t)(blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8 : (int64_t)blockIdx.x; };
+    int64_t tile = walk::first_tile();
     cf Z[16];          // the tile's samples, then its spectrum, then (behind the last H product) the next tile's samples
     float4 hh[G][8];   // the tables of the current group's passes
     bool have_x = false;   // Z holds the samples of `tile` (requested a pass ahead: interior tiles only)
     if (tile < A.ntiles) {
-        up4k_load_H(A, 0, t, hh[0]);
+        walk::load_H(A.Hp, 0, t, hh[0]);
     } else {
         up4k_no_H(hh[0]);
     }
@@ -309,7 +254,7 @@ template <bool XR, int G> __global__ __launch_bounds__(256, 2) void up4k_kernel(
                 constexpr int j = decltype(jc)::value;
                 if (j < cnt) {
                     cf P[16];
-                    if (j > 0) up4k_load_H(A, g0 + j, t, hh[j]);
+                    if (j > 0) walk::load_H(A.Hp, g0 + j, t, hh[j]);
                     mul_H(hh[j], Z, P);
                     if (j == cnt - 1 && last_group && pre_next)   // the tile's last pass: the spectrum is dead, the next tile's samples land in its registers
                         up4k_load_interior<XR>(A, tile + gridDim.x, t, Z);
@@ -318,16 +263,16 @@ template <bool XR, int G> __global__ __launch_bounds__(256, 2) void up4k_kernel(
                     __syncthreads();
                     inv_pass1(t, twl, img, out + 16 * j);
                     __syncthreads();   // every wave has read the image before the next pass (or tile) overwrites it
-                    up4k_pin(out + 16 * j);
+                    walk::pin<16>(out + 16 * j);
                 }
             });
             // the table of the next group's first pass: requested and waited for in front of the stores (an L2 round trip, exposed; held
             // across the last inverse transform it costs 32 registers at the peak and the kernel spills)
-            if (!last_group) up4k_load_H(A, g0 + G, t, hh[0]);
-            else if (has_next) up4k_load_H(A, 0, t, hh[0]);
+            if (!last_group) walk::load_H(A.Hp, g0 + G, t, hh[0]);
+            else if (has_next) walk::load_H(A.Hp, 0, t, hh[0]);
             else up4k_no_H(hh[0]);
-            up4k_settle(hh[0]);
-            if (last_group && pre_next) up4k_settle_x<XR>(Z);
+            walk::settle<8>(hh[0]);
+            if (last_group && pre_next) walk::settle_x<XR, 16>(Z);
             poisoned |= not_finite(out[15].x) | not_finite(out[15].y);
             const bool tail = A.odd_tail && last_group;
             auto store = [&](auto tc) __attribute__((always_inline)) {
@@ -349,33 +294,14 @@ template <bool XR, int G> __global__ __launch_bounds__(256, 2) void up4k_kernel(
                 store(std::false_type{});
             }
         }
-        if (__builtin_expect(__any(poisoned), 0)) careful_note(&up_noted, (tile - tile_first()) / gridDim.x);
+        if (__builtin_expect(__any(poisoned), 0)) careful_note(&up_noted, (tile - walk::first_tile()) / gridDim.x);
     }
     const unsigned long long noted = careful_noted(&up_noted);
     if (__builtin_expect(noted != 0, 0)) {
         int64_t k = 0;
-        for (int64_t tl = tile_first(); tl < A.ntiles; tl += gridDim.x, ++k)
+        for (int64_t tl = walk::first_tile(); tl < A.ntiles; tl += gridDim.x, ++k)
             if (careful_step_noted(noted, k)) up4k_careful_rows<XR>(A.x, A.y, A.n, A.n_hist, A.cf, A.row_bytes / (XR ? 4 : 8), tl * A.V, A.a0, t);
     }
-}
-
-struct Up4kPlanList { std::vector<Up4kPlan *> plans; };
-
-static void up4k_free_plan(Up4kPlan *p)
-{
-    if (!p) return;
-    if (p->tw) (void)hipFree(p->tw);
-    if (p->T2) (void)hipFree(p->T2);
-    if (p->Hp) (void)hipFree(p->Hp);
-    delete p;
-}
-
-void fir_up4k_free(void *list)
-{
-    Up4kPlanList *l = static_cast<Up4kPlanList *>(list);
-    if (!l) return;
-    for (Up4kPlan *p : l->plans) up4k_free_plan(p);
-    delete l;
 }
 
 // complex64 (any taps) or float32 with real taps; per phase at most 2049 taps (half a tile of overlap)
@@ -391,36 +317,20 @@ bool fir_up4k_supported(const FirHandle *h, int L)
 
 static int up4k_plan(FirHandle *h, int L, Up4kPlan **out)
 {
-    if (!h->up4k) h->up4k = new Up4kPlanList();
-    Up4kPlanList *l = static_cast<Up4kPlanList *>(h->up4k);
-    for (Up4kPlan *p : l->plans)
-        if (p->L == L) { *out = p; return SKDSP_OK; }
-    Up4kPlan *p = new Up4kPlan();
-    p->L = L;
-    p->pairs = h->dtype == SKDSP_F32;
-    p->T = up_taps_per_phase(h->ntaps, L);
-    p->ov = ((p->T - 1 + 255) / 256) * 256;
-    if (p->ov == 0) p->ov = 256;
-    p->V = kN - p->ov;
-    p->passes = up_passes(L, p->pairs);
-    std::vector<float2> tw, T2;
-    std::vector<float4> Hp;
-    make_tw(tw);
-    make_T2(T2);
-    make_up_tables(h->taps_host.data(), h->ntaps, h->taps_complex ? 2 : 1, L, p->pairs, Hp);
-    hipError_t e;
-    if ((e = hipMalloc((void **)&p->tw, tw.size() * sizeof(float2))) != hipSuccess ||
-        (e = hipMalloc((void **)&p->T2, T2.size() * sizeof(float2))) != hipSuccess ||
-        (e = hipMalloc((void **)&p->Hp, Hp.size() * sizeof(float4))) != hipSuccess ||
-        (e = hipMemcpy(p->tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(p->T2, T2.data(), T2.size() * sizeof(float2), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(p->Hp, Hp.data(), Hp.size() * sizeof(float4), hipMemcpyHostToDevice)) != hipSuccess) {
-        up4k_free_plan(p);
-        return hip_fail(e, "up4k tables", __FILE__, __LINE__);
-    }
-    l->plans.push_back(p);
-    *out = p;
-    return SKDSP_OK;
+    return tile_plan(h->up4k, L, out, [&](Up4kPlan &p) {
+        p.pairs = h->dtype == SKDSP_F32;
+        tile_overlap(up_taps_per_phase(h->ntaps, L), 256, kN, &p.ov, &p.V);
+        p.passes = up_passes(L, p.pairs);
+        std::vector<float2> tw, T2;
+        std::vector<float4> Hp;
+        make_tw(tw);
+        make_T2(T2);
+        make_up_tables(h->taps_host.data(), h->ntaps, h->taps_complex ? 2 : 1, L, p.pairs, Hp);
+        int rc = p.tw.upload(tw);
+        if (!rc) rc = p.T2.upload(T2);
+        if (!rc) rc = p.Hp.upload(Hp);
+        return rc;
+    });
 }
 
 int fir_up4k_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, int L, void *y, hipStream_t s)
@@ -434,20 +344,17 @@ int fir_up4k_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, int 
     const int esz = h->dtype == SKDSP_F32 ? 4 : 8;
     Up4kArgs A;
     A.x = x; A.y = y; A.n = n; A.n_hist = n_hist;
-    A.tw = p->tw; A.T2 = p->T2; A.Hp = p->Hp;
+    A.tw = p->tw.dev; A.T2 = p->T2.dev; A.Hp = p->Hp.dev;
     A.ov = p->ov; A.V = p->V; A.a0 = p->ov / 256;
     A.passes = p->passes;
     A.row_bytes = L * esz;
     A.odd_tail = p->pairs && (L & 1);
-    A.aligned = ((((uintptr_t)x) | ((uintptr_t)y)) & (esz - 1)) == 0;
+    A.aligned = elem_aligned(x, y, esz);
     A.ntiles = (n + p->V - 1) / p->V;
     A.staged = opt().fir_up4k_staged;
     if ((rc = fir_careful(h, &A.cf))) return rc;
     SK_CHECK(A.ntiles < (int64_t)1 << 31, SKDSP_ERR_BADARG, "fir_up4k: too many tiles");
-    int64_t grid = 2 * (int64_t)ctx().num_cus;
-    const int reserve_wgs = opt().ols_reserve;
-    if (reserve_wgs > 0 && grid >= 4 * (int64_t)reserve_wgs) grid -= reserve_wgs;
-    if (grid > A.ntiles) grid = A.ntiles;
+    const int64_t grid = persistent_grid(A.ntiles);
     const int G = opt().fir_up4k_group;
     if (p->pairs) {
         if (G == 2) hipLaunchKernelGGL((up4k_kernel<true, 2>), dim3((unsigned)grid), dim3(256), 0, s, A);

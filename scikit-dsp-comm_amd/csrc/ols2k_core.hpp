@@ -39,6 +39,7 @@ using ols::csub;
 using ols::madd_mi;
 using ols::msub_mi;
 using ols::twmul;
+using ols::dft4_ip;
 using ols::static_for;
 using ols::lo;
 using ols::hi;
@@ -58,14 +59,6 @@ SK_HD int unit(int k1, int i2, int i3, int d) { return k1 * kRegion + i2 * 72 + 
 constexpr int P8(int k) { return ((k & 3) << 1) | (k >> 2); }
 constexpr int Q8(int s) { return (s >> 1) | ((s & 1) << 2); }
 
-template <bool INV> SK_HD void dft4_ip(cf &x0, cf &x1, cf &x2, cf &x3)
-{
-    const cf s02 = cadd(x0, x2), d02 = csub(x0, x2), s13 = cadd(x1, x3), d13 = csub(x1, x3);
-    x0 = cadd(s02, s13);
-    x2 = csub(s02, s13);
-    x1 = madd_mi<INV>(d02, d13);
-    x3 = msub_mi<INV>(d02, d13);
-}
 SK_HD void dft2_ip(cf &x0, cf &x1)
 {
     const cf s = cadd(x0, x1), d = csub(x0, x1);

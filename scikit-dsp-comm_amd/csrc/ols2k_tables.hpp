@@ -58,49 +58,12 @@ inline void append_Hp(const cd *h, int len, std::vector<float4> &Hp)
         }
 }
 
-// multirate_FIR.up (multirate_helper.py:112-118): pass q IS phase q (complex64), h_q[t] = L b[q + L t]; float32 signals with real
-// taps: pass q carries phases 2q and 2q + 1 as real and imaginary part of one complex filter over the real signal
-inline int up_taps_per_phase(int ntaps, int L) { return (ntaps + L - 1) / L; }
-inline int up_passes(int L, bool real_pairs) { return real_pairs ? (L + 1) / 2 : L; }
-inline void make_up_tables(const double *taps, int ntaps, int comp, int L, bool real_pairs, std::vector<float4> &Hp)
-{
-    const int T = up_taps_per_phase(ntaps, L);
-    std::vector<cd> h(T);
-    Hp.clear();
-    auto tap = [&](int k) -> cd {
-        if (k >= ntaps) return cd(0, 0);
-        return comp == 2 ? cd(taps[2 * k], taps[2 * k + 1]) : cd(taps[k], 0.0);
-    };
-    for (int q = 0; q < up_passes(L, real_pairs); ++q) {
-        for (int t = 0; t < T; ++t) {
-            if (real_pairs) {
-                const double re = tap(2 * q + L * t).real();
-                const double im = 2 * q + 1 < L ? tap(2 * q + 1 + L * t).real() : 0.0;
-                h[t] = cd((double)L * re, (double)L * im);
-            } else {
-                h[t] = (double)L * tap(q + L * t);
-            }
-        }
-        append_Hp(h.data(), T, Hp);
-    }
-}
-
-// multirate_FIR.dn (multirate_helper.py:121-127) over ALIGNED input blocks u_r[i] = x[i M + r]:
-//   y[k] = sum_r sum_j g_r[j] u_r[k - j],   g_r[j] = b[j M - r]  (b[negative] = 0)
-inline int dn_taps_per_phase(int ntaps, int M) { return (ntaps - 1 + M - 1) / M + 1; }
-inline void make_dn_tables(const double *taps, int ntaps, int comp, int M, std::vector<float4> &Hp)
-{
-    const int T = dn_taps_per_phase(ntaps, M);
-    std::vector<cd> g(T);
-    Hp.clear();
-    for (int r = 0; r < M; ++r) {
-        for (int j = 0; j < T; ++j) {
-            const long long k = (long long)j * M - r;
-            g[j] = (k < 0 || k >= ntaps) ? cd(0, 0) : (comp == 2 ? cd(taps[2 * k], taps[2 * k + 1]) : cd(taps[k], 0.0));
-        }
-        append_Hp(g.data(), T, Hp);
-    }
-}
+// the phase filters of multirate_FIR.up / .dn on this tile (ols_tables.hpp)
+using ols::up_taps_per_phase;
+using ols::up_passes;
+using ols::dn_taps_per_phase;
+inline void make_up_tables(const double *taps, int ntaps, int comp, int L, bool real_pairs, std::vector<float4> &Hp) { ols::make_up_tables(taps, ntaps, comp, L, real_pairs, Hp, append_Hp); }
+inline void make_dn_tables(const double *taps, int ntaps, int comp, int M, std::vector<float4> &Hp) { ols::make_dn_tables(taps, ntaps, comp, M, Hp, append_Hp); }
 
 }  // namespace ols2k
 }  // namespace skdsp

@@ -43,6 +43,7 @@ using ols::csub;
 using ols::madd_mi;
 using ols::msub_mi;
 using ols::twmul;
+using ols::dft4_ip;
 
 constexpr int kN = 4096;
 constexpr int kThreads = 256;
@@ -63,14 +64,6 @@ SK_HD int unit(int row_k1, int mid, int c) { return row_k1 * kRowPitch + mid * 1
 // in registers this kernel has no room for that.
 constexpr int P16(int k) { return ((k & 3) << 2) | (k >> 2); }
 
-template <bool INV> SK_HD void dft4_ip(cf &x0, cf &x1, cf &x2, cf &x3)
-{
-    const cf s02 = cadd(x0, x2), d02 = csub(x0, x2), s13 = cadd(x1, x3), d13 = csub(x1, x3);
-    x0 = cadd(s02, s13);
-    x2 = csub(s02, s13);
-    x1 = madd_mi<INV>(d02, d13);
-    x3 = msub_mi<INV>(d02, d13);
-}
 SK_HD void dft16_f(cf *v)
 {
     // stage 1: DFT4 over n2 for each n1 (slots n1, n1 + 4, n1 + 8, n1 + 12): slot n1 + 4 k2 = a[n1][k2]
@@ -129,6 +122,20 @@ SK_HD void fwd_pass2(int t, const cf *T2, cf *img)
     static_for<1, 16>([&](auto kc) {
         constexpr int k2 = decltype(kc)::value;
         img[unit(k1, k2, c)] = cmul(in[P16(k2)], T2[k2 * 16 + c]);
+    });
+}
+// the same with the caller's registers as the working array (the decimator transforms each phase signal in place).  NOT one forwarding to the
+// other: hipcc compiles the forwarded form of the three-argument pass differently (3454 changed lines in fir_up4k.hip's device assembly, profiles/r11)
+SK_HD void fwd_pass2(int t, const cf *T2, cf *img, cf *w)
+{
+    const int k1 = t >> 4, c = t & 15;
+    SK_UNROLL
+    for (int b = 0; b < 16; ++b) w[b] = img[unit(k1, b, c)];
+    dft16_f(w);
+    img[unit(k1, 0, c)] = w[P16(0)];
+    static_for<1, 16>([&](auto kc) {
+        constexpr int k2 = decltype(kc)::value;
+        img[unit(k1, k2, c)] = cmul(w[P16(k2)], T2[k2 * 16 + c]);
     });
 }
 SK_HD void fwd_pass3(int t, const cf *img, cf *Z)

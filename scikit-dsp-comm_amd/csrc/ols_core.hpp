@@ -197,6 +197,16 @@ template <bool INV, class E> SK_HD E msub_mi(E p, E d) { return madd_mi<!INV>(p,
 template <bool INV> SK_HD cf mul_mi(cf a) { return madd_mi<INV>(make_float2(0.f, 0.f), a); }
 template <bool INV> SK_HD cf2 mul_mi(cf2 a) { return madd_mi<INV>(make_cf2(make_float2(0.f, 0.f), make_float2(0.f, 0.f)), a); }
 
+// 4-point DFT IN PLACE (unnormalised inverse when INV): the building block of the in-place DFT16 / DFT8 of ols4k_core.hpp / ols2k_core.hpp
+template <bool INV> SK_HD void dft4_ip(cf &x0, cf &x1, cf &x2, cf &x3)
+{
+    const cf s02 = cadd(x0, x2), d02 = csub(x0, x2), s13 = cadd(x1, x3), d13 = csub(x1, x3);
+    x0 = cadd(s02, s13);
+    x2 = csub(s02, s13);
+    x1 = madd_mi<INV>(d02, d13);
+    x3 = msub_mi<INV>(d02, d13);
+}
+
 // a * W_N^K  (forward, W = exp(-2 pi i / N)) or a * conj(W_N^K) (INV); K compile-time
 template <int N, int K, bool INV, class E> SK_HD E twmul(E a)
 {

@@ -86,5 +86,58 @@ inline void make_Hp(const double *taps, int ntaps, int comp, std::vector<float4>
         }
 }
 
+// ---- the phase filters of the frequency-domain interpolators / decimators (ols4k_tables.hpp, ols2k_tables.hpp) -------------------
+// One builder for every tile size: `append_Hp(h, len, Hp)` is the tile's own pre-permuted transfer function (ols4k:: / ols2k::append_Hp).
+//
+// multirate_FIR.up (multirate_helper.py:112-118): y[i L + p] = L sum_t b[p + L t] x[i - t].
+// complex64 signals: pass q IS phase q, h_q[t] = L b[q + L t].  float32 signals with real taps: pass q carries phases 2q and 2q + 1 as
+// the real and imaginary part of ONE complex filter over the real signal (x * (h_2q + i h_2q+1) = y_2q + i y_2q+1: the pass's output is
+// the interleaved pair (y[i L + 2q], y[i L + 2q + 1]) as one 8-byte element); an odd L leaves the last pass's imaginary part empty.
+inline int up_taps_per_phase(int ntaps, int L) { return (ntaps + L - 1) / L; }
+inline int up_passes(int L, bool real_pairs) { return real_pairs ? (L + 1) / 2 : L; }
+// taps: ntaps real (comp = 1) or interleaved complex (comp = 2) doubles
+template <class AppendHp>
+inline void make_up_tables(const double *taps, int ntaps, int comp, int L, bool real_pairs, std::vector<float4> &Hp, AppendHp append_Hp)
+{
+    const int T = up_taps_per_phase(ntaps, L);
+    std::vector<cd> h(T);
+    Hp.clear();
+    auto tap = [&](int k) -> cd {
+        if (k >= ntaps) return cd(0, 0);
+        return comp == 2 ? cd(taps[2 * k], taps[2 * k + 1]) : cd(taps[k], 0.0);
+    };
+    for (int q = 0; q < up_passes(L, real_pairs); ++q) {
+        for (int t = 0; t < T; ++t) {
+            if (real_pairs) {
+                const double re = tap(2 * q + L * t).real();
+                const double im = 2 * q + 1 < L ? tap(2 * q + 1 + L * t).real() : 0.0;
+                h[t] = cd((double)L * re, (double)L * im);
+            } else {
+                h[t] = (double)L * tap(q + L * t);
+            }
+        }
+        append_Hp(h.data(), T, Hp);
+    }
+}
+
+// multirate_FIR.dn (multirate_helper.py:121-127): y[k] = sum_n b[n] x[k M - n].
+// With the input cut into ALIGNED blocks u_r[i] = x[i M + r], r = 0..M-1 (what a lane reads as contiguous bytes):
+//   y[k] = sum_r sum_j g_r[j] u_r[k - j],   g_r[j] = b[j M - r]  (b[negative] = 0: for r > 0 the phase filter starts at j = 1)
+inline int dn_taps_per_phase(int ntaps, int M) { return (ntaps - 1 + M - 1) / M + 1; }
+template <class AppendHp>
+inline void make_dn_tables(const double *taps, int ntaps, int comp, int M, std::vector<float4> &Hp, AppendHp append_Hp)
+{
+    const int T = dn_taps_per_phase(ntaps, M);
+    std::vector<cd> g(T);
+    Hp.clear();
+    for (int r = 0; r < M; ++r) {
+        for (int j = 0; j < T; ++j) {
+            const long long k = (long long)j * M - r;
+            g[j] = (k < 0 || k >= ntaps) ? cd(0, 0) : (comp == 2 ? cd(taps[2 * k], taps[2 * k + 1]) : cd(taps[k], 0.0));
+        }
+        append_Hp(g.data(), T, Hp);
+    }
+}
+
 }  // namespace ols
 }  // namespace skdsp

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <string>
 #include <vector>
+#include <memory>
 #include <mutex>
 #include "../../include/skdsp.h"
 #include "careful.hpp"
@@ -154,6 +155,63 @@ struct HandleBase {
     }
 };
 
+// ---- device tables and per-key plans of the tile engines (fir_up4k.hip, fir_up2k.hip, fir_dn4k.hip, fir_bank.hip) -------
+// One device allocation, freed with its owner.
+template <class T> struct DevTable {
+    T *dev = nullptr;
+    DevTable() = default;
+    DevTable(const DevTable &) = delete;
+    DevTable &operator=(const DevTable &) = delete;
+    ~DevTable()
+    {
+        if (dev) (void)hipFree(dev);
+    }
+    int upload(const T *src, size_t count)
+    {
+        SK_HIP(hipMalloc((void **)&dev, count * sizeof(T)));
+        SK_HIP(hipMemcpy(dev, src, count * sizeof(T), hipMemcpyHostToDevice));
+        return SKDSP_OK;
+    }
+    int upload(const std::vector<T> &v) { return upload(v.data(), v.size()); }
+};
+// What a FIR handle keeps per rate-change factor (key = L or M): the engine's file derives its plan from this.
+struct TilePlan {
+    int key = 0;
+    virtual ~TilePlan() {}
+};
+typedef std::vector<std::unique_ptr<TilePlan>> TilePlans;
+// The plan of `key`, built by fill(P &) on first use (under the handle's lock, like every other table); a plan whose fill fails is
+// released with everything it had uploaded.
+template <class P, class Fill> int tile_plan(TilePlans &plans, int key, P **out, Fill fill)
+{
+    for (auto &q : plans)
+        if (q->key == key) { *out = static_cast<P *>(q.get()); return SKDSP_OK; }
+    std::unique_ptr<P> p(new P());
+    p->key = key;
+    const int rc = fill(*p);
+    if (rc) return rc;
+    *out = p.get();
+    plans.push_back(std::move(p));
+    return SKDSP_OK;
+}
+// The launch arithmetic of a persistent walk over tiles of N points.
+// Overlap = taps per phase - 1 rounded up to whole blocks (at least one), V = the samples a tile keeps.
+inline void tile_overlap(int taps_per_phase, int block, int N, int *ov, int *V)
+{
+    *ov = ((taps_per_phase - 1 + block - 1) / block) * block;
+    if (*ov == 0) *ov = block;
+    *V = N - *ov;
+}
+// 2 workgroups per CU, less the slots option ols_reserve leaves free (where the grid is at least 4 x that), at most one per tile
+inline int64_t persistent_grid(int64_t ntiles)
+{
+    int64_t grid = 2 * (int64_t)ctx().num_cus;
+    const int reserve_wgs = opt().ols_reserve;
+    if (reserve_wgs > 0 && grid >= 4 * (int64_t)reserve_wgs) grid -= reserve_wgs;
+    return grid > ntiles ? ntiles : grid;
+}
+inline bool elem_aligned(const void *x, const void *y, int esz) { return ((((uintptr_t)x) | ((uintptr_t)y)) & (uintptr_t)(esz - 1)) == 0; }
+
 // ---- FIR -----------------------------------------------------------------
 struct OlsPlan;    // fir_ols.hip
 struct Ols64Plan;  // fir_ols64.hip
@@ -178,9 +236,9 @@ struct FirHandle : HandleBase {
     OlsPlan *ols = nullptr;
     struct OlsUp { int L; OlsPlan *plan; };   // overlap-save plans of multirate_FIR.up, keyed by L (fir_ols_up_launch)
     std::vector<OlsUp> ols_up;
-    void *up4k = nullptr;   // plans of the frequency-domain interpolator, keyed by L (fir_up4k.hip)
-    void *up2k = nullptr;   // ... of its many-phase form (fir_up2k.hip)
-    void *dn4k = nullptr;   // plans of the frequency-domain decimator, keyed by M (fir_dn4k.hip)
+    TilePlans up4k;   // plans of the frequency-domain interpolator, keyed by L (fir_up4k.hip)
+    TilePlans up2k;   // ... of its many-phase form (fir_up2k.hip)
+    TilePlans dn4k;   // plans of the frequency-domain decimator, keyed by M (fir_dn4k.hip)
     Ols64Plan *ols64 = nullptr;
     struct Ols64Up { int L; Ols64Plan *plan; };
     std::vector<Ols64Up> ols64_up;
@@ -236,15 +294,12 @@ int fir_ols_rep_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_his
 // taps; at most 2049 taps per phase
 bool fir_up4k_supported(const FirHandle *h, int L);
 int fir_up4k_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, int L, void *y_dev, hipStream_t s);
-void fir_up4k_free(void *plans);
 // the same with a 2048-point tile and ALL phases of a sample in one thread (fir_up2k.hip): at most 1025 taps per phase
 bool fir_up2k_supported(const FirHandle *h, int L);
 int fir_up2k_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, int L, void *y_dev, hipStream_t s);
-void fir_up2k_free(void *plans);
 // multirate_FIR.dn, one workgroup per OUTPUT tile: M forward transforms accumulated in the frequency domain, one inverse (fir_dn4k.hip)
 bool fir_dn4k_supported(const FirHandle *h, int M);
 int fir_dn4k_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, int M, void *y_dev, hipStream_t s);
-void fir_dn4k_free(void *plans);
 // FFT overlap-save in float64 (fir_ols64.hip): complex128, and float64 with real taps; 2..2049 taps
 bool fir_ols64_supported(const FirHandle *h);
 int fir_ols64_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, void *y_dev, hipStream_t s, int dec = 1);
