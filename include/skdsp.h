@@ -159,7 +159,7 @@ int skdsp_iir_sequential(skdsp_handle h, int *is_sequential, double *spread);
 int skdsp_sos_create(const double *sos, int nsec, int dtype, skdsp_handle *out);
 /* transfer function (b,a) for signal.lfilter(b,a,.), multirate_helper.py:74,81;
  * a[0]-normalised.  scipy runs (b,a) as one DF2T section of order N; the scan kernel
- * runs the same transfer function factored into biquads (see capi.hip: the order-N
+ * runs the same transfer function factored into biquads (see iir_design.hpp: the order-N
  * companion coordinates are too ill-conditioned for an affine scan).  Order <= 24. */
 int skdsp_tf_create(const double *b, int nb, const double *a, int na, int dtype, skdsp_handle *out);
 /* host-only: the (b,a) -> sos factorisation tf_create applies; sos_out holds up to 12x6 doubles */

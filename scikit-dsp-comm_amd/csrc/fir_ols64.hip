@@ -16,7 +16,7 @@
 // and the mirror image back (decimation in time), so no bit reversal exists.  LDS image: 16 x (16 x 17) complex128 =
 // 68 KiB (row pitch 17: every 16-lane access pattern used here lands on 16 distinct 16-byte bank groups) -> two
 // persistent workgroups per CU.  V = 4096 - OV valid outputs per tile, OV = Ntaps-1 rounded up to 256 (<= 2048: longer
-// filters are partitioned by capi.hip).  Algorithmic bytes: 32 B per complex128 sample, 16 B per float64 sample.
+// filters are partitioned by fir_api.hip).  Algorithmic bytes: 32 B per complex128 sample, 16 B per float64 sample.
 // Precision: float64 butterflies, twiddle powers by repeated multiplication (<= 15 products): 1e-14 of the peak.
 #include "skdsp_internal.hpp"
 #include <complex>

@@ -2,7 +2,7 @@
 //
 // Serves  scipy.signal.sosfilt(sos,x)   multirate_helper.py:173,182,190 (multirate_IIR)
 //         scipy.signal.lfilter(b,a,x)   multirate_helper.py:74,81        (rate_change; the
-//                                       transfer function is factored into biquads by capi.hip)
+//                                       transfer function is factored into biquads by iir_api.hip)
 // with zero initial state, as the reference always calls them.
 //
 // The recurrence is serial in n, so the signal is cut into J contiguous chunks of T
@@ -1195,7 +1195,7 @@ int iir_dispatch_shape_f64(IirHandle *h, IirArgs &a, int nbatch, int W, hipStrea
 
 #if SK_SCAN_PART != 2
 // x_dev/y_dev: real planar arrays (float or double per h->dtype's precision); complex
-// callers deinterleave first (capi) and pass nbatch = 2 with batch_stride.
+// callers deinterleave first (iir_api.hip) and pass nbatch = 2 with batch_stride.
 int iir_launch_planar(IirHandle *h, const void *x, int64_t n, int nbatch, int64_t batch_stride, void *y, hipStream_t s,
                       const double *zi_host, double *zf_host, int interleaved, int dec)
 {

@@ -5,7 +5,7 @@
 // transitions instead; for well-conditioned cascades the two agree to the rounding of float64, but a 40th-order Chebyshev cascade is good
 // to 1e-6 of its output in float64 AT BEST -- two evaluations of the reference itself, sections in another order, lie that far apart --
 // and the scans lose another 30 - 400 x that spread on such designs (measured: profiles/r05/iir_illcond.txt).  Handles whose cascade
-// shows a float64 spread that the scans would lift above the contract (capi.hip: the probe at creation) therefore run HERE: the recursion
+// shows a float64 spread that the scans would lift above the contract (iir_api.hip: the probe at creation) therefore run HERE: the recursion
 // itself, in the reference's operation order, without fused multiply-adds -- bit for bit what scipy computes for float64 signals.
 //
 // One wave per row (a complex signal is two rows).  Lane s holds section s; the samples move down the lanes in BLOCKS of kSeqB: at block

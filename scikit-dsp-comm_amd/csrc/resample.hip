@@ -440,7 +440,7 @@ __global__ __launch_bounds__(256) void widen_kernel(const float4 *__restrict__ s
     if (blockIdx.x == 0 && (int)threadIdx.x < tail) dst[4 * n4 + threadIdx.x] = (double)tail_src[threadIdx.x];
 }
 
-// y[i] += t[i] over real scalars (the partial results of a tap-partitioned FIR, capi.hip)
+// y[i] += t[i] over real scalars (the partial results of a tap-partitioned FIR, fir_api.hip)
 template <typename R>
 __global__ __launch_bounds__(256) void accumulate_kernel(R *__restrict__ y, const R *__restrict__ t, int64_t n)
 {

@@ -61,7 +61,7 @@ struct Options {
     int fir_up_ols_min = 64;  // multirate_FIR.up: phases of at least this many taps MAY go through the overlap-save walk (the cost model
                               // of fir_up_prefers_ols decides); 0: never; -k: always from k taps per phase on (A/B switch)
     int fir_up_rows_min = -1; // multirate_FIR.up through the overlap-save walk: from this L on the phases leave as rows and a second kernel weaves them
-                              // (-1: the measured crossover per dtype, fir_up_rows in capi.hip; 0: never)
+                              // (-1: the measured crossover per dtype, fir_up_rows in fir_api.hip; 0: never)
     int fir_up_pair = 1;      // 0: float32 .up through the overlap-save walk never pairs its phases (A/B switch)
     int fir_up4k = 1;         // 0: multirate_FIR.up never through the one-workgroup-per-input-tile interpolator (fir_up4k.hip); the older engines instead (A/B switch)
     int fir_up2k = 1;         // the 2048-point tile with all phases per thread (fir_up2k.hip): 1 from five passes on (complex64: L >= 5, float32: L >= 9), 2 always, 0 never (A/B switch)
@@ -96,7 +96,7 @@ Options &opt();
 // entry points use from their own worker threads to spread a long host vector over all of them.  Each slot has its own
 // lock: calls that run on different slots do not serialise each other.
 constexpr int kMaxSlots = 16;
-struct HostPipe;  // capi.hip: pinned-free chunk pipeline state (streams, events, double buffers)
+struct HostPipe;  // host_pipe.hip: pinned-free chunk pipeline state (streams, events, double buffers)
 struct Context {
     bool ready = false;
     int slot = 0;
@@ -243,11 +243,11 @@ struct FirHandle : HandleBase {
     struct Ols64Up { int L; Ols64Plan *plan; };
     std::vector<Ols64Up> ols64_up;
     // Filters longer than one kernel launch takes (fir_part_len) run as partial FIRs over consecutive tap segments,
-    // each applied to the correspondingly delayed input and summed (capi.hip): parts[s] holds taps [s seg, (s+1) seg).
+    // each applied to the correspondingly delayed input and summed (fir_api.hip): parts[s] holds taps [s seg, (s+1) seg).
     std::vector<FirHandle *> parts;
     int part_seg = 0;
     // Calls FROM REST over fewer samples than taps only ever reach the first n taps: they run on a copy of the filter cut to the next power of
-    // two >= n (capi.hip, fir_head) -- exact, and the float32 rounding then scales with the taps that matter, not with the whole filter
+    // two >= n (fir_api.hip, fir_head) -- exact, and the float32 rounding then scales with the taps that matter, not with the whole filter
     std::vector<FirHandle *> heads;
     ~FirHandle();
 };
@@ -334,12 +334,12 @@ struct IirHandle : HandleBase {
     // scipy.signal.sosfilt takes any number of sections, and so does this.
     std::vector<IirHandle *> groups;
     // float32 handles whose sections cannot be grouped in float32 (the rounding of the signal between two groups, amplified by the rest
-    // of the cascade, would break the float32 contract: capi.hip) and are too many for one launch sequence: the same cascade as a float64
+    // of the cascade, would break the float32 contract: iir_api.hip) and are too many for one launch sequence: the same cascade as a float64
     // handle; the signal is widened, filtered and narrowed on the device
     IirHandle *twin64 = nullptr;
     void *twin_in = nullptr, *twin_out = nullptr;
     size_t twin_in_bytes = 0, twin_out_bytes = 0;
-    // Cascades whose float64 result is itself uncertain beyond what the scans may add to it (capi.hip: the probe at creation) run the reference's
+    // Cascades whose float64 result is itself uncertain beyond what the scans may add to it (iir_api.hip: the probe at creation) run the reference's
     // own recursion (iir_seq.hip): the caller's sections [nsec][5], the relative float64 spread the probe measured
     bool seq = false;
     double seq_spread = 0.0;

@@ -157,6 +157,17 @@ def test_interpolator_decimator_tiles_host_emulation(tmp_path, name):
     assert out.strip().endswith("OK"), out
 
 
+def test_iir_design_decisions_host_run(tmp_path):
+    """Compiles csrc/iir_design.hpp for the HOST (standard headers only: no device toolchain) and runs the numerical code of IIR handle
+    creation on inputs whose results the code determines exactly: the group split, the spread probe, the group-boundary cost, the
+    unit-tail re-factorisation, (b, a) -> sections and the sos row check."""
+    exe = str(tmp_path / "iir_design_emul")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "scikit-dsp-comm_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "host", "iir_design_emul.cpp"), "-o", exe])
+    out = subprocess.run([exe], stdout=subprocess.PIPE).stdout.decode()
+    assert out.strip().endswith("OK"), out
+
+
 def test_tf2sos_factorisation_matches_reference_tf_outputs():
     """skdsp_tf_create runs (b,a) as biquads (host-only factorisation, no GPU needed): the
     factored cascade, evaluated by the oracle's sosfilt, must reproduce the REFERENCE's
