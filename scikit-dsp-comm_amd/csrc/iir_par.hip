@@ -36,6 +36,7 @@
 // Nothing in A..B meets another wave: no workgroup barrier after the table load, so the 8 waves of a CU drift through
 // their memory / matrix / LDS / VALU phases independently.  N-D inputs are rows of the same launch (row = ticket / nseg).
 #include "iir_common.hpp"
+#include "iir_par_plan.hpp"
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -1080,25 +1081,28 @@ __global__ __launch_bounds__(kIirThreads, (UPJ && NSEC <= 4 && sizeof(IO) == 4) 
 }
 
 // ------------------------------------------------------------------------------------------------------- host side
+// The numerics (par_expand, par_v32_probe, the table values) and the dispatch decision (par_choose) are iir_par_plan.hpp: standard headers only,
+// run on the host by tests/host/iir_par_plan_emul.cpp.  Here: the device copies of the tables, the launch arguments and the one launch.
+static_assert(kParPlanMaxK == kParMaxK && kParPlanT32 == SK_PAR_T32 && kParPlanStageM2 == kParStageM2, "iir_par_plan.hpp mirrors these constants");
+static_assert(par_stage_image_bytes(4) == (int64_t)64 * Stage<float>::pitch * (int64_t)sizeof(float) &&
+              par_stage_image_bytes(8) == (int64_t)64 * Stage<double>::pitch * (int64_t)sizeof(double), "par_stage_image_bytes is 64 rows of Stage<IO>");
+
 struct ParTables {
-    int T = 0;
-    int n_lv = 0, K = 0;         // K = 0: the filter remembers more than kParMaxK segments of this length (not served)
-    double *gt_dev = nullptr;    // G in MFMA A-operand order [T / 4][64]
-    double *lvl_dev = nullptr;   // Phi^(2^l), l = 0..5: [6][nsec][4]
-    double *psi_dev = nullptr;   // Psi^m, m = 1..kParMaxK-1, Psi = Phi^(chunks per segment): [kParMaxK - 1][nsec][4]
+    int T = 0;                   // 0: not made yet
+    int n_lv = 0, K = 0;         // K = 0: the filter remembers more than par_max_k segments of this length (not served)
+    double *gt_dev = nullptr;    // ParTableValues::gt, lvl, psi on the device
+    double *lvl_dev = nullptr;
+    double *psi_dev = nullptr;
     int v32 = 0;                 // V = G x in float32 for chunks of this length (par_v32_probe): 0 not probed, 1 admitted, -1 refused
     double v32_err = 0.0;        // ... the worst probe error it showed
 };
 
 struct ParPlan {
     int state = 0;               // 0 untested, 1 expansion accepted, -1 not applicable
-    int nsec = 0;
-    long double a1[8], a2[8], r0[8], r1[8], c0 = 0.0L;
-    double na1[8], na2[8], al[8], be[8], gamma = 0.0;
-    double kappa = 0.0, ir_err = 0.0, l1h = 0.0;   // (l1h: the l1 norm of the impulse response -- the forward bound per unit input)
-    ParTables tab[8];            // [0] float32 (T = 128), [1] float64 (T = 64), [2] complex64, [3] complex128 (32 chunks per segment), [4] / [5] float32 / complex64 with T = 96 (.dn, .up), [6] / [7] float64 / complex128 with T = 96 (.up)
+    ParExpansion e;
+    ParTables tab[8];            // by slot (iir_par_plan.hpp: par_slot_T and its neighbours)
     struct UpJump { int up; double *dev; };
-    std::vector<UpJump> upj;     // per L: [L][2 nsec] rows c A^j + [nsec][4] blocks of A^L (UPJ kernels)
+    std::vector<UpJump> upj;     // per L: par_upj_values on the device (UPJ kernels)
     unsigned long long *lbg_dev = nullptr;
     size_t lbg_cap = 0;
     unsigned long long *ticket_dev = nullptr;
@@ -1120,294 +1124,11 @@ void iir_par_free(ParPlan *p)
     delete p;
 }
 
-namespace {
-struct Q2 { long double u, v; };   // u + v q  in R[q] / (1 + a1 q + a2 q^2)
-
-// partial fractions of prod_k B_k(q) / A_k(q), q = z^-1, by arithmetic modulo each denominator
-bool par_expand(const double *coef, int nsec, ParPlan &P)
-{
-    long double b[8][3], a[8][3];
-    int degA[8], degB[8], sumA = 0, sumB = 0;
-    for (int k = 0; k < nsec; ++k) {
-        const double *c = coef + 5 * k;
-        b[k][0] = c[0]; b[k][1] = c[1]; b[k][2] = c[2];
-        a[k][0] = 1.0L; a[k][1] = c[3]; a[k][2] = c[4];
-        for (int i = 0; i < 5; ++i)
-            if (!std::isfinite(c[i])) return false;
-        degA[k] = a[k][2] != 0.0L ? 2 : (a[k][1] != 0.0L ? 1 : 0);
-        degB[k] = b[k][2] != 0.0L ? 2 : (b[k][1] != 0.0L ? 1 : 0);
-        sumA += degA[k];
-        sumB += degB[k];
-    }
-    if (sumB > sumA) return false;   // a polynomial part beyond the direct term: not a sum of these branches
-    P.c0 = 0.0L;
-    if (sumB == sumA) {
-        P.c0 = 1.0L;
-        for (int k = 0; k < nsec; ++k) P.c0 *= b[k][degB[k]] / a[k][degA[k]];
-    }
-    for (int k = 0; k < nsec; ++k) {
-        P.a1[k] = a[k][1];
-        P.a2[k] = a[k][2];
-        P.r0[k] = P.r1[k] = 0.0L;
-        if (degA[k] == 2) {
-            const long double a1 = a[k][1], a2 = a[k][2];
-            auto red = [&](const long double *c) { return Q2{c[0] - c[2] / a2, c[1] - c[2] * a1 / a2}; };
-            auto mul = [&](Q2 x, Q2 y) {
-                const long double vv = x.v * y.v;
-                return Q2{x.u * y.u - vv / a2, x.u * y.v + x.v * y.u - vv * a1 / a2};
-            };
-            Q2 acc{1.0L, 0.0L};
-            for (int jx = 0; jx < nsec; ++jx) {
-                acc = mul(acc, red(b[jx]));
-                if (jx == k) continue;
-                const Q2 d = red(a[jx]);
-                // inverse of d: [u, -v/a2; v, u - v a1/a2] [s; t] = [1; 0]
-                const long double m11 = d.u, m12 = -d.v / a2, m21 = d.v, m22 = d.u - d.v * a1 / a2;
-                const long double det = m11 * m22 - m12 * m21;
-                const long double scale = fabsl(m11 * m22) + fabsl(m12 * m21);
-                if (!(fabsl(det) > 1e-12L * scale) || !std::isfinite((double)det)) return false;   // a pole shared with another section
-                acc = mul(acc, Q2{m22 / det, -m21 / det});
-            }
-            P.r0[k] = acc.u;
-            P.r1[k] = acc.v;
-        } else if (degA[k] == 1) {
-            const long double q0 = -1.0L / a[k][1];
-            long double val = 1.0L;
-            for (int jx = 0; jx < nsec; ++jx) {
-                val *= b[jx][0] + b[jx][1] * q0 + b[jx][2] * q0 * q0;
-                if (jx == k) continue;
-                const long double den = a[jx][0] + a[jx][1] * q0 + a[jx][2] * q0 * q0;
-                if (!(fabsl(den) > 1e-12L)) return false;
-                val /= den;
-            }
-            P.r0[k] = val;
-        }
-        if (!std::isfinite((double)P.r0[k]) || !std::isfinite((double)P.r1[k])) return false;
-    }
-    if (!std::isfinite((double)P.c0)) return false;
-    long double gam = P.c0;
-    for (int k = 0; k < nsec; ++k) {
-        P.na1[k] = (double)(-P.a1[k]);
-        P.na2[k] = (double)(-P.a2[k]);
-        P.al[k] = (double)(P.r1[k] - P.r0[k] * P.a1[k]);
-        P.be[k] = (double)(-P.r0[k] * P.a2[k]);
-        gam += P.r0[k];
-    }
-    P.gamma = (double)gam;
-    // acceptance: the expansion with its double coefficients against the cascade (long double DF2T), impulse response
-    const int NI = 8192;
-    long double zc[16] = {0}, w1[8] = {0}, w2[8] = {0};
-    long double hmax = 0.0L, emax = 0.0L, l1h = 0.0L, l1b = fabsl((long double)P.gamma);
-    for (int n = 0; n < NI; ++n) {
-        long double xin = n == 0 ? 1.0L : 0.0L, xc = xin;
-        for (int s = 0; s < nsec; ++s) {
-            const double *c = coef + 5 * s;
-            const long double yv = (long double)c[0] * xc + zc[2 * s];
-            zc[2 * s] = (long double)c[1] * xc - (long double)c[3] * yv + zc[2 * s + 1];
-            zc[2 * s + 1] = (long double)c[2] * xc - (long double)c[4] * yv;
-            xc = yv;
-        }
-        long double yp = (long double)P.gamma * xin;
-        for (int s = 0; s < nsec; ++s) {
-            const long double br = (long double)P.al[s] * w1[s] + (long double)P.be[s] * w2[s];
-            yp += br;
-            if (n > 0) l1b += fabsl(br);
-            const long double w0 = xin + (long double)P.na1[s] * w1[s] + (long double)P.na2[s] * w2[s];
-            w2[s] = w1[s];
-            w1[s] = w0;
-        }
-        hmax = std::max(hmax, fabsl(xc));
-        emax = std::max(emax, fabsl(xc - yp));
-        l1h += fabsl(xc);
-    }
-    if (!(hmax > 0.0L) || !std::isfinite((double)emax) || !std::isfinite((double)l1b)) return false;
-    P.ir_err = (double)(emax / hmax);
-    P.kappa = (double)(l1b / l1h);
-    P.l1h = (double)l1h;
-    return P.ir_err <= 1e-12 && P.kappa <= 1e3;
-}
-
-// V32 (see the kernel): may the from-rest end states of T-sample chunks of THIS filter be formed in float32?  The error such a state carries reaches the
-// outputs of the next chunks through the output taps, amplified by whatever cancels between the branches -- no norm of the expansion predicts it (an
-// elliptic band-pass with a cancellation factor of 2.8 shows 1.6e-6, one with 3.7 shows 4e-7), so it is MEASURED: the float32 chain of the matrix
-// instruction (acc = fmaf(G[t], x[t], acc), oldest sample first, G rounded to float32 -- bit for bit what v_mfma_f32_16x16x4_f32 computes) against the
-// exact from-rest state, on the inputs that are worst for it -- coherent ones: DC, the Nyquist alternation, a tone on every section's resonance -- and on
-// noise; the state errors are carried from chunk to chunk by the exact transition and through the output taps sample by sample.  Returned: the worst
-// output error over the probes, relative to the probe's output peak (or, for stop-band probes, 1 % of the forward bound -- the same floor the tests use).
-static double par_v32_probe(const ParPlan &P, int T)
-{
-    const int N = P.nsec, NCH = 24, n = NCH * T;
-    std::vector<float> g32((size_t)2 * N * T);
-    std::vector<double> gd((size_t)2 * N * T);
-    for (int k = 0; k < N; ++k) {
-        long double g0 = 1.0L, g1 = 0.0L;
-        for (int t = T - 1; t >= 0; --t) {
-            gd[((size_t)2 * k) * T + t] = (double)g0;
-            gd[((size_t)2 * k + 1) * T + t] = (double)g1;
-            g32[((size_t)2 * k) * T + t] = (float)(double)g0;
-            g32[((size_t)2 * k + 1) * T + t] = (float)(double)g1;
-            const long double g2 = -P.a1[k] * g0 - P.a2[k] * g1;
-            g1 = g0;
-            g0 = g2;
-        }
-    }
-    std::vector<std::vector<float>> probes;
-    {
-        std::vector<float> x((size_t)n);
-        unsigned long long lcg = 0x2545F4914F6CDD1Dull;
-        for (int i = 0; i < n; ++i) {
-            double a = 0.0;
-            for (int q = 0; q < 4; ++q) {
-                lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
-                a += (double)(lcg >> 11) / 9007199254740992.0 - 0.5;
-            }
-            x[i] = (float)(a * 1.7320508075688772);
-        }
-        probes.push_back(x);
-        for (int i = 0; i < n; ++i) x[i] = 1.0f;
-        probes.push_back(x);
-        for (int i = 0; i < n; ++i) x[i] = (i & 1) ? -1.0f : 1.0f;
-        probes.push_back(x);
-        for (int k = 0; k < N; ++k) {
-            const double a1 = (double)P.a1[k], a2 = (double)P.a2[k];
-            if (!(a2 > 0.0) || a1 * a1 >= 4.0 * a2) continue;   // (real poles: DC / Nyquist cover them)
-            const double th = std::acos(std::max(-1.0, std::min(1.0, -a1 / (2.0 * std::sqrt(a2)))));
-            for (int i = 0; i < n; ++i) x[i] = (float)std::cos(th * i);
-            probes.push_back(x);
-        }
-    }
-    double worst = 0.0;
-    for (const auto &x : probes) {
-        // the exact output (the parallel form in double, straight through) for the scale; the error by linearity: the state errors alone, carried exactly
-        double ymax = 0.0, xmax = 0.0;
-        {
-            std::vector<double> w1((size_t)N, 0.0), w2((size_t)N, 0.0);
-            for (int i = 0; i < n; ++i) {
-                double yv = P.gamma * (double)x[i];
-                for (int k = 0; k < N; ++k) {
-                    yv += P.al[k] * w1[k] + P.be[k] * w2[k];
-                    const double w0 = (double)x[i] + P.na1[k] * w1[k] + P.na2[k] * w2[k];
-                    w2[k] = w1[k];
-                    w1[k] = w0;
-                }
-                ymax = std::max(ymax, std::fabs(yv));
-                xmax = std::max(xmax, (double)std::fabs(x[i]));
-            }
-        }
-        std::vector<double> e1((size_t)N, 0.0), e2((size_t)N, 0.0);   // error of (w[n-1], w[n-2]) at the start of the current chunk
-        double emax = 0.0;
-        for (int j = 0; j < NCH; ++j) {
-            // outputs of chunk j see the start-state error through the taps; the error state runs the homogeneous recurrence
-            std::vector<double> f1 = e1, f2 = e2;
-            for (int t = 0; t < T; ++t) {
-                double ev = 0.0;
-                for (int k = 0; k < N; ++k) {
-                    ev += P.al[k] * f1[k] + P.be[k] * f2[k];
-                    const double f0 = P.na1[k] * f1[k] + P.na2[k] * f2[k];
-                    f2[k] = f1[k];
-                    f1[k] = f0;
-                }
-                emax = std::max(emax, std::fabs(ev));
-            }
-            // this chunk's from-rest end state: the float32 chain against the double sum of the same products with the unrounded G
-            for (int k = 0; k < N; ++k) {
-                for (int c = 0; c < 2; ++c) {
-                    const float *gf = g32.data() + ((size_t)2 * k + c) * T;
-                    const double *ge = gd.data() + ((size_t)2 * k + c) * T;
-                    float acc = 0.0f;
-                    long double ex = 0.0L;
-                    for (int t = 0; t < T; ++t) {
-                        acc = std::fmaf(gf[t], x[(size_t)j * T + t], acc);
-                        ex += (long double)ge[t] * (long double)x[(size_t)j * T + t];
-                    }
-                    (c == 0 ? f1[k] : f2[k]) += (double)acc - (double)ex;   // e_(j+1) = Phi e_j + delta_j (f holds Phi e_j now)
-                }
-            }
-            e1 = f1;
-            e2 = f2;
-        }
-        const double scale = std::max(ymax, 1e-2 * P.l1h * xmax);
-        if (!(scale > 0.0) || !std::isfinite(emax)) return 1.0;
-        worst = std::max(worst, emax / scale);
-    }
-    return worst;
-}
-constexpr double kParV32Limit = 5e-7;   // of the 1e-6 the float32 contract allows: the rest stays with the recurrence, the output rounding and the inputs no probe covers
-
-struct M2 { long double m[4]; };
-M2 m2mul(const M2 &x, const M2 &y)
-{
-    return M2{{x.m[0] * y.m[0] + x.m[1] * y.m[2], x.m[0] * y.m[1] + x.m[1] * y.m[3], x.m[2] * y.m[0] + x.m[3] * y.m[2],
-               x.m[2] * y.m[1] + x.m[3] * y.m[3]}};
-}
-long double m2max(const M2 &x) { return std::max(std::max(fabsl(x.m[0]), fabsl(x.m[1])), std::max(fabsl(x.m[2]), fabsl(x.m[3]))); }
-
-int par_tables(ParPlan &P, ParTables &tb, int T, int chunks, long double negl, int kmax, hipStream_t s)
-{
-    const int LV = chunks == 64 ? 6 : 5;   // scan levels inside a wave segment of `chunks` chunks
-    const int N = P.nsec;
-    tb.T = T;
-    std::vector<double> lvl((size_t)6 * N * 4), psi((size_t)(kParMaxK - 1) * N * 4), gt((size_t)T * 16, 0.0);
-    long double lvmax[7] = {0}, psimax[kParMaxK + 1] = {0};
-    for (int k = 0; k < N; ++k) {
-        // one-sample zero-input transition of (w[n-1], w[n-2]);  Phi = its T-th power
-        M2 one{{-P.a1[k], -P.a2[k], 1.0L, 0.0L}}, Phi{{1.0L, 0.0L, 0.0L, 1.0L}}, sq = one;
-        for (int e = T; e; e >>= 1) {
-            if (e & 1) Phi = m2mul(Phi, sq);
-            sq = m2mul(sq, sq);
-        }
-        M2 pw = Phi;
-        for (int l = 0; l <= LV; ++l) {
-            lvmax[l] = std::max(lvmax[l], m2max(pw));
-            if (!std::isfinite((double)m2max(pw))) return 1;
-            if (l < LV)
-                for (int i = 0; i < 4; ++i) lvl[((size_t)l * N + k) * 4 + i] = (double)pw.m[i];
-            if (l < LV) pw = m2mul(pw, pw);
-        }
-        const M2 Psi = pw;   // Phi^chunks: the transition over one wave segment
-        M2 pk = Psi;
-        for (int m = 1; m <= kParMaxK; ++m) {
-            psimax[m] = std::max(psimax[m], m2max(pk));
-            if (m < kParMaxK)
-                for (int i = 0; i < 4; ++i) psi[((size_t)(m - 1) * N + k) * 4 + i] = (double)pk.m[i];
-            pk = m2mul(pk, Psi);
-        }
-        // G rows 2k, 2k+1: g[T-1-t], g[T-2-t], g = impulse response of 1 / A_k; as the MFMA A operand of step t / 4:
-        // lane l holds row l & 15, column 4 (t / 4) + (l >> 4)
-        long double g0 = 1.0L, g1 = 0.0L;   // g[i], g[i-1]
-        for (int t = T - 1; t >= 0; --t) {
-            const size_t at = (size_t)(t / 4) * 64 + (size_t)(t % 4) * 16;
-            gt[at + 2 * k] = (double)g0;
-            gt[at + 2 * k + 1] = (double)g1;
-            const long double g2 = -P.a1[k] * g0 - P.a2[k] * g1;
-            g1 = g0;
-            g0 = g2;
-        }
-    }
-    tb.n_lv = LV;
-    for (int l = LV; l >= 0; --l)
-        if (lvmax[l] < negl) tb.n_lv = std::min(tb.n_lv, l);
-    tb.K = 0;
-    for (int m = 1; m <= kmax; ++m)
-        if (psimax[m] < negl) { tb.K = m; break; }
-    if (tb.K == 0) return 1;   // remembers more than kParMaxK segments
-    if (tb.n_lv < LV) tb.K = 1;
-    SK_HIP(hipMalloc((void **)&tb.gt_dev, gt.size() * 8));
-    SK_HIP(hipMalloc((void **)&tb.lvl_dev, lvl.size() * 8));
-    SK_HIP(hipMalloc((void **)&tb.psi_dev, psi.size() * 8));
-    SK_HIP(hipMemcpyAsync(tb.gt_dev, gt.data(), gt.size() * 8, hipMemcpyHostToDevice, s));
-    SK_HIP(hipMemcpyAsync(tb.lvl_dev, lvl.data(), lvl.size() * 8, hipMemcpyHostToDevice, s));
-    SK_HIP(hipMemcpyAsync(tb.psi_dev, psi.data(), psi.size() * 8, hipMemcpyHostToDevice, s));
-    SK_HIP(hipStreamSynchronize(s));
-    return SKDSP_OK;
-}
-}  // namespace
-
-// host-only: the expansion of a handle's cascade (tests; no GPU needed).  out = [c0, (a1, a2, r0, r1) x nsec, kappa, ir_err]
+// host-only: the expansion of a handle's cascade (tests; no GPU needed).  out = [c0, (a1, a2, r0, r1) x nsec, kappa, ir_err, v32_err at 128, at 96]:
+// 5 + 4 nsec doubles
 int iir_par_expand_host(const double *coef, int nsec, double *out, int *accepted)
 {
-    ParPlan P;
-    P.nsec = nsec;
+    ParExpansion P;
     const bool ok = nsec >= 1 && nsec <= 8 && par_expand(coef, nsec, P);
     if (accepted) *accepted = ok ? 1 : 0;
     if (out) {
@@ -1427,91 +1148,156 @@ int iir_par_expand_host(const double *coef, int nsec, double *out, int *accepted
     return SKDSP_OK;
 }
 
-// .dn: can a segment's kept outputs be gathered in the wave's stage image (see ParArgs::dec_compact)?
-// (lean: the 96-sample kernels put a kept output into its slot straight from the sum -- no unit to pick it from, so M may be below the samples of a unit)
-template <typename IO, bool CPLX> static bool par_dec_compact(int dec, int64_t seg_samples, bool lean = false, int64_t image_bytes = 0)
+static int par_upload(const std::vector<double> &v, double **dev, hipStream_t s)
 {
-    constexpr int elems = 16 / (int)sizeof(IO), ls = CPLX ? 2 : 1;
-    const int64_t slots = (seg_samples / dec + 2) * ls;
-    const int64_t bytes = (slots + slots / 32 + 2) * (int64_t)sizeof(IO);
-    return (lean || dec >= elems) && bytes <= (image_bytes ? image_bytes : (int64_t)64 * Stage<IO>::pitch * (int64_t)sizeof(IO)) && opt().iir_dn_compact;
+    SK_HIP(hipMalloc((void **)dev, v.size() * 8));
+    SK_HIP(hipMemcpyAsync(*dev, v.data(), v.size() * 8, hipMemcpyHostToDevice, s));
+    return SKDSP_OK;
 }
 
-// .dn with dec below the samples of a 16-byte unit (float32 / complex64, dec = 2, 3): gathered in two ranges of chunks behind the recurrence
-template <typename IO, bool CPLX> static bool par_dec_rounds(int dec)
+// par_choose's K query: the tables of a slot, made on first use.  Returns K (0: not served at this chunk length) or a negative error
+static int par_slot_K(ParPlan &P, int slot, hipStream_t s)
 {
-    return sizeof(IO) == 4 && (dec == 2 || dec == 3) && opt().iir_dn_compact;
+    ParTables &tb = P.tab[slot];
+    if (tb.T != 0) return tb.K;
+    const ParTableValues v = par_table_values(P.e, par_slot_T(slot), par_slot_chunks(slot), par_slot_negl(slot), par_max_k(par_slot_dbl(slot)));
+    tb.T = par_slot_T(slot);
+    tb.n_lv = v.n_lv;
+    tb.K = v.failed ? 0 : v.K;
+    if (v.failed) return 0;
+    int rc = par_upload(v.gt, &tb.gt_dev, s);
+    if (!rc) rc = par_upload(v.lvl, &tb.lvl_dev, s);
+    if (!rc) rc = par_upload(v.psi, &tb.psi_dev, s);
+    if (rc) return rc;
+    SK_HIP(hipStreamSynchronize(s));
+    return tb.K;
 }
 
-
-// UPJ table of a plan for the factor L (see the kernel): rows c A^j, j = 0 .. L - 1, c = (al, be) of every section; then the 2 x 2 blocks of A^L
-static int par_upj_table(ParPlan &P, int L, const double **out)
+// UPJ table of a plan for the factor L, made on first use
+static int par_upj_table(ParPlan &P, int L, hipStream_t s, const double **out)
 {
     for (auto &u : P.upj)
         if (u.up == L) { *out = u.dev; return SKDSP_OK; }
-    const int N = P.nsec, D = 2 * N;
-    // layout: rows 0 .. L - 1; up to 4 biquads (the kernels that read rows in pairs) row 0 once more; the blocks of A^L
-    const size_t rows = (size_t)L + (N <= 4 ? 1 : 0);
-    std::vector<double> tab(rows * D + (size_t)N * 4);
-    for (int k = 0; k < N; ++k) {
-        const long double A[4] = {-P.a1[k], -P.a2[k], 1.0L, 0.0L};   // (w[n-1], w[n-2]) -> (w[n], w[n-1]) without input
-        long double c0 = (long double)P.al[k], c1 = (long double)P.be[k];   // the row c A^j
-        long double M[4] = {1.0L, 0.0L, 0.0L, 1.0L};                  // A^j
-        for (int j = 0; j < L; ++j) {
-            tab[(size_t)j * D + 2 * k] = (double)c0;
-            tab[(size_t)j * D + 2 * k + 1] = (double)c1;
-            const long double n0 = c0 * A[0] + c1 * A[2], n1 = c0 * A[1] + c1 * A[3];
-            c0 = n0; c1 = n1;
-            const long double m0 = M[0] * A[0] + M[1] * A[2], m1 = M[0] * A[1] + M[1] * A[3], m2 = M[2] * A[0] + M[3] * A[2], m3 = M[2] * A[1] + M[3] * A[3];
-            M[0] = m0; M[1] = m1; M[2] = m2; M[3] = m3;
-        }
-        if (N <= 4) {
-            tab[(size_t)L * D + 2 * k] = tab[2 * k];
-            tab[(size_t)L * D + 2 * k + 1] = tab[2 * k + 1];
-        }
-        for (int i = 0; i < 4; ++i) tab[rows * D + 4 * k + i] = (double)M[i];   // A^L
-    }
+    const std::vector<double> tab = par_upj_values(P.e, L);
     double *dev = nullptr;
-    SK_HIP(hipMalloc((void **)&dev, tab.size() * 8));
-    SK_HIP(hipMemcpy(dev, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+    const int rc = par_upload(tab, &dev, s);
+    if (rc) return rc;
+    SK_HIP(hipStreamSynchronize(s));
     P.upj.push_back(ParPlan::UpJump{L, dev});
     *out = dev;
     return SKDSP_OK;
 }
 
-template <typename IO, bool CPLX, int TT = 0, bool UPJ = false, int UPS = 0>
-static int launch_par_impl(IirHandle *h, ParPlan *p, ParTables &tb, const void *x, int64_t n, int nrow, int64_t x_stride, int64_t y_stride,
-                           void *y, hipStream_t s, int dec, int up);
-
-template <typename IO, bool CPLX, int TT = 0, bool UPJ = false, int UPS = 0>
-static int launch_par(IirHandle *h, ParPlan *p, ParTables &tb, const void *x, int64_t n, int nrow, int64_t x_stride, int64_t y_stride,
-                      void *y, hipStream_t s, int dec, int up = 1)
+// Which <N, IO, DECM, CPLX, TT, UPJ, UPS, V32> exist: the families <IO, TT, UPJ, UPS> par_choose names, and inside them the variants the kernel was
+// written for.  Nothing else is instantiated (this file is the long pole of the build), and par_launch_kernel refuses everything else.
+template <int N, typename IO, int DECM, bool CPLX, int TT, bool UPJ, int UPS, bool V32> constexpr bool par_kernel_exists()
 {
-#ifdef SK_PAR_DEV_F32REAL   // (developer builds: float32 real signals only -- a third of the instantiations)
-    if constexpr (sizeof(IO) == 8 || CPLX) return 1;
-    else
+#ifdef SK_PAR_DEV_NSEC   // (developer builds: one cascade length only)
+    if (N != SK_PAR_DEV_NSEC) return false;
 #endif
-    return launch_par_impl<IO, CPLX, TT, UPJ, UPS>(h, p, tb, x, n, nrow, x_stride, y_stride, y, s, dec, up);
+#ifdef SK_PAR_DEV_F32REAL   // (developer builds: float32 real signals only -- a third of the instantiations)
+    if (sizeof(IO) == 8 || CPLX) return false;
+#endif
+    constexpr bool io4 = sizeof(IO) == 4;
+    // UPJ: chunks of 96, every dtype.  Other chunks of 96 (.dn, .up by 3): 4-byte types.  Default chunks: plain / .dn and .up by 2 for every dtype, .up by 4 for 4-byte types
+    constexpr bool family = UPJ ? (TT == 96 && UPS == 0) : TT == 96 ? (io4 && (UPS == 0 || UPS == 3)) : (TT == 0 && (UPS == 0 || UPS == 2 || (UPS == 4 && io4)));
+    constexpr bool variant = DECM == 2 ? (io4 && !UPJ && UPS == 0)                              // (the .up families never decimate)
+                             : DECM == 3 ? (io4 && !UPJ && UPS == 0 && TT == 96 && N > 4)
+                             : DECM == 1 ? (!UPJ && UPS == 0)
+                                         : (UPJ || UPS != 0 || TT == 0);
+    constexpr bool v32 = !V32 || (N >= 7 && io4 && DECM <= 1 && !UPJ);
+    return family && variant && v32;
 }
 
-template <typename IO, bool CPLX, int TT, bool UPJ, int UPS>
-static int launch_par_impl(IirHandle *h, ParPlan *p, ParTables &tb, const void *x, int64_t n, int nrow, int64_t x_stride, int64_t y_stride,
-                           void *y, hipStream_t s, int dec, int up)
+struct ParLaunch {   // a launch, but for the kernel's template parameters
+    ParArgs a;
+    const ParExpansion *e;
+    const ParTables *tb;
+    const double *upj;   // UPJ: the jump table; else null
+    unsigned grid;
+    hipStream_t s;
+};
+
+static int par_no_kernel(int N, int elem_bytes, int DECM, bool CPLX, int TT, bool UPJ, int UPS, bool V32)
+{
+    set_error("iir: no parallel-form kernel for %d biquads, %d-byte %s samples, DECM %d, TT %d, UPJ %d, UPS %d, V32 %d", N, elem_bytes,
+              CPLX ? "complex" : "real", DECM, TT, (int)UPJ, UPS, (int)V32);
+    return SKDSP_ERR_UNSUPPORTED;
+}
+
+template <int N, typename IO, int DECM, bool CPLX, int TT, bool UPJ, int UPS, bool V32> static int par_launch_kernel(const ParLaunch &L)
+{
+    if constexpr (par_kernel_exists<N, IO, DECM, CPLX, TT, UPJ, UPS, V32>()) {
+        ParCoef<N> cf;
+        for (int k = 0; k < N; ++k) { cf.na1[k] = L.e->na1[k]; cf.na2[k] = L.e->na2[k]; cf.al[k] = L.e->al[k]; cf.be[k] = L.e->be[k]; }
+        cf.gamma = L.e->gamma;
+        if constexpr (V32) note_path("iir_par_v32");   // (tests assert which arithmetic ran by this record)
+        hipLaunchKernelGGL((iir_par_kernel<N, IO, DECM, CPLX, TT, UPJ, UPS, V32>), dim3(L.grid), dim3(kIirThreads), 0, L.s, L.a, cf,
+                           (const double *)L.tb->gt_dev, (const double *)L.tb->lvl_dev, (const double *)L.tb->psi_dev, 0ull, L.upj);
+        return SKDSP_OK;
+    } else
+        return par_no_kernel(N, (int)sizeof(IO), DECM, CPLX, TT, UPJ, UPS, V32);
+}
+
+// run time -> template parameters: the variant (DECM, V32), the cascade length, the sample type
+template <int N, typename IO, bool CPLX, int TT, bool UPJ, int UPS> static int par_launch_variant(int decm, bool v32, const ParLaunch &L)
+{
+    switch (2 * decm + (v32 ? 1 : 0)) {
+        case 0: return par_launch_kernel<N, IO, 0, CPLX, TT, UPJ, UPS, false>(L);
+        case 1: return par_launch_kernel<N, IO, 0, CPLX, TT, UPJ, UPS, true>(L);
+        case 2: return par_launch_kernel<N, IO, 1, CPLX, TT, UPJ, UPS, false>(L);
+        case 3: return par_launch_kernel<N, IO, 1, CPLX, TT, UPJ, UPS, true>(L);
+        case 4: return par_launch_kernel<N, IO, 2, CPLX, TT, UPJ, UPS, false>(L);
+        case 6: return par_launch_kernel<N, IO, 3, CPLX, TT, UPJ, UPS, false>(L);
+        default: return par_no_kernel(N, (int)sizeof(IO), decm, CPLX, TT, UPJ, UPS, v32);
+    }
+}
+
+template <typename IO, bool CPLX, int TT, bool UPJ, int UPS> static int par_launch_nsec(int nsec, int decm, bool v32, const ParLaunch &L)
+{
+    switch (nsec) {
+        case 1: return par_launch_variant<1, IO, CPLX, TT, UPJ, UPS>(decm, v32, L);
+        case 2: return par_launch_variant<2, IO, CPLX, TT, UPJ, UPS>(decm, v32, L);
+        case 3: return par_launch_variant<3, IO, CPLX, TT, UPJ, UPS>(decm, v32, L);
+        case 4: return par_launch_variant<4, IO, CPLX, TT, UPJ, UPS>(decm, v32, L);
+        case 5: return par_launch_variant<5, IO, CPLX, TT, UPJ, UPS>(decm, v32, L);
+        case 6: return par_launch_variant<6, IO, CPLX, TT, UPJ, UPS>(decm, v32, L);
+        case 7: return par_launch_variant<7, IO, CPLX, TT, UPJ, UPS>(decm, v32, L);
+        case 8: return par_launch_variant<8, IO, CPLX, TT, UPJ, UPS>(decm, v32, L);
+        default: break;
+    }
+    set_error("iir: parallel-form scan takes 1..8 biquads");
+    return SKDSP_ERR_UNSUPPORTED;
+}
+
+template <int TT, bool UPJ, int UPS> static int par_launch_dtype(bool dbl, bool interleaved, int nsec, int decm, bool v32, const ParLaunch &L)
+{
+    switch ((dbl ? 1 : 0) + (interleaved ? 2 : 0)) {
+        case 0: return par_launch_nsec<float, false, TT, UPJ, UPS>(nsec, decm, v32, L);
+        case 1: return par_launch_nsec<double, false, TT, UPJ, UPS>(nsec, decm, v32, L);
+        case 2: return par_launch_nsec<float, true, TT, UPJ, UPS>(nsec, decm, v32, L);
+        default: return par_launch_nsec<double, true, TT, UPJ, UPS>(nsec, decm, v32, L);
+    }
+}
+
+// the call par_choose decided on: the launch arguments, the scratch a launch needs, the kernel
+static int launch_par(IirHandle *h, ParPlan *p, const ParChoice &c, bool dbl, bool interleaved, const void *x, int64_t n, int nrow, int64_t x_stride,
+                      int64_t y_stride, void *y, hipStream_t s, int dec, int up)
 {
     note_path("iir_par");   // (here, not in iir_par_launch: that function returns 1 -- nothing launched -- for every call the parallel form does not take)
+    ParTables &tb = p->tab[c.slot];
     const int T = tb.T;
-    // V32 (see the kernel): float32 / complex64 signals through 7 - 8 biquads, once the probe has admitted this filter at this chunk length
+    const size_t elem = dbl ? 8 : 4;
+    // V32 (see the kernel), once the probe has admitted this filter at this chunk length
     bool v32 = false;
-    // (not for .up by 8 or more through the general kernel: its from-rest states are formed per lane on the vector ALU from the FLOAT64 table -- `sparse` in the kernel)
-    if (sizeof(IO) == 4 && !UPJ && h->nsec >= 7 && opt().iir_par_v32 > 0 && !(UPS == 0 && dec <= 1 && up >= 8)) {
+    if (c.v32_wanted) {
         if (tb.v32 == 0) {
-            tb.v32_err = par_v32_probe(*p, T);
+            tb.v32_err = par_v32_probe(p->e, T);
             tb.v32 = tb.v32_err <= kParV32Limit ? 1 : -1;
         }
         v32 = tb.v32 == 1 || opt().iir_par_v32 >= 2;
-        if (v32) note_path("iir_par_v32");
     }
-    const int64_t S = (int64_t)(CPLX ? 32 : 64) * T;   // samples per wave segment
+    const int64_t S = (int64_t)(interleaved ? 32 : 64) * T;   // samples per wave segment
     const int64_t nseg = (n + S - 1) / S;
     SK_CHECK(nseg * nrow < (1 << 30), SKDSP_ERR_BADARG, "iir: too many segments");
     const int total = (int)(nseg * nrow);
@@ -1520,7 +1306,7 @@ static int launch_par_impl(IirHandle *h, ParPlan *p, ParTables &tb, const void *
         SK_HIP(hipMemsetAsync(p->ticket_dev, 0, 8 * kParTickets, s));
         p->ticket_count = 0;
     }
-    const size_t need = (size_t)total * (CPLX ? 64 : 32) * 8;
+    const size_t need = (size_t)total * (interleaved ? 64 : 32) * 8;
     if (need > p->lbg_cap) {
         if (p->lbg_dev) {
             SK_HIP(hipStreamSynchronize(s));
@@ -1531,7 +1317,8 @@ static int launch_par_impl(IirHandle *h, ParPlan *p, ParTables &tb, const void *
         SK_HIP(hipMemsetAsync(p->lbg_dev, 0, need, s));  // epoch 0 is never used as a tag
         p->lbg_cap = need;
     }
-    ParArgs a;
+    ParLaunch L;
+    ParArgs &a = L.a;
     a.x = x; a.y = y; a.n = n; a.x_stride = x_stride; a.y_stride = y_stride;
     a.nseg = (int)nseg; a.total = total;
     a.lb = p->lbg_dev; a.ticket = p->ticket_dev; a.ticket_base = p->ticket_count;
@@ -1540,92 +1327,38 @@ static int launch_par_impl(IirHandle *h, ParPlan *p, ParTables &tb, const void *
     a.n_lv = tb.n_lv; a.K = tb.K;
     a.err = async_err_dev(kAsyncErrIirLookback);
     SK_CHECK(a.err, SKDSP_ERR_HIP, "iir: no host-mapped error word");
-    a.aligned = ((uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0 && (nrow == 1 || ((x_stride * sizeof(IO)) % 16 == 0 && (y_stride * sizeof(IO)) % 16 == 0))) ? 1 : 0;
+    a.aligned = ((uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0 && (nrow == 1 || ((x_stride * elem) % 16 == 0 && (y_stride * elem) % 16 == 0))) ? 1 : 0;
     a.dec = dec > 1 ? dec : 1;
     a.dec_magic = a.dec > 1 ? (unsigned)((((unsigned long long)1 << 32) + a.dec - 1) / a.dec) : 0u;
-    // (M = 2 on 96-sample chunks, more than 4 biquads, float32 / complex64: the DECM = 3 kernels with their larger image)
-    const bool big_m2 = TT == 96 && sizeof(IO) == 4 && !UPJ && UPS == 0 && a.dec == 2 && h->nsec > 4 && opt().iir_dn_t96 != 3;
-    a.dec_compact = a.dec > 1 && par_dec_compact<IO, CPLX>(a.dec, S, TT == 96, big_m2 ? kParStageM2 : 0) ? 1 : 0;
-    a.dec_rounds = !a.dec_compact && par_dec_rounds<IO, CPLX>(a.dec) ? 2 : 1;
+    a.dec_compact = c.dec_compact ? 1 : 0;
+    a.dec_rounds = c.dec_rounds;
     a.up = up > 1 ? up : 1;
     a.up_magic = a.up > 1 ? (unsigned)((((unsigned long long)1 << 32) + a.up - 1) / a.up) : 0u;
     a.n_in = a.up > 1 ? n / a.up : n;
     a.n_keep = (n / a.dec) * a.dec;
-    const double *upj_tab = nullptr;
-    if constexpr (UPJ) {
-        const int rc = par_upj_table(*p, a.up, &upj_tab);
+    L.upj = nullptr;
+    if (c.UPJ) {
+        const int rc = par_upj_table(*p, a.up, s, &L.upj);
         if (rc) return rc;
     }
     {
-        const int64_t step = (int64_t)(64 / Stage<IO>::segs) * T;   // samples between a lane's staged segments
+        const int64_t step = (int64_t)(64 / (dbl ? Stage<double>::segs : Stage<float>::segs)) * T;   // samples between a lane's staged segments
         a.dec_dq = (int)(step / a.dec);
         a.dec_dr = (int)(step % a.dec);
     }
     // (whole rounds of kParTickets workgroups, so that every dispenser advances by the same amount: the surplus workgroups
     // draw segments beyond the last and leave)
-    const unsigned grid = (unsigned)(((total + 3) / 4 + kParTickets - 1) / kParTickets * kParTickets);
-    p->ticket_count += (unsigned long long)(grid / kParTickets);
-#define SK_PAR(N)                                                                                                       \
-    case N: {                                                                                                           \
-        ParCoef<N> cf;                                                                                                  \
-        for (int k = 0; k < N; ++k) { cf.na1[k] = p->na1[k]; cf.na2[k] = p->na2[k]; cf.al[k] = p->al[k]; cf.be[k] = p->be[k]; } \
-        cf.gamma = p->gamma;                                                                                            \
-        if (a.dec > 1 && a.dec_rounds > 1) {                                                                            \
-            if constexpr (sizeof(IO) == 4 && !UPJ && UPS == 0)   /* (the .up launchers never decimate: no decimating kernels on their account) */ \
-                hipLaunchKernelGGL((iir_par_kernel<N, IO, 2, CPLX, TT>), dim3(grid), dim3(kIirThreads), 0, s, a, cf,    \
-                                   (const double *)tb.gt_dev, (const double *)tb.lvl_dev, (const double *)tb.psi_dev, 0ull, (const double *)nullptr);  \
-        } else if (a.dec > 1 && big_m2 && a.dec_compact) {                                                              \
-            if constexpr (TT == 96 && sizeof(IO) == 4 && N > 4 && !UPJ && UPS == 0)                                     \
-                hipLaunchKernelGGL((iir_par_kernel<N, IO, 3, CPLX, TT>), dim3(grid), dim3(kIirThreads), 0, s, a, cf,    \
-                                   (const double *)tb.gt_dev, (const double *)tb.lvl_dev, (const double *)tb.psi_dev, 0ull, (const double *)nullptr);  \
-        } else if (a.dec > 1) {                                                                                         \
-            if constexpr (!UPJ && UPS == 0) {                                                                           \
-                if constexpr (N >= 7 && sizeof(IO) == 4) {                                                              \
-                    if (v32) {                                                                                          \
-                        hipLaunchKernelGGL((iir_par_kernel<N, IO, 1, CPLX, TT, false, 0, true>), dim3(grid), dim3(kIirThreads), 0, s, a, cf, \
-                                           (const double *)tb.gt_dev, (const double *)tb.lvl_dev, (const double *)tb.psi_dev, 0ull, (const double *)nullptr); \
-                        break;                                                                                          \
-                    }                                                                                                   \
-                }                                                                                                       \
-                hipLaunchKernelGGL((iir_par_kernel<N, IO, 1, CPLX, TT>), dim3(grid), dim3(kIirThreads), 0, s, a, cf,    \
-                                   (const double *)tb.gt_dev, (const double *)tb.lvl_dev, (const double *)tb.psi_dev, 0ull, (const double *)nullptr);  \
-            }                                                                                                           \
-        } else if constexpr (UPJ)                                                                                         \
-            hipLaunchKernelGGL((iir_par_kernel<N, IO, 0, CPLX, TT, true>), dim3(grid), dim3(kIirThreads), 0, s, a, cf,  \
-                               (const double *)tb.gt_dev, (const double *)tb.lvl_dev, (const double *)tb.psi_dev, 0ull, upj_tab); \
-        else if constexpr (UPS != 0) {                                                                                  \
-            if constexpr (N >= 7 && sizeof(IO) == 4) {                                                                  \
-                if (v32) {                                                                                              \
-                    hipLaunchKernelGGL((iir_par_kernel<N, IO, 0, CPLX, TT, false, UPS, true>), dim3(grid), dim3(kIirThreads), 0, s, a, cf, \
-                                       (const double *)tb.gt_dev, (const double *)tb.lvl_dev, (const double *)tb.psi_dev, 0ull, (const double *)nullptr); \
-                    break;                                                                                              \
-                }                                                                                                       \
-            }                                                                                                           \
-            hipLaunchKernelGGL((iir_par_kernel<N, IO, 0, CPLX, TT, false, UPS>), dim3(grid), dim3(kIirThreads), 0, s, a, cf, \
-                               (const double *)tb.gt_dev, (const double *)tb.lvl_dev, (const double *)tb.psi_dev, 0ull, (const double *)nullptr); \
-        } else if constexpr (TT == 0) {                                                                                 \
-            if constexpr (N >= 7 && sizeof(IO) == 4) {                                                                  \
-                if (v32) {                                                                                              \
-                    hipLaunchKernelGGL((iir_par_kernel<N, IO, 0, CPLX, 0, false, 0, true>), dim3(grid), dim3(kIirThreads), 0, s, a, cf, \
-                                       (const double *)tb.gt_dev, (const double *)tb.lvl_dev, (const double *)tb.psi_dev, 0ull, (const double *)nullptr); \
-                    break;                                                                                              \
-                }                                                                                                       \
-            }                                                                                                           \
-            hipLaunchKernelGGL((iir_par_kernel<N, IO, 0, CPLX>), dim3(grid), dim3(kIirThreads), 0, s, a, cf,            \
-                               (const double *)tb.gt_dev, (const double *)tb.lvl_dev, (const double *)tb.psi_dev, 0ull, (const double *)nullptr);      \
-        }                                                                                                               \
-        break;                                                                                                          \
-    }
-    switch (h->nsec) {
-#ifdef SK_PAR_DEV_NSEC   // (developer builds: one cascade length only -- this file is the long pole of the build)
-        SK_PAR(SK_PAR_DEV_NSEC)
-#else
-        SK_PAR(1) SK_PAR(2) SK_PAR(3) SK_PAR(4) SK_PAR(5) SK_PAR(6) SK_PAR(7)
-        SK_PAR(8)
-#endif
-        default: SK_CHECK(false, SKDSP_ERR_UNSUPPORTED, "iir: parallel-form scan takes 1..8 biquads");
-    }
-#undef SK_PAR
+    L.grid = (unsigned)(((total + 3) / 4 + kParTickets - 1) / kParTickets * kParTickets);
+    L.e = &p->e; L.tb = &tb; L.s = s;
+    int rc;
+    if (c.UPJ) rc = par_launch_dtype<96, true, 0>(dbl, interleaved, h->nsec, c.DECM, v32, L);
+    else if (c.TT == 96) rc = c.UPS == 3 ? par_launch_dtype<96, false, 3>(dbl, interleaved, h->nsec, c.DECM, v32, L)
+                                         : par_launch_dtype<96, false, 0>(dbl, interleaved, h->nsec, c.DECM, v32, L);
+    else if (c.UPS == 2) rc = par_launch_dtype<0, false, 2>(dbl, interleaved, h->nsec, c.DECM, v32, L);
+    else if (c.UPS == 4) rc = par_launch_dtype<0, false, 4>(dbl, interleaved, h->nsec, c.DECM, v32, L);
+    else rc = par_launch_dtype<0, false, 0>(dbl, interleaved, h->nsec, c.DECM, v32, L);
+    if (rc) return rc;   // (nothing was launched: the dispensers stay where they are)
+    p->ticket_count += (unsigned long long)(L.grid / kParTickets);
     SK_HIP(hipGetLastError());
     return SKDSP_OK;
 }
@@ -1634,87 +1367,22 @@ static int launch_par_impl(IirHandle *h, ParPlan *p, ParTables &tb, const void *
 int iir_par_launch(IirHandle *h, const void *x, int64_t n, int nrow, int64_t x_stride, int64_t y_stride, void *y, hipStream_t s, int dec,
                    int interleaved, int up)
 {
-    if (interleaved && nrow != 1) return 1;
-    // .up: x holds n / up samples; one row, no decimation; the exact-division trick of the staging covers up <= 4096
-    if (up > 1 && (dec > 1 || nrow != 1 || up > 4096 || n % up != 0)) return 1;
-    if (h->order != 2 || h->nsec < 1 || h->nsec > 8) return 1;
+    if (h->order != 2 || !par_call_shape_ok(h->nsec, interleaved != 0, nrow, dec, up, n)) return 1;
+    const bool dbl = dtype_double(h->dtype);
+#ifdef SK_PAR_DEV_F32REAL   // (developer builds have the float32 real kernels only: every other signal takes the cascade kernels)
+    if (dbl || interleaved) return 1;
+#endif
     if (!h->par) {
         h->par = new ParPlan();
-        h->par->nsec = h->nsec;
-        h->par->state = par_expand(h->coef.data(), h->nsec, *h->par) ? 1 : -1;
+        h->par->state = par_expand(h->coef.data(), h->nsec, h->par->e) ? 1 : -1;
     }
     ParPlan *p = h->par;
     if (p->state != 1) return 1;
-    const bool dbl = dtype_double(h->dtype);
-    // .dn of float32 / complex64 signals by a divisor of 96: chunks of 96 samples, so that all lanes of a wave walk the same phase (see the kernel).
-    // From M = 4 on the 96-sample kernel is the compact store in its lean form (DNL in the kernel: which samples are kept is wave-uniform).  Measured, 2^26 inputs
-    // (_var/dn_t96.py, profiles/r05/iir_dn_lean.txt): order-8 Butterworth M = 4 .. 96 float32 0.105 - 0.122 -> 0.086 - 0.099 ms, complex64 0.198 - 0.223 -> 0.172 - 0.196;
-    // 8 biquads: float32 - 3 .. - 6 %, complex64 - 3 % where 3 divides M (128-sample chunks then start on three phases) and + 4 .. + 7 % elsewhere.
-    // Before the lean form: M = 2, 3, 6 only (M = 3 0.193 -> 0.173 ms, M = 4 + 7 .. 9 %).  Option iir_dn_t96 = 2: every divisor of 96; 0: never.
-    const bool t96_pays = dec == 2 || dec == 3 || dec == 6 || (96 % dec == 0 && (h->nsec <= 4 || !interleaved || dec % 3 == 0));
-    bool t96 = !dbl && dec > 1 && (((opt().iir_dn_t96 == 1 || opt().iir_dn_t96 == 3) && t96_pays) || (opt().iir_dn_t96 == 2 && 96 % dec == 0));
-    // (the 96-sample kernels have no store but the gathering ones: the lean compact store where a segment's kept outputs fit the image -- from M = 3 on --, ranges of chunks for M = 2)
-    if (t96 && !(interleaved ? par_dec_compact<float, true>(dec, (int64_t)32 * 96, true) || par_dec_rounds<float, true>(dec)
-                             : par_dec_compact<float, false>(dec, (int64_t)64 * 96, true) || par_dec_rounds<float, false>(dec)))
-        t96 = false;
-    // .up by a divisor of 96 from 8 on (the reference default 12): the lean kernels whose state jumps from input sample to input sample (UPJ, chunks of 96 so
-    // that every chunk starts on one).  Measured, same box (profiles/r05/iir_up_lean.txt): rate_change(12).up float32 0.101 -> 0.072 ms per 2^26 outputs; 8-biquad
-    // elliptic by 12 0.113 -> 0.092 per 5e7 (complex64 0.216 -> 0.183); 5 biquads by 8 0.132 -> 0.096 (0.231 -> 0.164).  Option iir_up_jump = 0: never
-    const bool upj = dec <= 1 && up >= 8 && 96 % up == 0 && opt().iir_up_jump >= 1;
-    // .up by 3 (a stage of sigsys.interp24): the lean staging at the input rate (UPS in the kernel), on chunks of 96
-    const bool ups3 = !dbl && dec <= 1 && up == 3 && opt().iir_up_lean;   // (float64: four images of 96 doubles per row and the table leave room for ONE workgroup per CU)
-    t96 = t96 || upj || ups3;
-    if (t96) {
-        ParTables &t9 = p->tab[(dbl ? 6 : 4) + (interleaved ? 1 : 0)];
-        if (t9.T == 0) {
-            const int rc = par_tables(*p, t9, 96, interleaved ? 32 : 64, dbl ? 1e-30L : 1e-18L, par_max_k(dbl), s);
-            if (rc < 0) return rc;
-        }
-        if (t9.K == 0) t96 = false;   // (the filter remembers more segments of this length than the look-back serves: the 128-sample chunks, if they do)
-    }
-    if (t96 && upj) {
-        if (dbl)
-            return interleaved ? launch_par<double, true, 96, true>(h, p, p->tab[7], x, n, 1, 0, 0, y, s, dec, up)
-                               : launch_par<double, false, 96, true>(h, p, p->tab[6], x, n, nrow, x_stride, y_stride, y, s, dec, up);
-        return interleaved ? launch_par<float, true, 96, true>(h, p, p->tab[5], x, n, 1, 0, 0, y, s, dec, up)
-                           : launch_par<float, false, 96, true>(h, p, p->tab[4], x, n, nrow, x_stride, y_stride, y, s, dec, up);
-    }
-    if (t96 && ups3) {
-        ParTables &t3 = p->tab[4 + (interleaved ? 1 : 0)];
-        return interleaved ? launch_par<float, true, 96, false, 3>(h, p, t3, x, n, 1, 0, 0, y, s, dec, up)
-                           : launch_par<float, false, 96, false, 3>(h, p, t3, x, n, nrow, x_stride, y_stride, y, s, dec, up);
-    }
-    if (upj || ups3) t96 = false;
-    ParTables &tb = t96 ? p->tab[4 + (interleaved ? 1 : 0)] : p->tab[(dbl ? 1 : 0) + (interleaved ? 2 : 0)];
-    if (tb.T == 0) {
-        // negligibility as in iir_scan.hip: 1e-30 for float64 signals, 1e-18 for float32 signals (a tenth of an ulp of the
-        // float64 state the dropped term would be added to)
-        const int rc = par_tables(*p, tb, dbl ? SK_PAR_T32 / 2 : SK_PAR_T32, interleaved ? 32 : 64, dbl ? 1e-30L : 1e-18L, par_max_k(dbl), s);
-        if (rc < 0) return rc;
-    }
-    if (tb.K == 0) return 1;
-    // (interleaved signals have no decimating store here but the compact one)
-    if (interleaved && dec > 1 && !(dbl ? par_dec_compact<double, true>(dec, (int64_t)32 * tb.T)
-                                        : (par_dec_compact<float, true>(dec, (int64_t)32 * tb.T) || par_dec_rounds<float, true>(dec)))) return 1;
-    if (t96)
-        return interleaved ? launch_par<float, true, 96>(h, p, tb, x, n, 1, 0, 0, y, s, dec, up)
-                           : launch_par<float, false, 96>(h, p, tb, x, n, nrow, x_stride, y_stride, y, s, dec, up);
-    // .up by 2 / 4 (where the state jump does not pay; with 3 above, the stages of sigsys.interp24): staged at the input rate, the stuffed zeros known to the
-    // compiler (UPS in the kernel).  Measured (profiles/r05/iir_up_lean.txt); option iir_up_lean = 0: the zero-stuffed image as for every other factor
-    if (up == 2 && dec <= 1 && opt().iir_up_lean) {
-        if (interleaved)
-            return dbl ? launch_par<double, true, 0, false, 2>(h, p, tb, x, n, 1, 0, 0, y, s, dec, up)
-                       : launch_par<float, true, 0, false, 2>(h, p, tb, x, n, 1, 0, 0, y, s, dec, up);
-        return dbl ? launch_par<double, false, 0, false, 2>(h, p, tb, x, n, nrow, x_stride, y_stride, y, s, dec, up)
-                   : launch_par<float, false, 0, false, 2>(h, p, tb, x, n, nrow, x_stride, y_stride, y, s, dec, up);
-    }
-    if (up == 4 && dec <= 1 && !dbl && opt().iir_up_lean)   // (a float64 chunk of 64 holds 16 inputs: half a staging piece)
-        return interleaved ? launch_par<float, true, 0, false, 4>(h, p, tb, x, n, 1, 0, 0, y, s, dec, up)
-                           : launch_par<float, false, 0, false, 4>(h, p, tb, x, n, nrow, x_stride, y_stride, y, s, dec, up);
-    if (interleaved)
-        return dbl ? launch_par<double, true>(h, p, tb, x, n, 1, 0, 0, y, s, dec, up) : launch_par<float, true>(h, p, tb, x, n, 1, 0, 0, y, s, dec, up);
-    return dbl ? launch_par<double, false>(h, p, tb, x, n, nrow, x_stride, y_stride, y, s, dec, up)
-               : launch_par<float, false>(h, p, tb, x, n, nrow, x_stride, y_stride, y, s, dec, up);
+    const ParOptions o{opt().iir_dn_t96, opt().iir_up_jump, opt().iir_up_lean, opt().iir_dn_compact, opt().iir_par_v32};
+    const ParChoice c = par_choose(h->nsec, dbl, interleaved != 0, nrow, dec, up, n, o, [&](int slot) { return par_slot_K(*p, slot, s); });
+    if (c.status) return c.status;
+    if (interleaved) return launch_par(h, p, c, dbl, true, x, n, 1, 0, 0, y, s, dec, up);
+    return launch_par(h, p, c, dbl, false, x, n, nrow, x_stride, y_stride, y, s, dec, up);
 }
 
 }  // namespace skdsp

@@ -52,11 +52,11 @@ struct Options {
     int iir_two_pass = 0;     // 1: K1 + carries + K3 even where the single-pass scan applies; -1: single pass wherever it applies
     int iir_par = 1;          // 0: never the parallel-form scan (iir_par.hip); the cascade kernels everywhere
     int iir_par_v32 = 1;      // the parallel form's from-rest end states of float32 / complex64 signals, 7 - 8 biquads, on the float32 matrix instruction: 1 where the
-                              // plan's probe admits the filter (iir_par.hip: par_v32_probe), 2 always (tests, A/B), 0 never
+                              // plan's probe admits the filter (iir_par_plan.hpp: par_v32_probe), 2 always (tests, A/B), 0 never
     int iir_up_jump = 1;      // the parallel-form .up of float32 / complex64 signals by L >= 8, a divisor of 96: lean kernels whose state jumps from input sample to input sample; 0 never (A/B switch)
     int iir_seq = 1;          // cascades of more than 8 sections whose float64 spread the scans would lift past the contract run the reference's recursion (iir_seq.hip): 1 probed, 2 always, 0 never
     int iir_up_lean = 1;      // multirate_IIR.up by 2 staged at the input rate with the stuffed zeros known at compile time (A/B switch; 0: the zero-stuffed image)
-    int iir_dn_t96 = 1;       // the parallel-form .dn of float32 / complex64 signals on 96-sample chunks: 1 where measured to pay (see iir_par_launch), 2 wherever M divides 96, 3 as 1 but M = 2 keeps its gathering in ranges for every cascade, 0 never (A/B switch)
+    int iir_dn_t96 = 1;       // the parallel-form .dn of float32 / complex64 signals on 96-sample chunks: 1 where measured to pay (see par_choose in iir_par_plan.hpp), 2 wherever M divides 96, 3 as 1 but M = 2 keeps its gathering in ranges for every cascade, 0 never (A/B switch)
     int iir_dn_compact = 1;   // 0: the parallel-form .dn keeps the image-and-pick store for every M (A/B switch)
     int fir_up_ols_min = 64;  // multirate_FIR.up: phases of at least this many taps MAY go through the overlap-save walk (the cost model
                               // of fir_up_prefers_ols decides); 0: never; -k: always from k taps per phase on (A/B switch)
@@ -365,7 +365,7 @@ int iir_seq_launch(IirHandle *h, const void *x_dev, int64_t n, int nrow, int64_t
 int iir_par_launch(IirHandle *h, const void *x_dev, int64_t n, int nrow, int64_t x_stride, int64_t y_stride, void *y_dev, hipStream_t s,
                    int dec = 1, int interleaved = 0,    // interleaved = 1: x / y interleaved complex, n complex samples, one row
                    int up = 1);                         // up > 1: x holds n / up samples, the launch filters up * upsample(x, up) (n outputs)
-int iir_par_expand_host(const double *coef, int nsec, double *out, int *accepted);   // host-only (tests): [c0, (a1,a2,r0,r1) x nsec, kappa, ir_err]
+int iir_par_expand_host(const double *coef, int nsec, double *out, int *accepted);   // host-only (tests): [c0, (a1,a2,r0,r1) x nsec, kappa, ir_err, v32_err at 128, at 96]: 5 + 4 nsec doubles
 void iir_par_free(ParPlan *p);
 bool iir_shape_supported(int nsec, int order);
 

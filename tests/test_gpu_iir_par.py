@@ -931,3 +931,43 @@ def test_v32_refuses_a_cancelling_design():
             forced_worst = max(forced_worst, np.max(np.abs(yd.to_host() - ref)) / np.max(np.abs(ref)))
         xd.free(); yd.free()
     assert forced_worst > 6e-7, forced_worst      # (the probe was right to refuse it)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.complex64])
+def test_v32_is_recorded_only_where_a_v32_kernel_runs(dtype):
+    """The .dn kernels that gather behind the recurrence (DECM = 2: M = 2, 3 on 128-sample chunks; DECM = 3: M = 2 on 96-sample chunks, more than
+    4 biquads) have no float32 from-rest form, so for BASELINE config 4's band-pass -- admitted to V32 -- they record `iir_par` alone and give the
+    bytes they give with iir_par_v32 = 0 (the same kernel runs); .dn(x, 4) runs a V32 kernel and says so.  25200 samples: three 8192-sample and
+    four 6144-sample wave segments and a ragged tail.  All inside the float32 contract of 1e-6 of the output peak."""
+    sos = np.load(os.path.join(GOLDEN, "g7_iir_sos.npz"))["sos8"]
+    assert _ffi.sos_par_info(sos)["v32_admitted"] and _ffi.get_option("iir_par_v32") == 1
+    rng = np.random.default_rng(13)
+    x = rng.standard_normal(25200).astype(np.float32)
+    if dtype == np.complex64:
+        x = (x + 1j * rng.standard_normal(25200)).astype(np.complex64)
+    k = _ffi.IirKernel(_ffi.code_of(dtype), sos=sos)
+
+    def dn(M):
+        _ffi.debug_path()
+        y = k.dn(x, M)
+        path = _ffi.debug_path()
+        ref = orc.sos_dn(sos, x, M)
+        err = float(np.max(np.abs(y - ref)) / np.max(np.abs(ref)))
+        print("%s .dn(%d) t96 = %d: %s, error %.2e" % (np.dtype(dtype).name, M, _ffi.get_option("iir_dn_t96"), path, err))
+        return y, path, err
+
+    def no_v32_form(M):
+        y, path, err = dn(M)
+        assert "iir_par" in path and "iir_par_v32" not in path, (M, path)
+        assert err <= TOL32, (M, err)
+        with _ffi.option("iir_par_v32", 0):
+            y0, path0, _ = dn(M)
+        assert path0 == path and y0.tobytes() == y.tobytes(), M
+
+    no_v32_form(2)                       # DECM = 3
+    with _ffi.option("iir_dn_t96", 0):
+        no_v32_form(2)                   # DECM = 2
+        no_v32_form(3)
+    y, path, err = dn(4)                 # DECM = 1 on float32 from-rest states
+    assert "iir_par" in path and "iir_par_v32" in path, path
+    assert err <= TOL32, err

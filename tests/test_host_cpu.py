@@ -168,6 +168,18 @@ def test_iir_design_decisions_host_run(tmp_path):
     assert out.strip().endswith("OK"), out
 
 
+def test_iir_par_plan_decisions_host_run(tmp_path):
+    """Compiles csrc/iir_par_plan.hpp for the HOST (standard headers only) and runs the plan code of the parallel-form IIR scan on inputs
+    whose results the code determines exactly: the partial-fraction expansion and its refusals, the layout and the powers of the scan
+    tables, the look-back depth, the .up jump table, the V32 probe's floor, and par_choose -- which table slot and kernel every kind of
+    call gets."""
+    exe = str(tmp_path / "iir_par_plan_emul")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "scikit-dsp-comm_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "host", "iir_par_plan_emul.cpp"), "-o", exe])
+    out = subprocess.run([exe], stdout=subprocess.PIPE).stdout.decode()
+    assert out.strip().endswith("OK"), out
+
+
 def test_tf2sos_factorisation_matches_reference_tf_outputs():
     """skdsp_tf_create runs (b,a) as biquads (host-only factorisation, no GPU needed): the
     factored cascade, evaluated by the oracle's sosfilt, must reproduce the REFERENCE's
@@ -336,7 +348,7 @@ def test_host_chunk_planner(n, L, M, hist, lg):
             assert ib <= (ob * M) // L and ((oe - 1) * M) // L < ie
 
 
-# ---- parallel-form expansion of the IIR cascade (host side of csrc/iir_par.hip; no GPU) -----------------------------
+# ---- parallel-form expansion of the IIR cascade (csrc/iir_par_plan.hpp, the host side of csrc/iir_par.hip; no GPU) -----------------------------
 def _par_designs():
     from scipy import signal
     sos8 = np.load(os.path.join(GOLDEN, "g7_iir_sos.npz"))["sos8"]

@@ -196,6 +196,73 @@ def iir_cases():
                  z1.tobytes() + z2.tobytes())
 
 
+def resonator_sos(radius=0.997, angle=0.6):
+    """One section whose pole pair decays so slowly that a float32 wave segment (8192 or 6144 samples) is not the whole memory: the look-back
+    depth K of the parallel form is 2 (128-sample chunks) and 3 (96-sample chunks) for float32, 4 and none for complex64, 6 for float64, none for
+    complex128 (tests/host/iir_par_plan_emul.cpp prints them)."""
+    return np.array([[1.0, 0.0, 0.0, 1.0, -2 * radius * np.cos(angle), radius ** 2]])
+
+
+def par_cases():
+    """Every row of par_choose (csrc/iir_par_plan.hpp): designs x dtypes x operations at the defaults, then every option that changes the
+    decision, for the operations it affects.  25200 samples at the rate of the longer side: divisible by every factor, three 8192-sample and
+    four 6144-sample float32 wave segments plus a ragged tail -- look-back, ticket order and tail staging all run."""
+    prng = np.random.default_rng(13)
+    n, dts = 25200, ("f32", "c64", "f64", "c128")
+
+    def pnoise(m, dt):
+        dt = np.dtype(DT[dt])
+        if dt.kind == "c":
+            return ((prng.standard_normal(m) + 1j * prng.standard_normal(m)) / np.sqrt(2)).astype(dt)
+        return prng.standard_normal(m).astype(dt)
+
+    x = {dt: pnoise(3 * n, dt) for dt in dts}
+    sos8 = np.load(os.path.join(ROOT, "tests", "golden", "g7_iir_sos.npz"))["sos8"]
+    designs = [("butter %d" % ns, butter_sos(ns, 0.2)) for ns in (2, 5, 8)] + [("g7 sos8", sos8), ("resonator 0.997", resonator_sos())]
+    DN, UP = (2, 3, 4, 5, 12), (2, 3, 4, 5, 8, 10, 12)
+    refs = {}
+
+    def ref(key, fn):
+        if key not in refs:
+            refs[key] = fn()
+        return refs[key]
+
+    def run(tag, dname, sos, dt, ops, m=n):
+        k = _ffi.IirKernel(_ffi.code_of(x[dt].dtype), sos=sos)
+        xs = x[dt][:m]
+        for op, f in ops:
+            name = "par%s %s %s %s%s" % (tag, dname, dt, op if f is None else "%s(%d)" % (op, f), "" if m == n else " n = %d" % m)
+            if op == "filter":
+                line(name, k.filter(xs), ref((dname, dt, op, m), lambda: orc.sos_filter(sos, wide(xs))))
+            elif op == "dn":
+                line(name, k.dn(xs, f), ref((dname, dt, op, f, m), lambda: orc.sos_dn(sos, wide(xs), f)))
+            elif op == "up":
+                xi = xs[:m // f]
+                line(name, k.up(xi, f), ref((dname, dt, op, f, m), lambda: orc.sos_up(sos, wide(xi), f)))
+            else:
+                x2 = x[dt].reshape(3, n)
+                line(name, k.filter_rows(x2), ref((dname, dt, op), lambda: np.stack([orc.sos_filter(sos, wide(r)) for r in x2])))
+
+    dn_ops, up_ops = [("dn", M) for M in DN], [("up", L) for L in UP]
+    every = [("filter", None)] + dn_ops + up_ops + [("rows", None)]
+    for dname, sos in designs:
+        for dt in dts:
+            run("", dname, sos, dt, every)
+    four = ("f32", "c64")
+    sweeps = [("iir_par_v32", (0, 2), four, [("filter", None)] + dn_ops + [("up", L) for L in (2, 3, 4, 5)] + [("rows", None)], 7),
+              ("iir_dn_t96", (0, 2, 3), four, dn_ops, 1), ("iir_up_jump", (0,), dts, [("up", 8), ("up", 12)], 1),
+              ("iir_up_lean", (0,), dts, [("up", 2), ("up", 3), ("up", 4)], 1), ("iir_dn_compact", (0,), dts, dn_ops, 1)]
+    for option, values, types, ops, min_sections in sweeps:
+        for v in values:
+            with _ffi.option(option, v):
+                for dname, sos in designs:
+                    if len(sos) >= min_sections:
+                        for dt in types:
+                            run(" %s = %d" % (option, v), dname, sos, dt, ops)
+    for dt in dts:   # less than one wave segment
+        run("", "g7 sos8", sos8, dt, [("filter", None), ("dn", 2), ("dn", 3), ("up", 3), ("up", 12)], 5040)
+
+
 def one_call_cases():
     for dt in ("f32", "c64"):
         x = noise(5000, dt)
@@ -242,6 +309,7 @@ _ffi.init(0)
 _ffi.debug_path()
 fir_cases()
 iir_cases()
+par_cases()
 one_call_cases()
 host_pipeline_cases()
 print("lib", os.path.basename(os.environ.get("SKDSP_LIB", "in-tree")), flush=True)
