@@ -564,15 +564,16 @@ __device__ __forceinline__ OlsCareful ols_careful_args(const OlsArgs &A, int ph,
 template <bool REAL, bool DEC, bool UP = false, bool XR = false>   // XR: real signal into the complex tile (see load_tile_xr)
 __global__ __launch_bounds__(256, 2) void ols_tile_kernel(OlsArgs A)
 {
-    __shared__ float4 lds[kLdsUnits + 2 * kT2Units];
+    __shared__ float4 lds[kLdsUnits];
+    __shared__ float4 t2lds[2 * kT2Units];   // T2 and its transpose: an object of their own, so that a table read cannot alias an exchange write
     __shared__ unsigned long long ols_noted;   // poisoned tiles, by walk step (careful.hpp)
     if (threadIdx.x == 0) ols_noted = 0;       // (the barrier behind the table load lies between this and any note)
     // Decimating store (.dn): the last HS of the thread's 16 H registers are fetched per tile (HS x 4 KiB from L2, requested at the top of the
     // tile, used behind the forward transform).  With all 16 held across tiles hipcc spilled four of them and reloaded them from scratch INSIDE
     // the H multiply: four round trips per tile on the critical path.
     constexpr int HS = (DEC && !UP) ? (REAL ? 4 : 5) : 0;   // (the counts that leave no spill)
-    float4 *T2f = lds + kLdsUnits;            // [k2][q]
-    float4 *T2t = lds + kLdsUnits + kT2Units; // [qq][k2] (transposed copy for the inverse)
+    float4 *T2f = t2lds;            // [k2][q]
+    float4 *T2t = t2lds + kT2Units; // [qq][k2] (transposed copy for the inverse)
     const int t = threadIdx.x;
 
     // one-time: LDS twiddle tables and this thread's 15 register twiddles
@@ -731,10 +732,11 @@ __global__ __launch_bounds__(256, 2) void ols_tile_kernel(OlsArgs A)
 template <bool REAL, int MF>
 __global__ __launch_bounds__(256, 2) void ols_fold_kernel(OlsArgs A)
 {
-    __shared__ float4 lds[kLdsUnits + 2 * kT2Units];
+    __shared__ float4 lds[kLdsUnits];
+    __shared__ float4 t2lds[2 * kT2Units];   // T2 and its transpose: an object of their own, so that a table read cannot alias an exchange write
     __shared__ unsigned long long ols_noted;   // poisoned tiles, by walk step (careful.hpp)
     if (threadIdx.x == 0) ols_noted = 0;
-    float4 *T2f = lds + kLdsUnits, *T2t = lds + kLdsUnits + kT2Units;
+    float4 *T2f = t2lds, *T2t = t2lds + kT2Units;
     const int t = threadIdx.x;
     {
         const float4 w = A.T2[t];
@@ -909,10 +911,11 @@ __device__ __forceinline__ void load_rep(const OlsArgs &A, int64_t tile, int t, 
 template <bool REAL, int LF>
 __global__ __launch_bounds__(256, 2) void ols_rep_kernel(OlsArgs A)
 {
-    __shared__ float4 lds[kLdsUnits + 2 * kT2Units];
+    __shared__ float4 lds[kLdsUnits];
+    __shared__ float4 t2lds[2 * kT2Units];   // T2 and its transpose: an object of their own, so that a table read cannot alias an exchange write
     __shared__ unsigned long long ols_noted;   // poisoned tiles, by walk step (careful.hpp)
     if (threadIdx.x == 0) ols_noted = 0;
-    float4 *T2f = lds + kLdsUnits, *T2t = lds + kLdsUnits + kT2Units;
+    float4 *T2f = t2lds, *T2t = t2lds + kT2Units;
     const int t = threadIdx.x;
     {
         const float4 w = A.T2[t];

@@ -48,7 +48,12 @@ constexpr int kN = 8192;
 constexpr int kThreads = 256;
 constexpr int kRowPitch = 272;             // float4 units per k1 row (16 x 17)
 constexpr int kLdsUnits = 16 * kRowPitch;  // 4352 float4 = 69632 B  (exchange image)
-constexpr int kT2Units = 256;              // one 16 x 16 float4 twiddle table = 4 KiB (two copies follow the image)
+constexpr int kT2Units = 256;              // one 16 x 16 float4 twiddle table = 4 KiB (two copies, in an LDS object of their own)
+// How far the T2 reads run ahead of the exchange writes that use them (entries; see lds_req).  The registers set the depth, not the latency: behind
+// the two pass-2 transforms hipcc keeps 8 - 12 VGPRs free, not the 60 that the arrays suggest (every deeper setting spilled H registers: 4, 8, 15
+// ahead -> 4 - 16, 20 - 24, 48 - 52 spilled VGPRs in ols_tile_kernel<false, false>; profiles/r14).
+constexpr int kFwdAhead = 2;   // fwd_pass23: entries in flight ahead of the write loop (the first two ride behind the image reads)
+constexpr int kInvBatch = 2;   // inv_pass32: entries per request (a divisor of 16); 4 spilled 16 VGPRs under the next tile's 64 in flight
 
 // cos/sin(2 pi k / 32), k = 0..31, rounded from float64
 #define SK_C32                                                                                             \
@@ -298,6 +303,49 @@ template <class T, int N, int S, bool INV> struct DftT {
 template <int N, int S, bool INV> using Dft = DftT<cf, N, S, INV>;
 
 // ----------------------------------------------------------------------------
+// LDS requests that stay where they are written.  The inter-pass twiddle tables are LDS objects of their own (fir_ols.hip), so
+// a table read cannot alias an exchange write and hipcc no longer has to keep the two in order (while they were slices of the
+// image's array every T2 entry cost a full LDS round trip between two exchange writes: ds_write, ds_read, s_waitcnt lgkmcnt(0),
+// four v_pk_*, fifteen times over).  How far ahead a read is issued is then said here: a volatile read keeps its place among
+// the other memory operations, so a request written N writes ahead of its use is issued N writes ahead, and LDS answers in
+// order, so the waits hipcc derives for it are counted ones.  hold() -- an empty asm naming the operands of the arithmetic
+// that follows -- keeps that arithmetic behind a burst of requests (the pruned passes, which have the registers for a burst).
+// Host build: plain reads, nothing to hold.
+// ----------------------------------------------------------------------------
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef float v4f __attribute__((ext_vector_type(4)));
+// (the LDS address space is spelled out: a volatile access through a generic pointer stays a flat_load, whatever the pointer is known to be.
+// The cast keeps the low 32 bits of the pointer: lds_req / lds_req_lo are for pointers into __shared__ objects ONLY -- handed a table in global
+// memory they would read whatever LDS holds at that offset, silently.  The same holds for every pass below that takes a table and reads it
+// through them: fwd_pass23, inv_pass32, inv_pass32_fold, inv_pass1_fold (the image), fwd_pass23_rep.)
+#define SK_LDS_PTR(T, p) ((const volatile __attribute__((address_space(3))) T *)(p))
+SK_HD float4 lds_req(const float4 *p)
+{
+    const v4f r = *SK_LDS_PTR(v4f, p);
+    return make_float4(r.x, r.y, r.z, r.w);
+}
+// the first half of a float4 unit (column e = 0)
+SK_HD cf lds_req_lo(const float4 *p) { return C(*SK_LDS_PTR(v2f, p)); }
+template <int N> SK_HD void hold(cf *v)
+{
+    if constexpr (N % 4 == 0) {
+        SK_UNROLL
+        for (int i = 0; i < N; i += 4)
+            asm volatile("" : "+v"(v[i].x), "+v"(v[i].y), "+v"(v[i + 1].x), "+v"(v[i + 1].y), "+v"(v[i + 2].x), "+v"(v[i + 2].y), "+v"(v[i + 3].x), "+v"(v[i + 3].y));
+    } else {
+        SK_UNROLL
+        for (int i = 0; i < N; ++i) asm volatile("" : "+v"(v[i].x), "+v"(v[i].y));
+    }
+}
+SK_HD void hold(cf &a, cf &b, cf &c, cf &d) { asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(b.x), "+v"(b.y), "+v"(c.x), "+v"(c.y), "+v"(d.x), "+v"(d.y)); }
+#else
+SK_HD float4 lds_req(const float4 *p) { return *p; }
+SK_HD cf lds_req_lo(const float4 *p) { return make_float2(p->x, p->y); }
+template <int N> SK_HD void hold(cf *) {}
+SK_HD void hold(cf &, cf &, cf &, cf &) {}
+#endif
+
+// ----------------------------------------------------------------------------
 // LDS addressing (float4 units)
 // ----------------------------------------------------------------------------
 SK_HD int lds_unit(int row_k1, int mid, int q) { return row_k1 * kRowPitch + mid * 17 + q; }
@@ -365,7 +413,7 @@ SK_HD void fwd_pass1_real(int t, const cf *v, const cf *tw, float4 *lds)
 
 // exchange-1 read + pass 2 + twiddle + exchange-2 write/read + pass 3.
 // thread t = 16 k1 + q for pass 2 and t = 16 k1 + k2 for pass 3.  Z[k3] out (32).
-SK_HD void fwd_pass23(int t, const float4 *T2 /* LDS copy [k2][q] */, float4 *lds, cf *Z)
+SK_HD void fwd_pass23(int t, const float4 *T2 /* LDS copy [k2][q]; device build: MUST point into LDS (lds_req) */, float4 *lds, cf *Z)
 {
     const int k1 = t >> 4, q = t & 15;
     cf in0[16], in1[16], o0[16], o1[16];
@@ -375,13 +423,18 @@ SK_HD void fwd_pass23(int t, const float4 *T2 /* LDS copy [k2][q] */, float4 *ld
         in0[b] = lo(f);
         in1[b] = hi(f);
     }
+    // T2 of exchange 2, kFwdAhead entries ahead: the first ones are requested behind the image reads and are in flight under both transforms,
+    // every later one kFwdAhead writes ahead of its products, so that no write waits for the read in front of it
+    float4 w[16];
+    SK_UNROLL
+    for (int k2 = 1; k2 <= kFwdAhead; ++k2) w[k2] = lds_req(T2 + k2 * 16 + q);
     Dft<16, 1, false>::run(in0, o0);
     Dft<16, 1, false>::run(in1, o1);
     lds[lds_unit(k1, 0, q)] = pack(o0[0], o1[0]);
     SK_UNROLL
     for (int k2 = 1; k2 < 16; ++k2) {
-        const float4 w = T2[k2 * 16 + q];
-        lds[lds_unit(k1, k2, q)] = pack(cmul(o0[k2], lo(w)), cmul(o1[k2], hi(w)));
+        if (k2 + kFwdAhead < 16) w[k2 + kFwdAhead] = lds_req(T2 + (k2 + kFwdAhead) * 16 + q);
+        lds[lds_unit(k1, k2, q)] = pack(cmul(o0[k2], lo(w[k2])), cmul(o1[k2], hi(w[k2])));
     }
     // (wave-local: the 16 lanes of this k1 row only read what they wrote)
     const int k2 = q;
@@ -412,15 +465,24 @@ SK_HD void mul_H(const float4 *hh, cf *Z)
 }
 
 // inverse pass 3 + conj twiddle + exchange-2' + inverse pass 2 + exchange-1' write.
-SK_HD void inv_pass32(int t, const float4 *T2t /* LDS copy, transposed [qq][k2] */, float4 *lds, const cf *Z)
+SK_HD void inv_pass32(int t, const float4 *T2t /* LDS copy, transposed [qq][k2]; device build: MUST point into LDS (lds_req) */, float4 *lds, const cf *Z)
 {
     const int k1 = t >> 4, k2 = t & 15;
+    // T2t in batches of kInvBatch entries, one batch ahead: the first behind the transform (the next tile's 64 registers are in flight here and the
+    // transform leaves no room beside them), every later one ahead of the products and writes of the batch before it
     cf z[32];
     Dft<32, 1, true>::run(Z, z);
+    float4 w[16];
     SK_UNROLL
-    for (int qq = 0; qq < 16; ++qq) {
-        const float4 w = T2t[qq * 16 + k2];
-        lds[lds_unit(k1, k2, qq)] = pack(cmulc(z[2 * qq], lo(w)), cmulc(z[2 * qq + 1], hi(w)));
+    for (int j = 0; j < kInvBatch; ++j) w[j] = lds_req(T2t + j * 16 + k2);
+    SK_UNROLL
+    for (int g = 0; g < 16; g += kInvBatch) {
+        if (g + kInvBatch < 16) {
+            SK_UNROLL
+            for (int j = g + kInvBatch; j < g + 2 * kInvBatch; ++j) w[j] = lds_req(T2t + j * 16 + k2);
+        }
+        SK_UNROLL
+        for (int qq = g; qq < g + kInvBatch; ++qq) lds[lds_unit(k1, k2, qq)] = pack(cmulc(z[2 * qq], lo(w[qq])), cmulc(z[2 * qq + 1], hi(w[qq])));
     }
     const int q = k2;  // now thread (k1,q)
     cf in0[16], in1[16], o0[16], o1[16];
@@ -441,16 +503,17 @@ SK_HD void inv_pass1(int t, const cf *tw, const float4 *lds, cf *v)
 {
     const int b = t >> 4, q = t & 15;
     cf in0[16], in1[16], o0[16], o1[16];
-    {
-        const float4 f = lds[lds_unit(0, b, q)];
-        in0[0] = lo(f);
-        in1[0] = hi(f);
-    }
+    // the sixteen image reads written as one burst in front of the products: hipcc then issues them as one and consumes them under counted waits
+    // (lgkmcnt(14) ... (0)); written read by read between the products they came out in pairs, each pair behind a wait for everything
+    float4 f[16];
+    SK_UNROLL
+    for (int k1 = 0; k1 < 16; ++k1) f[k1] = lds[lds_unit(k1, b, q)];
+    in0[0] = lo(f[0]);
+    in1[0] = hi(f[0]);
     static_for<1, 16>([&](auto kc) {
         constexpr int k1 = decltype(kc)::value;
-        const float4 f = lds[lds_unit(k1, b, q)];
-        in0[k1] = cmulc(lo(f), tw[k1]);
-        in1[k1] = mul_w8192<k1, true>(cmulc(hi(f), tw[k1]));
+        in0[k1] = cmulc(lo(f[k1]), tw[k1]);
+        in1[k1] = mul_w8192<k1, true>(cmulc(hi(f[k1]), tw[k1]));
     });
     Dft<16, 1, true>::run(in0, o0);
     Dft<16, 1, true>::run(in1, o1);
@@ -469,7 +532,7 @@ SK_HD void inv_pass1(int t, const cf *tw, const float4 *lds, cf *v)
 // with e = 0 and q a multiple of MF / 2, i.e. ONE 16-point transform per lane and pass where the full inverse runs two, on every
 // (MF / 2)-th lane.  Forward transform, H product, loads: untouched.  Per tile: 1 forward + ~1/4 inverse transform instead of 2.
 // ----------------------------------------------------------------------------
-template <int MF> SK_HD void inv_pass32_fold(int t, const float4 *T2t /* LDS copy, transposed [qq][k2] */, float4 *lds, const cf *Z)
+template <int MF> SK_HD void inv_pass32_fold(int t, const float4 *T2t /* LDS copy, transposed [qq][k2]; device build: MUST point into LDS (lds_req) */, float4 *lds, const cf *Z)
 {
     constexpr int R = 32 / MF, LS = MF / 2;   // points of the folded transform; lane step of the columns in use
     const int k1 = t >> 4, k2 = t & 15;
@@ -481,13 +544,14 @@ template <int MF> SK_HD void inv_pass32_fold(int t, const float4 *T2t /* LDS cop
         for (int m = 1; m < MF; ++m) acc = cadd(acc, Z[k + R * m]);
         F[k] = acc;
     }
+    cf w[R];   // (the R entries of T2t in use, 8 bytes each: all requested ahead of the folded transform)
+    SK_UNROLL
+    for (int cp = 0; cp < R; ++cp) w[cp] = lds_req_lo(T2t + cp * LS * 16 + k2);
+    hold<R>(F);
     Dft<R, 1, true>::run(F, z);   // z[c'] = the full inverse DFT32 at c = c' MF
     cf *l2 = reinterpret_cast<cf *>(lds);   // (the first half of a float4 unit: column e = 0)
     SK_UNROLL
-    for (int cp = 0; cp < R; ++cp) {
-        const int qq = cp * LS;
-        l2[2 * lds_unit(k1, k2, qq)] = cmulc(z[cp], lo(T2t[qq * 16 + k2]));
-    }
+    for (int cp = 0; cp < R; ++cp) l2[2 * lds_unit(k1, k2, cp * LS)] = cmulc(z[cp], w[cp]);
     const int q = k2;  // now thread (k1, q): its column exists where LS divides q
     if (q % LS == 0) {
         cf in0[16], o0[16];
@@ -505,12 +569,18 @@ template <int MF> SK_HD void inv_pass1_fold(int t, const cf *tw, const float4 *l
     constexpr int LS = MF / 2;
     const int b = t >> 4, q = t & 15;
     if (q % LS != 0) return;
-    const cf *l2 = reinterpret_cast<const cf *>(lds);
-    cf in0[16];
-    in0[0] = l2[2 * lds_unit(0, b, q)];
+    cf in0[16], f[16];   // (one read burst, as in inv_pass1)
+    SK_UNROLL
+    for (int c = 0; c < 4; ++c) {
+        SK_UNROLL
+        for (int k1 = c; k1 < 16; k1 += 4) f[k1] = lds_req_lo(lds + lds_unit(k1, b, q));
+    }
+    SK_UNROLL
+    for (int c = 0; c < 4; ++c) hold(f[c], f[c + 4], f[c + 8], f[c + 12]);
+    in0[0] = f[0];
     static_for<1, 16>([&](auto kc) {
         constexpr int k1 = decltype(kc)::value;
-        in0[k1] = cmulc(l2[2 * lds_unit(k1, b, q)], tw[k1]);
+        in0[k1] = cmulc(f[k1], tw[k1]);
     });
     Dft<16, 1, true>::run(in0, v);
 }
@@ -538,7 +608,7 @@ template <int LF> SK_HD void fwd_pass1_rep(int t, const cf *in, const cf *tw, fl
     });
 }
 // exchange-1 read + pass 2 + twiddle + exchange-2 + the R-point pass 3, replicated.  Z[k3] out (32).
-template <int LF> SK_HD void fwd_pass23_rep(int t, const float4 *T2 /* LDS copy [k2][q] */, float4 *lds, cf *Z)
+template <int LF> SK_HD void fwd_pass23_rep(int t, const float4 *T2 /* LDS copy [k2][q]; device build: MUST point into LDS (lds_req) */, float4 *lds, cf *Z)
 {
     constexpr int R = 32 / LF, LS = LF / 2;
     const int k1 = t >> 4, q = t & 15;
@@ -547,10 +617,14 @@ template <int LF> SK_HD void fwd_pass23_rep(int t, const float4 *T2 /* LDS copy 
         cf in0[16], o0[16];
         SK_UNROLL
         for (int b = 0; b < 16; ++b) in0[b] = l2[2 * lds_unit(k1, b, q)];
+        cf w[16];   // (column e = 0 of the fifteen T2 entries, in flight under the transform: see fwd_pass23)
+        SK_UNROLL
+        for (int k2 = 1; k2 < 16; ++k2) w[k2] = lds_req_lo(T2 + k2 * 16 + q);
+        hold<16>(in0);
         Dft<16, 1, false>::run(in0, o0);
         l2[2 * lds_unit(k1, 0, q)] = o0[0];
         SK_UNROLL
-        for (int k2 = 1; k2 < 16; ++k2) l2[2 * lds_unit(k1, k2, q)] = cmul(o0[k2], lo(T2[k2 * 16 + q]));
+        for (int k2 = 1; k2 < 16; ++k2) l2[2 * lds_unit(k1, k2, q)] = cmul(o0[k2], w[k2]);
     }
     // (wave-local: the 16 lanes of this k1 row only read what they wrote)
     const int k2 = q;

@@ -1,5 +1,5 @@
 """Time the overlap-save kernels that share load_tile (csrc/fir_ols.hip) under the values of the option ols_keep_overlap, as bench.py makes the workloads
-(1024 taps, complex64, 2^26 samples at the high rate): fir1024 (.filter), firdn4 (.dn(x, 4)), firup4 (.up(x, 4)).
+(1024 taps, complex64, 2^26 samples at the high rate): fir1024 (.filter), firdn4 (.dn(x, 4)), firup4 (.up(x, 4)); with --only also fir1024f32 (.filter, float32).
     python tools/time_ols_loads.py [--reps 1] [--only fir1024,firdn4] v1 v2 ...
 One line per (workload, value, rep); SKDSP_LIB selects another build of the library, so that a shell loop can alternate two builds on one box."""
 import os, sys, time
@@ -23,6 +23,10 @@ if "fir1024" in only:
     k = _ffi.FirKernel(bench.firwin_lowpass(1024, 0.2), _ffi.C64)
     xd = _ffi.DeviceArray(n, np.complex64, headroom=1024).fill_noise(1); yd = _ffi.DeviceArray(n, np.complex64)
     work["fir1024"] = (lambda k=k, xd=xd, yd=yd: k.filter_dev(xd, yd))
+if "fir1024f32" in only:
+    kf = _ffi.FirKernel(bench.firwin_lowpass(1024, 0.2), _ffi.F32)
+    xf = _ffi.DeviceArray(n, np.float32, headroom=1024).fill_noise(1); yf = _ffi.DeviceArray(n, np.float32)
+    work["fir1024f32"] = (lambda: kf.filter_dev(xf, yf))
 if "firdn4" in only:
     k4 = _ffi.FirKernel(bench.firwin_lowpass(1024, 0.2 / 4), _ffi.C64)
     xd4 = _ffi.DeviceArray(n, np.complex64, headroom=1024).fill_noise(1); yd4 = _ffi.DeviceArray(n // 4, np.complex64)
