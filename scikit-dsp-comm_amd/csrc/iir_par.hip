@@ -1094,7 +1094,7 @@ struct ParTables {
     double *lvl_dev = nullptr;
     double *psi_dev = nullptr;
     int v32 = 0;                 // V = G x in float32 for chunks of this length (par_v32_probe): 0 not probed, 1 admitted, -1 refused
-    double v32_err = 0.0;        // ... the worst probe error it showed
+    double v32_err = 0.0;        // ... the worst probe error it showed (a refusal: the first one above the limit)
 };
 
 struct ParPlan {
@@ -1205,7 +1205,7 @@ template <int N, typename IO, int DECM, bool CPLX, int TT, bool UPJ, int UPS, bo
                              : DECM == 3 ? (io4 && !UPJ && UPS == 0 && TT == 96 && N > 4)
                              : DECM == 1 ? (!UPJ && UPS == 0)
                                          : (UPJ || UPS != 0 || TT == 0);
-    constexpr bool v32 = !V32 || (N >= 7 && io4 && DECM <= 1 && !UPJ);
+    constexpr bool v32 = !V32 || (N >= 7 && io4 && DECM == 0 && !UPJ);   // (.dn keeps the float64 from-rest states: par_choose)
     return family && variant && v32;
 }
 
@@ -1292,7 +1292,7 @@ static int launch_par(IirHandle *h, ParPlan *p, const ParChoice &c, bool dbl, bo
     bool v32 = false;
     if (c.v32_wanted) {
         if (tb.v32 == 0) {
-            tb.v32_err = par_v32_probe(p->e, T);
+            tb.v32_err = par_v32_probe(p->e, T, kParV32Limit);
             tb.v32 = tb.v32_err <= kParV32Limit ? 1 : -1;
         }
         v32 = tb.v32 == 1 || opt().iir_par_v32 >= 2;

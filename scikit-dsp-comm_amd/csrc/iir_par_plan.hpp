@@ -135,110 +135,175 @@ inline bool par_expand(const double *coef, int nsec, ParExpansion &P)
 
 // V32 (see the kernel): may the from-rest end states of T-sample chunks of THIS filter be formed in float32?  The error such a state carries reaches the
 // outputs of the next chunks through the output taps, amplified by whatever cancels between the branches -- no norm of the expansion predicts it (an
-// elliptic band-pass with a cancellation factor of 2.8 shows 1.6e-6, one with 3.7 shows 4e-7), so it is MEASURED: the float32 chain of the matrix
-// instruction (acc = fmaf(G[t], x[t], acc), oldest sample first, G rounded to float32 -- bit for bit what v_mfma_f32_16x16x4_f32 computes) against the
-// exact from-rest state, on the inputs that are worst for it -- coherent ones: DC, the Nyquist alternation, a tone on every section's resonance -- and on
-// noise; the state errors are carried from chunk to chunk by the exact transition and through the output taps sample by sample.  Returned: the worst
-// output error over the probes, relative to the probe's output peak (or, for stop-band probes, 1 % of the forward bound -- the same floor the tests use).
-inline double par_v32_probe(const ParExpansion &P, int T)
+// elliptic band-pass with a cancellation factor of 2.8 shows 1.6e-6, one with 3.7 shows 4e-7), so it is MEASURED by a model of the kernel: the float32
+// chain of the matrix instruction (acc = fmaf(G[t], x[t], acc), oldest sample first, G rounded to float32 -- bit for bit what v_mfma_f32_16x16x4_f32
+// computes) against the exact from-rest state; the state errors are carried from chunk to chunk by the exact transition and through the output taps
+// sample by sample.  par_v32_input_error is the model on one input, par_v32_probe the admission test: the model on a fixed set of inputs.
+
+// the table G of T-sample chunks as the float32 kernel holds it (g32) and unrounded (gd): rows 2k, 2k + 1 are g[T-1-t], g[T-2-t], g = impulse response of 1 / A_k
+struct ParV32G {
+    int T = 0;
+    std::vector<float> g32;
+    std::vector<double> gd;
+};
+inline ParV32G par_v32_g(const ParExpansion &P, int T)
 {
-    const int N = P.nsec, NCH = 24, n = NCH * T;
-    std::vector<float> g32((size_t)2 * N * T);
-    std::vector<double> gd((size_t)2 * N * T);
+    const int N = P.nsec;
+    ParV32G G;
+    G.T = T;
+    G.g32.resize((size_t)2 * N * T);
+    G.gd.resize((size_t)2 * N * T);
     for (int k = 0; k < N; ++k) {
         long double g0 = 1.0L, g1 = 0.0L;
         for (int t = T - 1; t >= 0; --t) {
-            gd[((size_t)2 * k) * T + t] = (double)g0;
-            gd[((size_t)2 * k + 1) * T + t] = (double)g1;
-            g32[((size_t)2 * k) * T + t] = (float)(double)g0;
-            g32[((size_t)2 * k + 1) * T + t] = (float)(double)g1;
+            G.gd[((size_t)2 * k) * T + t] = (double)g0;
+            G.gd[((size_t)2 * k + 1) * T + t] = (double)g1;
+            G.g32[((size_t)2 * k) * T + t] = (float)(double)g0;
+            G.g32[((size_t)2 * k + 1) * T + t] = (float)(double)g1;
             const long double g2 = -P.a1[k] * g0 - P.a2[k] * g1;
             g1 = g0;
             g0 = g2;
         }
     }
-    std::vector<std::vector<float>> probes;
+    return G;
+}
+
+// The model on ONE input: x holds nch chunks of G.T samples.  Returned: the worst output error the float32 from-rest states cause on it, over the scale
+// (the input's exact output peak, or 1 % of the forward bound); infinity where there is nothing to scale by.  State errors only: the recurrence and the
+// output rounding of the kernel are not in it.
+inline double par_v32_input_error(const ParExpansion &P, const ParV32G &G, const float *x, int nch)
+{
+    const int N = P.nsec, T = G.T, n = nch * T;
+    // the exact output (the parallel form in double, straight through) for the scale; the error by linearity: the state errors alone, carried exactly
+    double ymax = 0.0, xmax = 0.0;
     {
-        std::vector<float> x((size_t)n);
-        unsigned long long lcg = 0x2545F4914F6CDD1Dull;
+        std::vector<double> w1((size_t)N, 0.0), w2((size_t)N, 0.0);
         for (int i = 0; i < n; ++i) {
-            double a = 0.0;
-            for (int q = 0; q < 4; ++q) {
-                lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
-                a += (double)(lcg >> 11) / 9007199254740992.0 - 0.5;
+            double yv = P.gamma * (double)x[i];
+            for (int k = 0; k < N; ++k) {
+                yv += P.al[k] * w1[k] + P.be[k] * w2[k];
+                const double w0 = (double)x[i] + P.na1[k] * w1[k] + P.na2[k] * w2[k];
+                w2[k] = w1[k];
+                w1[k] = w0;
             }
-            x[i] = (float)(a * 1.7320508075688772);
-        }
-        probes.push_back(x);
-        for (int i = 0; i < n; ++i) x[i] = 1.0f;
-        probes.push_back(x);
-        for (int i = 0; i < n; ++i) x[i] = (i & 1) ? -1.0f : 1.0f;
-        probes.push_back(x);
-        for (int k = 0; k < N; ++k) {
-            const double a1 = (double)P.a1[k], a2 = (double)P.a2[k];
-            if (!(a2 > 0.0) || a1 * a1 >= 4.0 * a2) continue;   // (real poles: DC / Nyquist cover them)
-            const double th = std::acos(std::max(-1.0, std::min(1.0, -a1 / (2.0 * std::sqrt(a2)))));
-            for (int i = 0; i < n; ++i) x[i] = (float)std::cos(th * i);
-            probes.push_back(x);
+            ymax = std::max(ymax, std::fabs(yv));
+            xmax = std::max(xmax, (double)std::fabs(x[i]));
         }
     }
-    double worst = 0.0;
-    for (const auto &x : probes) {
-        // the exact output (the parallel form in double, straight through) for the scale; the error by linearity: the state errors alone, carried exactly
-        double ymax = 0.0, xmax = 0.0;
-        {
-            std::vector<double> w1((size_t)N, 0.0), w2((size_t)N, 0.0);
-            for (int i = 0; i < n; ++i) {
-                double yv = P.gamma * (double)x[i];
-                for (int k = 0; k < N; ++k) {
-                    yv += P.al[k] * w1[k] + P.be[k] * w2[k];
-                    const double w0 = (double)x[i] + P.na1[k] * w1[k] + P.na2[k] * w2[k];
-                    w2[k] = w1[k];
-                    w1[k] = w0;
-                }
-                ymax = std::max(ymax, std::fabs(yv));
-                xmax = std::max(xmax, (double)std::fabs(x[i]));
-            }
-        }
-        std::vector<double> e1((size_t)N, 0.0), e2((size_t)N, 0.0);   // error of (w[n-1], w[n-2]) at the start of the current chunk
-        double emax = 0.0;
-        for (int j = 0; j < NCH; ++j) {
-            // outputs of chunk j see the start-state error through the taps; the error state runs the homogeneous recurrence
-            std::vector<double> f1 = e1, f2 = e2;
-            for (int t = 0; t < T; ++t) {
-                double ev = 0.0;
-                for (int k = 0; k < N; ++k) {
-                    ev += P.al[k] * f1[k] + P.be[k] * f2[k];
-                    const double f0 = P.na1[k] * f1[k] + P.na2[k] * f2[k];
-                    f2[k] = f1[k];
-                    f1[k] = f0;
-                }
-                emax = std::max(emax, std::fabs(ev));
-            }
-            // this chunk's from-rest end state: the float32 chain against the double sum of the same products with the unrounded G
+    std::vector<double> e1((size_t)N, 0.0), e2((size_t)N, 0.0);   // error of (w[n-1], w[n-2]) at the start of the current chunk
+    double emax = 0.0;
+    for (int j = 0; j < nch; ++j) {
+        // outputs of chunk j see the start-state error through the taps; the error state runs the homogeneous recurrence
+        std::vector<double> f1 = e1, f2 = e2;
+        for (int t = 0; t < T; ++t) {
+            double ev = 0.0;
             for (int k = 0; k < N; ++k) {
-                for (int c = 0; c < 2; ++c) {
-                    const float *gf = g32.data() + ((size_t)2 * k + c) * T;
-                    const double *ge = gd.data() + ((size_t)2 * k + c) * T;
-                    float acc = 0.0f;
-                    long double ex = 0.0L;
-                    for (int t = 0; t < T; ++t) {
-                        acc = std::fmaf(gf[t], x[(size_t)j * T + t], acc);
-                        ex += (long double)ge[t] * (long double)x[(size_t)j * T + t];
-                    }
-                    (c == 0 ? f1[k] : f2[k]) += (double)acc - (double)ex;   // e_(j+1) = Phi e_j + delta_j (f holds Phi e_j now)
-                }
+                ev += P.al[k] * f1[k] + P.be[k] * f2[k];
+                const double f0 = P.na1[k] * f1[k] + P.na2[k] * f2[k];
+                f2[k] = f1[k];
+                f1[k] = f0;
             }
-            e1 = f1;
-            e2 = f2;
+            emax = std::max(emax, std::fabs(ev));
         }
-        const double scale = std::max(ymax, 1e-2 * P.l1h * xmax);
-        if (!(scale > 0.0) || !std::isfinite(emax)) return 1.0;
-        worst = std::max(worst, emax / scale);
+        // this chunk's from-rest end state: the float32 chain against the double sum of the same products with the unrounded G
+        for (int k = 0; k < N; ++k) {
+            for (int c = 0; c < 2; ++c) {
+                const float *gf = G.g32.data() + ((size_t)2 * k + c) * T;
+                const double *ge = G.gd.data() + ((size_t)2 * k + c) * T;
+                float acc = 0.0f;
+                long double ex = 0.0L;
+                for (int t = 0; t < T; ++t) {
+                    acc = std::fmaf(gf[t], x[(size_t)j * T + t], acc);
+                    ex += (long double)ge[t] * (long double)x[(size_t)j * T + t];
+                }
+                (c == 0 ? f1[k] : f2[k]) += (double)acc - (double)ex;   // e_(j+1) = Phi e_j + delta_j (f holds Phi e_j now)
+            }
+        }
+        e1 = f1;
+        e2 = f2;
+    }
+    const double scale = std::max(ymax, 1e-2 * P.l1h * xmax);
+    if (!(scale > 0.0) || !std::isfinite(emax)) return HUGE_VAL;
+    return emax / scale;
+}
+inline double par_v32_input_error(const ParExpansion &P, int T, const float *x, int nch) { return par_v32_input_error(P, par_v32_g(P, T), x, nch); }
+
+// the resonance angle of section k (complex poles), or a negative value: real poles -- DC / Nyquist cover them
+inline double par_resonance(const ParExpansion &P, int k)
+{
+    const double a1 = (double)P.a1[k], a2 = (double)P.a2[k];
+    if (!(a2 > 0.0) || a1 * a1 >= 4.0 * a2) return -1.0;
+    return std::acos(std::max(-1.0, std::min(1.0, -a1 / (2.0 * std::sqrt(a2)))));
+}
+
+// the probe's noise: sums of four uniform draws of a fixed generator, unit variance
+inline void par_v32_noise(float *x, int n)
+{
+    unsigned long long lcg = 0x2545F4914F6CDD1Dull;
+    for (int i = 0; i < n; ++i) {
+        double a = 0.0;
+        for (int q = 0; q < 4; ++q) {
+            lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
+            a += (double)(lcg >> 11) / 9007199254740992.0 - 0.5;
+        }
+        x[i] = (float)(a * 1.7320508075688772);
+    }
+}
+
+// The admission test: the worst model error over noise, DC, the Nyquist alternation and, for every section with complex poles, tones ON its resonance
+// (cosine and sine phase) and DETUNED from it by +- 0.005, 0.015 and 0.03 rad / sample, 96 chunks each.  The detuned tones are the ones that decide: just
+// outside a band edge the states of the edge sections are still as large as on the resonance while the output -- the scale -- has fallen to a fraction,
+// and a tone that is not periodic in the chunk length meets every phase of the chunk grid, which takes some tens of chunks (measured, model and GPU,
+// BASELINE config 4 shows 4.0e-7 on its resonances over 24 chunks, 1.33e-6 at 0.009 rad above its upper edge resonance over 96
+// and 1.37e-6 over 512; the GPU 1.46e-6).  Over a 0.001 rad grid of +- 0.03 around every resonance, square waves, combs and zero-stuffed tones the model
+// stays within 1.5 times this probe's value for every cascade the probe admits (tests/host/iir_par_v32_emul.cpp holds it to that).
+// Returned: the worst error over scale; 1.0 where an input has nothing to scale by.  stop_above: the inputs after the first one that shows more than this
+// are not run (the launch passes kParV32Limit: a refusal needs no more than one such input, and the whole set costs 0.1 - 0.2 s for 8 biquads).
+constexpr int kParV32ProbeChunks = 96;
+constexpr double kParV32Detune[3] = {0.005, 0.015, 0.03};
+inline double par_v32_probe(const ParExpansion &P, int T, double stop_above = HUGE_VAL)
+{
+    const int N = P.nsec, NCH = kParV32ProbeChunks, n = NCH * T;
+    const ParV32G G = par_v32_g(P, T);
+    std::vector<float> x((size_t)n);
+    double worst = 0.0;
+    auto run = [&]() {
+        const double e = par_v32_input_error(P, G, x.data(), NCH);
+        worst = std::max(worst, e);
+        return std::isfinite(e);
+    };
+    auto done = [&]() { return worst > stop_above; };
+    auto tone = [&](double w) {
+        for (int i = 0; i < n; ++i) x[i] = (float)std::cos(w * i);
+        return run();
+    };
+    par_v32_noise(x.data(), n);
+    if (!run()) return 1.0;
+    for (int i = 0; i < n; ++i) x[i] = 1.0f;
+    if (!run()) return 1.0;
+    for (int i = 0; i < n; ++i) x[i] = (i & 1) ? -1.0f : 1.0f;
+    if (!run()) return 1.0;
+    // (the sections with the sharpest poles first: where a filter is refused, it is mostly next to those)
+    int order[8] = {0, 1, 2, 3, 4, 5, 6, 7};
+    std::stable_sort(order, order + N, [&](int a, int b) { return P.a2[a] > P.a2[b]; });
+    for (int ko = 0; ko < N && !done(); ++ko) {
+        const int k = order[ko];
+        const double th = par_resonance(P, k);
+        if (th < 0.0) continue;
+        if (!tone(th)) return 1.0;
+        for (int i = 0; i < n; ++i) x[i] = (float)std::sin(th * i);
+        if (!run()) return 1.0;
+        for (double d : kParV32Detune)
+            for (double w : {th - d, th + d})
+                if (w > 0.0 && w < 3.141592653589793 && !done() && !tone(w)) return 1.0;
     }
     return worst;
 }
 constexpr double kParV32Limit = 5e-7;   // of the 1e-6 the float32 contract allows: the rest stays with the recurrence, the output rounding and the inputs no probe covers
+// ... of which the kernel with float64 from-rest states (recurrence, output rounding) takes this much: the largest error tests/test_gpu_iir_v32.py records
+// with iir_par_v32 = 0 on its designs' resonance and worst detuned tones (MI355X, 49152 samples, 15 cascades the parallel form serves, float32 and complex64,
+// .filter / .dn / .up: 5.0e-8 ... 6.7e-8), rounded up.  tests/host/iir_par_v32_emul.cpp holds the model to 1e-6 minus this.
+constexpr double kParV32Rest = 1e-7;
 
 struct M2 { long double m[4]; };
 inline M2 m2mul(const M2 &x, const M2 &y)
@@ -447,9 +512,11 @@ inline ParChoice par_choose(int nsec, bool dbl, bool interleaved, int nrow, int 
     c.dec_compact = adec > 1 && par_dec_compact(eb, interleaved, adec, S, c.TT == 96, big_m2 ? kParPlanStageM2 : 0, o.iir_dn_compact);
     c.dec_rounds = !c.dec_compact && par_dec_rounds(eb, adec, o.iir_dn_compact) ? 2 : 1;
     c.DECM = adec <= 1 ? 0 : c.dec_rounds > 1 ? 2 : (big_m2 && c.dec_compact) ? 3 : 1;
-    // V32 (see the kernel): float32 / complex64 signals through 7 - 8 biquads; the DECM = 2, 3 kernels have no such form
+    // V32 (see the kernel): float32 / complex64 signals through 7 - 8 biquads, .filter and .up.  Not .dn: the contract is relative to the peak of the outputs a call
+    // KEEPS, and every M-th sample of a tone can peak far below the tone -- the probe's scale is the full-rate peak, and a state error it admits at 4.4e-7 of that
+    // measured 1.6e-6 of the kept outputs' peak (an 8-band equaliser, sine on its lowest resonance, .dn(x, 5)); the float64 states (6e-8) have the room for that
     // (not for .up by 8 or more through the general kernel: its from-rest states are formed per lane on the vector ALU from the FLOAT64 table -- `sparse` in the kernel)
-    c.v32_wanted = eb == 4 && !c.UPJ && nsec >= 7 && o.iir_par_v32 > 0 && !(c.UPS == 0 && dec <= 1 && up >= 8) && c.DECM < 2;
+    c.v32_wanted = eb == 4 && !c.UPJ && nsec >= 7 && o.iir_par_v32 > 0 && !(c.UPS == 0 && up >= 8) && dec <= 1;
     c.status = 0;
     return c;
 }

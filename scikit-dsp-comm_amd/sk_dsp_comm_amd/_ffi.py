@@ -701,7 +701,9 @@ def sos_par_info(sos):
     return {"c0": out[0], "sections": out[1:1 + 4 * ns].reshape(ns, 4).copy(), "kappa": out[1 + 4 * ns], "ir_err": out[2 + 4 * ns],
             "accepted": bool(ok.value),
             # the float32 from-rest states (7 - 8 biquads, float32 / complex64 signals): worst probe error on 128- / 96-sample chunks, admitted below 5e-7
-            "v32_err": out[3 + 4 * ns], "v32_err_t96": out[4 + 4 * ns], "v32_admitted": bool(ok.value) and out[3 + 4 * ns] <= 5e-7}
+            # -- per chunk length: .filter and .up by 2 / 4 run 128-sample chunks, .up by 3 runs 96-sample ones (.dn keeps the float64 states)
+            "v32_err": out[3 + 4 * ns], "v32_err_t96": out[4 + 4 * ns], "v32_admitted": bool(ok.value) and out[3 + 4 * ns] <= 5e-7,
+            "v32_admitted_t96": bool(ok.value) and out[4 + 4 * ns] <= 5e-7}
 
 
 def tf2sos(b, a):
