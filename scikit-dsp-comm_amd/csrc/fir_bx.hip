@@ -29,6 +29,7 @@
 // tile comes out transposed (col = lane & 15 = row of the tile, the four registers = four columns), so that
 // the 16 lanes of a group store 16 consecutive outputs.
 #include "skdsp_internal.hpp"
+#include "fir_route.hpp"
 #include <cmath>
 #include <cstring>
 #include <numeric>
@@ -46,7 +47,9 @@ constexpr int kBxUnitsR = 1024;  // float32: 4 per thread, the same 32 VGPRs
 // ... of the lag-split kernels (KSP = 4): their registers and the smaller fp16 planes leave room for windows of several column tiles
 // where 16 columns are already thousands of samples (56 / 64 KiB of planes + the partial tiles: still two workgroups per CU)
 constexpr int kBxUnitsCK = 896, kBxUnitsRK = 2048;
-static constexpr int bx_units(bool cplx, bool ksp) { return ksp ? (cplx ? kBxUnitsCK : kBxUnitsRK) : (cplx ? kBxUnitsC : kBxUnitsR); }
+// (bx_units, bx_fits, bx_geometry, bx_columns -- which shapes the family covers and how a workgroup is laid out -- are host arithmetic: fir_route.hpp)
+static_assert(kBxPlanUnitsC == kBxUnitsC && kBxPlanUnitsR == kBxUnitsR && kBxPlanUnitsCK == kBxUnitsCK && kBxPlanUnitsRK == kBxUnitsRK,
+              "fir_route.hpp sizes the windows of these kernels");
 
 struct BxArgs {
     int64_t n, n_hist, n_out;
@@ -76,6 +79,7 @@ struct BxArgs {
 
 constexpr int kBxPx = 2;          // fp16 pieces of a signal sample
 constexpr int kBxPh = 2;          // fp16 pieces of a tap
+static_assert(kBxPlanPx == kBxPx && kBxPlanPh == kBxPh, "fir_route.hpp counts the registers of these kernels (bx_fits)");
 // The SECOND piece of every operand is the residual times 2^11 (kBxLift): fp16's floor is 2^-24, and a residual is 2^-11 of its first piece at
 // most, so unlifted it fell off that floor for every sample 2^-25 or more below its window's largest -- lifted, a sample keeps its full 22 bits
 // down to 2^-29 of the window's largest and something of itself down to 2^-50 (a 1e12 glitch leaves the rest of its window accurate to 5e-4
@@ -615,107 +619,6 @@ static double bx_f16_val(unsigned short h)
     return (double)hv;
 }
 
-// does a wave's share fit its 256 VGPRs (2 waves per SIMD)?  A operands (4 per tap piece, 32-lag block and row tile) + accumulators + B
-// fragments + 32 prefetch registers + ~60 others; kb, rt: blocks / row tiles PER WAVE.  Used by the geometry below and by the dispatch, so
-// that only kernels the geometry can pick are instantiated.
-static constexpr bool bx_fits(bool cplx, int kb, int rt)
-{
-    return kb * rt <= 16 && 4 * kBxPh * kb * rt + 8 * (cplx ? 2 : 1) * rt + 4 * kBxPx * (cplx ? 2 : 1) + 32 + 60 <= 252;
-}
-
-// geometry of one (L, M): false if the kernel family does not cover it
-static bool bx_geometry(const FirHandle *h, int L, int M, FirHandle::BxTab *t)
-{
-    const int g = std::gcd(L, M), Lp = L / g, q = M / g;
-    const int P = h->ntaps, T = (P + L - 1) / L;
-    const int ds0 = 8 / std::gcd(q, 8);  // q DS must be a multiple of 8
-    int best_k = 0;
-    double best_util = 0.0;
-    for (int k = 1; k <= 16; ++k) {
-        const int RS = Lp * ds0 * k, RT = (RS + 15) / 16;
-        if (RT > 8) break;
-        const double util = (double)RS / (16.0 * RT);
-        if (util > best_util + 1e-9) { best_util = util; best_k = k; }
-    }
-    if (best_k == 0 || best_util < 0.74) return false;
-    const int comp = dtype_complex(h->dtype) ? 2 : 1;
-    const int al = comp == 2 ? 2 : 4;
-    const int cap = 8 * (comp == 2 ? kBxUnitsC : kBxUnitsR);
-    int DS, RS, RT, U0, KB;
-    for (;; best_k /= 2) {
-        DS = ds0 * best_k; RS = Lp * DS; RT = (RS + 15) / 16;
-        int imax = 0;
-        for (int c = 0; c < Lp; ++c) imax = std::max(imax, (int)(((int64_t)c * M) / L));
-        U0 = imax + q * (DS - 1);
-        // window element 0 is input q_ds S0 + U0 + 1 - 32 KB: a 16-byte boundary of x for U0 + 1 = 0 mod 4 (2 for complex)
-        U0 += (al - (U0 + 1) % al) % al;
-        KB = (T + U0 + 31) / 32;
-        // A decimator with a large M (one class, one row tile): 16 slots per column are 16 M inputs, and 16 columns of them may not fit the
-        // window (M = 24: 16 x 384 samples).  Fewer slots per column then -- half-empty row tiles cost matrix-pipe time these shapes do
-        // not lack (M = 24, 512 taps, complex64: 1.43 ms per 2^26 inputs on the kernels behind this one).
-        if (Lp > 1 || best_k % 2 || RS < 8 || 8 * bx_units(comp == 2, true) >= q * DS * 15 + 32 * ((KB + 3) / 4 * 4)) break;
-    }
-    // What does not fit one wave (bx_fits) is tried with the row tiles dealt to wave pairs (RSP = 2: see the kernel); four or more row tiles
-    // always are (the same speed where both fit -- L = 8, 48 taps per phase: 0.1245 / 0.1259 ms -- and the one-wave forms of 4 x 2, 6 x 1 spilled)
-    int RSP = 0;
-    const bool pairs_first = RT >= 4 && RT % 2 == 0;
-    for (int i = 0; i < 2 && !RSP; ++i) {
-        const int rsp = (i == 0) == pairs_first ? 2 : 1;
-        if (RT % rsp || (rsp > 1 && RT < 4)) continue;
-        if (bx_fits(comp == 2, KB, RT / rsp)) RSP = rsp;
-    }
-    // One row tile and a window that holds fewer column tiles than the workgroup has waves (a decimator with a large M), or more blocks
-    // than one wave's registers take: the waves split the lags (KSP = 4: see the kernel); the table is padded to 4 equal shares.
-    int KSP = 1, KBT = KB;
-    if (RT == 1) {
-        const int ns_max = cap > 32 * KB ? (cap - 32 * KB) / (q * DS) + 1 : 0;
-        if (!RSP || ns_max < 64) {
-            const int kbw = (KB + 3) / 4;
-            if (kbw <= 12 && 8 * bx_units(comp == 2, true) >= 32 * 4 * kbw + q * DS * 15) { KSP = 4; KBT = 4 * kbw; RSP = 1; }
-        }
-    }
-    if (!RSP) return false;
-    t->RSP = RSP;
-    t->KSP = KSP;
-    t->L = L; t->M = M; t->Lp = Lp; t->q = q; t->DS = DS; t->RS = RS; t->RT = RT; t->U0 = U0; t->KB = KBT; t->At = nullptr;
-    return true;
-}
-
-static int bx_columns(const FirHandle::BxTab *t, int comp, int64_t n_out)
-{
-    // columns per workgroup: what a window of kBxUnitsC / kBxUnitsR 8-sample units holds (32 KiB of fp16 planes: 3
-    // workgroups per CU by LDS, 2 by registers), multiples of 64 (16 for wide strides), at most 512
-    auto win_of = [&](int NS) { return ((t->q * t->DS * (NS - 1) + 32 * t->KB) + 7) / 8 * 8; };
-    const int cap = 8 * bx_units(comp == 2, t->KSP > 1);
-    int NS = 512;
-    while (NS > 64 && win_of(NS) > cap) NS -= 64;
-    while (NS > 16 && win_of(NS) > cap) NS -= 16;
-    if (win_of(NS) > cap) return 0;
-    const int64_t ncols = (n_out + t->RS - 1) / t->RS;
-    while (NS > 64 && (ncols + NS - 1) / NS < 2 * ctx().num_cus) NS -= 64;  // small problems: more windows
-    return NS;
-}
-
-bool fir_bx_supported(const FirHandle *h, int L, int M, int64_t n_out)
-{
-    if (h->taps_complex || dtype_double(h->dtype)) return false;
-    FirHandle::BxTab t;
-    if (!bx_geometry(h, L, M, &t)) return false;
-    if (bx_columns(&t, dtype_complex(h->dtype) ? 2 : 1, n_out) == 0) return false;
-    return n_out >= (int64_t)t.RS * 64;
-}
-
-// 32-lag blocks the kernel would run for (L, M); 0: not covered (cost model of the callers)
-int fir_bx_blocks(const FirHandle *h, int L, int M, int *row_tiles)
-{
-    if (h->taps_complex || dtype_double(h->dtype)) return 0;
-    if (!opt().fir_bx || !opt().fir_mm) return 0;
-    FirHandle::BxTab t;
-    if (!bx_geometry(h, L, M, &t)) return 0;
-    if (row_tiles) *row_tiles = t.RT;
-    return t.KB;
-}
-
 // A-operand table of one (L, M): At[((kb RT + rt) kBxPh + piece) 64 + lane] = 8 fp16 of row 16 rt + (lane & 15),
 // lags u = K - 1 - (32 kb + 8 (lane >> 4) + i); the taps are L b 2^te, te the power of two that puts the largest into [2^13, 2^14)
 static int get_bx_table(FirHandle *h, int L, int M, const FirHandle::BxTab **out)
@@ -723,7 +626,7 @@ static int get_bx_table(FirHandle *h, int L, int M, const FirHandle::BxTab **out
     for (auto &t : h->bx)
         if (t.L == L && t.M == M) { *out = &t; return SKDSP_OK; }
     FirHandle::BxTab t;
-    SK_CHECK(bx_geometry(h, L, M, &t), SKDSP_ERR_UNSUPPORTED, "fir_bx: L=%d M=%d not covered", L, M);
+    SK_CHECK(bx_geometry(fir_shape_of(h), L, M, &t), SKDSP_ERR_UNSUPPORTED, "fir_bx: L=%d M=%d not covered", L, M);
     const int P = h->ntaps, T = (P + L - 1) / L, K = 32 * t.KB;
     double tmax = 0.0;
     for (int k = 0; k < P; ++k) tmax = std::max(tmax, std::fabs((double)L * h->taps_host[k]));
@@ -835,7 +738,7 @@ int fir_bx_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, int L,
     BxArgs a;
     a.n = n; a.n_hist = n_hist; a.n_out = n_out;
     a.q_ds = t->q * t->DS; a.RS = t->RS; a.U0 = t->U0;
-    a.NS = bx_columns(t, cplx ? 2 : 1, n_out);
+    a.NS = bx_columns(t, cplx ? 2 : 1, n_out, ctx().num_cus);
     SK_CHECK(a.NS > 0, SKDSP_ERR_UNSUPPORTED, "fir_bx: window does not fit LDS (L=%d M=%d)", L, M);
     a.win = ((a.q_ds * (a.NS - 1) + 32 * t->KB) + 7) / 8 * 8;
     a.eo = ((a.q_ds / 8) & 1) && a.NS % 32 == 0 ? 1 : 0;

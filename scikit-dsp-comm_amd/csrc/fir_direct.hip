@@ -23,6 +23,7 @@
 // c64 sample); long .filter calls go to fir_ols.hip instead.  It is the HBM-bound
 // choice only for short filters.
 #include "skdsp_internal.hpp"
+#include "fir_route.hpp"
 #include <type_traits>
 #include <cstring>
 #include <numeric>
@@ -711,16 +712,15 @@ static int get_sw_table(FirHandle *h, int L, int M, int R, int nB, const FirHand
     return SKDSP_OK;
 }
 
-int fir_direct_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, int L, int M, int64_t n_out, void *y,
+int fir_direct_launch(FirHandle *h, int tier, const void *x, int64_t n, int64_t n_hist, int L, int M, int64_t n_out, void *y,
                       hipStream_t s)
 {
     SK_CHECK(L >= 1 && M >= 1, SKDSP_ERR_BADARG, "fir: L and M must be >= 1 (L=%d M=%d)", L, M);
     if (n_out <= 0) return SKDSP_OK;
     SK_CHECK(!(h->taps_complex && !dtype_complex(h->dtype)), SKDSP_ERR_BADARG,
              "fir: complex taps need a complex signal dtype (promote x first)");
-    const int mm_mode = opt().fir_mm, bx_mode = opt().fir_bx;  // 0: never (developer A/B)
-    if (mm_mode && bx_mode && fir_bx_supported(h, L, M, n_out)) return fir_bx_launch(h, x, n, n_hist, L, M, n_out, y, s);
-    if (mm_mode && fir_mm_supported(h, L, M, n_out)) return fir_mm_launch(h, x, n, n_hist, L, M, n_out, y, s);
+    if (tier == kRouteBx) return fir_bx_launch(h, x, n, n_hist, L, M, n_out, y, s);
+    if (tier == kRouteMm) return fir_mm_launch(h, x, n, n_hist, L, M, n_out, y, s);
     void *bank = nullptr;
     int T = 0;
     int rc = get_bank(h, L, &bank, &T);
@@ -738,112 +738,109 @@ int fir_direct_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, in
     const size_t lds_cap = 80 * 1024;  // <= 2 workgroups per CU of the 160 KiB LDS
 
     // ---- preferred: register sliding window (R consecutive outputs per thread) ----
-    const bool no_sw = false;
-    if (!no_sw) {
-        const int Rmax = dtype_double(h->dtype) && dtype_complex(h->dtype) ? 4 : 8;
-        for (int R = Rmax; R >= 2; R >>= 1) {
-            const int q = a.q, P = q * R;
-            const int Tq = (T + q - 1) / q;
-            const int nB = (Tq + 1 + R - 1) / R;      // +1: the optional leading zero tap (delta)
-            const int G = nB;
-            const int64_t win = (int64_t)(G + 256) * P;
-            const int64_t phys = (int64_t)(G + 256) * (P + 1);
-            if ((size_t)phys * esz > lds_cap) continue;
-            const int64_t nb = (a.n_s + 256 * R - 1) / (256 * R);
-            if (nb < ctx().num_cus && R > 2) continue;  // small problems: smaller tiles
-            // interpolation by more than 4 classes: the whole output run of the workgroup is staged
-            // in LDS (needs 256*R*Lp elements next to the window) -- prefer a smaller R that fits
-            const size_t tile_bytes = (size_t)256 * R * a.Lp * esz;
-            const bool want_tile = a.Lp > 4;  // up to 4 classes the per-class row transposition measured faster
-            const bool tile_fits = (size_t)phys * esz + 4096 + tile_bytes <= lds_cap;
-            if (want_tile && !tile_fits && R > 2) continue;
-            const FirHandle::SwTab *tab = nullptr;
-            int rc2 = get_sw_table(h, L, M, R, nB, &tab);
-            if (rc2) return rc2;
-            SwArgs w;
-            w.n = n; w.n_hist = n_hist; w.n_out = n_out;
-            w.L = L; w.Lp = a.Lp; w.q = q; w.G = G; w.nB = nB; w.win = (int)win;
-            w.M = M; w.cf = a.cf;
-            w.half_last = (R == 8 && (Tq + 1) - (nB - 1) * R <= R / 2) ? 1 : 0;
-            size_t lds = (size_t)phys * esz;
-            w.tap_off = -1; w.tap_cnt = 0;
-            if (h->dtype == SKDSP_C64 && !h->taps_complex && R == 8) {
-                const size_t tbytes = (size_t)q * nB * R * 4;  // one class; two buffers
-                const size_t off = (lds + 15) & ~(size_t)15;
-                if (off + 2 * tbytes <= lds_cap) { w.tap_off = (int)off; w.tap_cnt = (int)(tbytes / 4); lds = off + 2 * tbytes; }
-            }
-            w.out_off = -1;
-            w.out_tile = 0;
-            const bool lpt_ok = h->dtype == SKDSP_C64 && !h->taps_complex && R == 8 && w.tap_off >= 0 && a.Lp >= 2 && a.Lp <= 4;
-            if (lpt_ok) {
-                w.out_off = 0;  // unrolled-class kernel: its output tiles alias the (finished) window image
-            } else if (want_tile && tile_fits) {
-                const size_t off = (lds + 15) & ~(size_t)15;
-                w.out_off = (int)off;
-                w.out_tile = 1;
-                lds = off + tile_bytes;
-            } else {
-                const size_t off = (lds + 15) & ~(size_t)15;
-                const size_t obytes = (size_t)4 * 64 * (R + 1) * esz;
-                if (a.Lp > 1 && off + obytes <= lds_cap) { w.out_off = (int)off; lds = off + obytes; }  // Lp == 1 stores 16-byte vectors directly
-            }
+    const int Rmax = dtype_double(h->dtype) && dtype_complex(h->dtype) ? 4 : 8;
+    for (int R = Rmax; R >= 2; R >>= 1) {
+        const int q = a.q, P = q * R;
+        const int Tq = (T + q - 1) / q;
+        const int nB = (Tq + 1 + R - 1) / R;      // +1: the optional leading zero tap (delta)
+        const int G = nB;
+        const int64_t win = (int64_t)(G + 256) * P;
+        const int64_t phys = (int64_t)(G + 256) * (P + 1);
+        if ((size_t)phys * esz > lds_cap) continue;
+        const int64_t nb = (a.n_s + 256 * R - 1) / (256 * R);
+        if (nb < ctx().num_cus && R > 2) continue;  // small problems: smaller tiles
+        // interpolation by more than 4 classes: the whole output run of the workgroup is staged
+        // in LDS (needs 256*R*Lp elements next to the window) -- prefer a smaller R that fits
+        const size_t tile_bytes = (size_t)256 * R * a.Lp * esz;
+        const bool want_tile = a.Lp > 4;  // up to 4 classes the per-class row transposition measured faster
+        const bool tile_fits = (size_t)phys * esz + 4096 + tile_bytes <= lds_cap;
+        if (want_tile && !tile_fits && R > 2) continue;
+        const FirHandle::SwTab *tab = nullptr;
+        int rc2 = get_sw_table(h, L, M, R, nB, &tab);
+        if (rc2) return rc2;
+        SwArgs w;
+        w.n = n; w.n_hist = n_hist; w.n_out = n_out;
+        w.L = L; w.Lp = a.Lp; w.q = q; w.G = G; w.nB = nB; w.win = (int)win;
+        w.M = M; w.cf = a.cf;
+        w.half_last = (R == 8 && (Tq + 1) - (nB - 1) * R <= R / 2) ? 1 : 0;
+        size_t lds = (size_t)phys * esz;
+        w.tap_off = -1; w.tap_cnt = 0;
+        if (h->dtype == SKDSP_C64 && !h->taps_complex && R == 8) {
+            const size_t tbytes = (size_t)q * nB * R * 4;  // one class; two buffers
+            const size_t off = (lds + 15) & ~(size_t)15;
+            if (off + 2 * tbytes <= lds_cap) { w.tap_off = (int)off; w.tap_cnt = (int)(tbytes / 4); lds = off + 2 * tbytes; }
+        }
+        w.out_off = -1;
+        w.out_tile = 0;
+        const bool lpt_ok = h->dtype == SKDSP_C64 && !h->taps_complex && R == 8 && w.tap_off >= 0 && a.Lp >= 2 && a.Lp <= 4;
+        if (lpt_ok) {
+            w.out_off = 0;  // unrolled-class kernel: its output tiles alias the (finished) window image
+        } else if (want_tile && tile_fits) {
+            const size_t off = (lds + 15) & ~(size_t)15;
+            w.out_off = (int)off;
+            w.out_tile = 1;
+            lds = off + tile_bytes;
+        } else {
+            const size_t off = (lds + 15) & ~(size_t)15;
+            const size_t obytes = (size_t)4 * 64 * (R + 1) * esz;
+            if (a.Lp > 1 && off + obytes <= lds_cap) { w.out_off = (int)off; lds = off + obytes; }  // Lp == 1 stores 16-byte vectors directly
+        }
 #define SK_SWQ(XT, BT, RR, QQ)                                                                                        \
-    do {                                                                                                              \
-        if (lds > 64 * 1024)                                                                                          \
-            (void)hipFuncSetAttribute((const void *)fir_sw_kernel<XT, BT, RR, QQ>,                                    \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
-        hipLaunchKernelGGL((fir_sw_kernel<XT, BT, RR, QQ>), dim3((unsigned)nb), dim3(256), lds, s, (const XT *)x,     \
-                           (const BT *)tab->taps, (const int *)tab->rho, w, (XT *)y);                                 \
-    } while (0)
+do {                                                                                                              \
+    if (lds > 64 * 1024)                                                                                          \
+        (void)hipFuncSetAttribute((const void *)fir_sw_kernel<XT, BT, RR, QQ>,                                    \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
+    hipLaunchKernelGGL((fir_sw_kernel<XT, BT, RR, QQ>), dim3((unsigned)nb), dim3(256), lds, s, (const XT *)x,     \
+                       (const BT *)tab->taps, (const int *)tab->rho, w, (XT *)y);                                 \
+} while (0)
 #define SK_SWR(XT, BT, RR)                                   \
-    do {                                                     \
-        if (q == 1) SK_SWQ(XT, BT, RR, 1);                   \
-        else if (q == 2) SK_SWQ(XT, BT, RR, 2);              \
-        else if (q == 3) SK_SWQ(XT, BT, RR, 3);              \
-        else SK_SWQ(XT, BT, RR, 0);                          \
-    } while (0)
+do {                                                     \
+    if (q == 1) SK_SWQ(XT, BT, RR, 1);                   \
+    else if (q == 2) SK_SWQ(XT, BT, RR, 2);              \
+    else if (q == 3) SK_SWQ(XT, BT, RR, 3);              \
+    else SK_SWQ(XT, BT, RR, 0);                          \
+} while (0)
 #define SK_SW(XT, BT)                                        \
-    do {                                                     \
-        if (R == 8) SK_SWR(XT, BT, 8);                       \
-        else if (R == 4) SK_SWR(XT, BT, 4);                  \
-        else SK_SWR(XT, BT, 2);                              \
-    } while (0)
+do {                                                     \
+    if (R == 8) SK_SWR(XT, BT, 8);                       \
+    else if (R == 4) SK_SWR(XT, BT, 4);                  \
+    else SK_SWR(XT, BT, 2);                              \
+} while (0)
 #define SK_SWL(QQ, LL)                                                                                                 \
-    do {                                                                                                               \
-        if (lds > 64 * 1024)                                                                                           \
-            (void)hipFuncSetAttribute((const void *)fir_sw_kernel<float2, float, 8, QQ, LL>,                           \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                          \
-        hipLaunchKernelGGL((fir_sw_kernel<float2, float, 8, QQ, LL>), dim3((unsigned)nb), dim3(256), lds, s,           \
-                           (const float2 *)x, (const float *)tab->taps, (const int *)tab->rho, w, (float2 *)y);        \
-    } while (0)
+do {                                                                                                               \
+    if (lds > 64 * 1024)                                                                                           \
+        (void)hipFuncSetAttribute((const void *)fir_sw_kernel<float2, float, 8, QQ, LL>,                           \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                          \
+    hipLaunchKernelGGL((fir_sw_kernel<float2, float, 8, QQ, LL>), dim3((unsigned)nb), dim3(256), lds, s,           \
+                       (const float2 *)x, (const float *)tab->taps, (const int *)tab->rho, w, (float2 *)y);        \
+} while (0)
 #define SK_SWLQ(LL)                                   \
-    do {                                              \
-        if (q == 1) SK_SWL(1, LL);                    \
-        else if (q == 2) SK_SWL(2, LL);               \
-        else if (q == 3) SK_SWL(3, LL);               \
-        else SK_SWL(0, LL);                           \
-    } while (0)
-            if (lpt_ok) {
-                if (a.Lp == 2) SK_SWLQ(2);
-                else if (a.Lp == 3) SK_SWLQ(3);
-                else SK_SWLQ(4);
-                SK_HIP(hipGetLastError());
-                return SKDSP_OK;
-            }
-#undef SK_SWLQ
-#undef SK_SWL
-            switch (h->dtype) {
-            case SKDSP_F32: SK_SW(float, float); break;
-            case SKDSP_F64: SK_SW(double, double); break;
-            case SKDSP_C64: if (h->taps_complex) SK_SW(float2, float2); else SK_SW(float2, float); break;
-            case SKDSP_C128: if (h->taps_complex) SK_SW(double2, double2); else SK_SW(double2, double); break;
-            }
-#undef SK_SW
-#undef SK_SWR
-#undef SK_SWQ
+do {                                              \
+    if (q == 1) SK_SWL(1, LL);                    \
+    else if (q == 2) SK_SWL(2, LL);               \
+    else if (q == 3) SK_SWL(3, LL);               \
+    else SK_SWL(0, LL);                           \
+} while (0)
+        if (lpt_ok) {
+            if (a.Lp == 2) SK_SWLQ(2);
+            else if (a.Lp == 3) SK_SWLQ(3);
+            else SK_SWLQ(4);
             SK_HIP(hipGetLastError());
             return SKDSP_OK;
         }
+#undef SK_SWLQ
+#undef SK_SWL
+        switch (h->dtype) {
+        case SKDSP_F32: SK_SW(float, float); break;
+        case SKDSP_F64: SK_SW(double, double); break;
+        case SKDSP_C64: if (h->taps_complex) SK_SW(float2, float2); else SK_SW(float2, float); break;
+        case SKDSP_C128: if (h->taps_complex) SK_SW(double2, double2); else SK_SW(double2, double); break;
+        }
+#undef SK_SW
+#undef SK_SWR
+#undef SK_SWQ
+        SK_HIP(hipGetLastError());
+        return SKDSP_OK;
     }
 
     // ---- generic fallback: one LDS read per FMA, any stride ----

@@ -15,6 +15,7 @@
 #include "skdsp_internal.hpp"
 #include "ols4k_tables.hpp"
 #include "tile_walk.hpp"
+#include "fir_route.hpp"
 
 namespace skdsp {
 
@@ -239,15 +240,6 @@ template <bool REAL, int MS> __global__ __launch_bounds__(256, 2) void dn4k_kern
     }
 }
 
-// complex64 (any taps) or float32 with real taps; per phase at most 2049 taps (half a tile of overlap)
-bool fir_dn4k_supported(const FirHandle *h, int M)
-{
-    if (M < 2 || M > 4) return false;   // (one load group: all phases of a sample in one thread)
-    const int T = dn_taps_per_phase(h->ntaps, M);
-    if (T - 1 > 2048) return false;
-    return h->dtype == SKDSP_C64 || (h->dtype == SKDSP_F32 && !h->taps_complex);
-}
-
 static int dn4k_plan(FirHandle *h, int M, Dn4kPlan **out)
 {
     return tile_plan(h->dn4k, M, out, [&](Dn4kPlan &p) {
@@ -269,7 +261,7 @@ int fir_dn4k_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, int 
     note_path("fir_dn4k");
     const int64_t n_out = n / M;
     if (n_out <= 0) return SKDSP_OK;
-    SK_CHECK(fir_dn4k_supported(h, M), SKDSP_ERR_UNSUPPORTED, "fir_dn4k: needs complex64 (or float32 with real taps), 2 <= M <= 4, at most 2049 taps per phase");
+    SK_CHECK(fir_dn4k_supported(fir_shape_of(h), M), SKDSP_ERR_UNSUPPORTED, "fir_dn4k: needs complex64 (or float32 with real taps), 2 <= M <= 4, at most 2049 taps per phase");
     Dn4kPlan *p = nullptr;
     int rc = dn4k_plan(h, M, &p);
     if (rc) return rc;

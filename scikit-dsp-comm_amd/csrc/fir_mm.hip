@@ -22,6 +22,7 @@
 // B read are q DS elements apart, which without the skew lands them on a few banks for most strides
 // (12 complex elements: 2-way, 16: 8-way; with it at most 2-way for every stride, none for 12).
 #include "skdsp_internal.hpp"
+#include "fir_route.hpp"
 #include <numeric>
 #include <vector>
 
@@ -236,21 +237,6 @@ static int get_mm_table(FirHandle *h, int L, int M, const FirHandle::MmTab **out
     return SKDSP_OK;
 }
 
-bool fir_mm_supported(const FirHandle *h, int L, int M, int64_t n_out)
-{
-    if (h->taps_complex || h->dtype == SKDSP_C128) return false;  // complex128: the sliding-window kernel measured faster
-    const int kmax = dtype_double(h->dtype) ? 48 : 96;  // A operands in registers: 1 (float) or 2 (double) VGPRs per step
-    const int g = std::gcd(L, M), Lp = L / g, q = M / g;
-    if (Lp > 16) return false;
-    const int T = (h->ntaps + L - 1) / L, DS = 16 / Lp;
-    const int64_t imax = ((int64_t)(Lp - 1) * M) / L;
-    const int64_t K = T + imax + (int64_t)q * (DS - 1);
-    if (K > 4 * kmax - 12) return false;                  // A operands must fit the register file
-    const int64_t win = (int64_t)q * DS * 63 + K + 32;    // smallest workgroup tile (NS = 64)
-    if (win * 9 / 8 * (int64_t)dtype_size(h->dtype) > 63 * 1024) return false;
-    return n_out >= 16 * 64;
-}
-
 int fir_mm_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, int L, int M, int64_t n_out, void *y, hipStream_t s)
 {
     note_path("fir_mm");
@@ -303,6 +289,7 @@ int fir_mm_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, int L,
     case 96: SK_MM(XT, 96); break;                                      \
     default: SK_CHECK(false, SKDSP_ERR_UNSUPPORTED, "fir_mm: %d steps", a.K4); \
     }
+    static_assert(kMmPlanStepsF == 96 && kMmPlanStepsD == 48, "fir_route.hpp (fir_mm_supported) admits what the lists of SK_MMK / SK_MMKD instantiate");
 #define SK_MMKD(XT)                                                      \
     switch (a.K4) {                                                      \
     case 4: SK_MM(XT, 4); break;                                      \

@@ -20,6 +20,7 @@
 // max-abs/peak against a float64 direct FIR (tests/host/ols_emul.cpp, GPU parity tests).
 #include "skdsp_internal.hpp"
 #include "ols_tables.hpp"
+#include "fir_route.hpp"
 #include <cstdlib>
 #include <cstdio>
 
@@ -978,14 +979,6 @@ __global__ __launch_bounds__(256, 2) void ols_rep_kernel(OlsArgs A)
     }
 }
 
-bool fir_ols_supported(const FirHandle *h)
-{
-    // complex64 signal; overlap must leave at least half the tile as useful output
-    if (h->ntaps < 2 || h->ntaps - 1 > 4096) return false;
-    // complex64 with any taps; float32 with real taps (two real tiles per complex tile)
-    return h->dtype == SKDSP_C64 || (h->dtype == SKDSP_F32 && !h->taps_complex);
-}
-
 // Tables of one plan: `up` phase filters (phase p: taps gain * b[p + up t], t < T) as `up` consecutive Hp tables; up = 1 is the filter itself.
 // kind 0: all `up` phases; 1: pairs of phases (real taps: table k holds phase 2k + i phase 2k+1, see load_tile_xr; an odd up leaves its last
 // phase out); 2: the last phase alone (what kind 1 leaves out)
@@ -1115,7 +1108,7 @@ int fir_ols_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, void 
     if (n <= 0) return SKDSP_OK;
     if (dec > 1) n = (n / dec) * dec;  // the dropped tail is never computed
     if (n <= 0) return SKDSP_OK;
-    SK_CHECK(fir_ols_supported(h), SKDSP_ERR_UNSUPPORTED, "fir_ols: needs complex64 (or float32 with real taps) and 2..4097 taps");
+    SK_CHECK(fir_ols_supported(fir_shape_of(h)), SKDSP_ERR_UNSUPPORTED, "fir_ols: needs complex64 (or float32 with real taps) and 2..4097 taps");
     // (the decimating stores divide tile-local indices below M + 16384 by M through a multiply-high by ceil(2^32 / M): exact while (M + 16384) M < 2^32)
     SK_CHECK(dec <= 32768, SKDSP_ERR_UNSUPPORTED, "fir_ols: decimation by %d (the decimating store takes M <= 32768)", dec);
     int rc = ensure_plan(h);
@@ -1179,26 +1172,8 @@ int fir_ols_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, void 
 // ---- multirate_FIR.up with long phases ---------------------------------------------------------------------------
 // y[i L + p] = L sum_t b[p + L t] x[i - t]: L filters of ceil(Ntaps / L) taps over the SAME input, outputs interleaved.  The polyphase
 // kernels (fir_direct / fir_bx) spend Ntaps / L multiply-adds per output; from ~100 taps per phase on, the overlap-save walk over (tile,
-// phase) pairs is cheaper: every pair costs what one tile of .filter costs, whatever the phase length.
-bool fir_ols_up_supported(const FirHandle *h, int L)
-{
-    if (L < 2 || L > 256) return false;   // (the every-M-th store: L <= 64, checked at launch)
-    const int T = (h->ntaps + L - 1) / L;
-    if (T < 2 || T - 1 > 4096) return false;
-    return h->dtype == SKDSP_C64 || (h->dtype == SKDSP_F32 && !h->taps_complex);
-}
-
-// float32 signals, no decimation: the phases run in pairs through the complex tile (load_tile_xr).  Even L: an 8-byte aligned destination
-// (L / 2 rows of pairs in the rows form).  Odd L (7 .. 13, strided form only): (L - 1) / 2 pairs as 8-byte elements at 4-byte aligned
-// addresses, then the last phase on its own (two real tiles per pass) -- L passes per two tiles either way.  Measured against one phase
-// per pass (2^26 outputs, 256 taps per phase): L = 7 0.237 -> 0.216 ms, 9 0.248 (rows) -> 0.209, 11 0.255 -> 0.229, 13 0.254 -> 0.245;
-// L = 3, 5 lose (0.168 -> 0.186, 0.200 -> 0.208: the misaligned 8-byte stores and the second launch), 15 loses to the rows form.
-bool fir_ols_up_pairs(const FirHandle *h, int L, int dec, const void *y)
-{
-    if (!opt().fir_up_pair || h->dtype != SKDSP_F32 || h->taps_complex || dec > 1) return false;
-    if (L % 2 == 0) return ((uintptr_t)y & 7) == 0;
-    return L >= 7 && L <= 13 && ((uintptr_t)y & 3) == 0;
-}
+// phase) pairs is cheaper: every pair costs what one tile of .filter costs, whatever the phase length (which calls, and when the phases
+// of a float32 signal run in pairs: fir_ols_up_supported, fir_ols_up_pairs in fir_route.hpp).
 
 static int up_plan(FirHandle *h, int L, int kind, OlsPlan **out)
 {
@@ -1266,17 +1241,11 @@ static int up_walk(FirHandle *h, int kind, const void *x, int64_t n, int64_t n_h
 }
 
 // multirate_FIR.up, even L, at most 4097 taps in all: tiles of the OUTPUT, the zero-stuffed tile's spectrum from its non-zero columns (ols_rep_kernel)
-bool fir_ols_rep_supported(const FirHandle *h, int L)
-{
-    if (L < 2 || L % 2 || L > 4096 || !opt().fir_up_rep) return false;
-    return fir_ols_supported(h);
-}
-
 int fir_ols_rep_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, int L, void *y, hipStream_t s)
 {
     note_path("fir_ols_rep");
     if (n <= 0) return SKDSP_OK;
-    SK_CHECK(fir_ols_rep_supported(h, L), SKDSP_ERR_UNSUPPORTED, "fir_ols_rep: needs complex64 (or float32 with real taps), an even L and 2..4097 taps");
+    SK_CHECK(fir_ols_rep_supported(fir_shape_of(h), L, opt().fir_up_rep), SKDSP_ERR_UNSUPPORTED, "fir_ols_rep: needs complex64 (or float32 with real taps), an even L and 2..4097 taps");
     OlsPlan *p = nullptr;
     int rc = up_plan(h, L, 3, &p);
     if (rc) return rc;
@@ -1324,10 +1293,10 @@ int fir_ols_up_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, in
     note_path("fir_ols_up");
     if (n <= 0) return SKDSP_OK;
     SK_CHECK(dec >= 1 && dec <= 4096 && (dec == 1 || L <= 64), SKDSP_ERR_UNSUPPORTED, "fir_ols_up: L / M = %d / %d (the fused L / M store takes L <= 64, M <= 4096)", L, dec);
-    SK_CHECK(fir_ols_up_supported(h, L), SKDSP_ERR_UNSUPPORTED, "fir_ols_up: needs complex64 (or float32 with real taps), 2 <= L <= 256, 2..4097 taps per phase");
+    SK_CHECK(fir_ols_up_supported(fir_shape_of(h), L), SKDSP_ERR_UNSUPPORTED, "fir_ols_up: needs complex64 (or float32 with real taps), 2 <= L <= 256, 2..4097 taps per phase");
     if (!paired) return up_walk(h, 0, x, n, n_hist, L, y, s, dec, rows_pitch);
     // (rows_pitch of a paired launch counts 8-byte elements: the caller weaves L / 2 rows of pairs)
-    SK_CHECK(fir_ols_up_pairs(h, L, dec, y) && (L % 2 == 0 || rows_pitch == 0), SKDSP_ERR_BADARG,
+    SK_CHECK(fir_ols_up_pairs(fir_shape_of(h), L, dec, (unsigned)(uintptr_t)y, opt().fir_up_pair) && (L % 2 == 0 || rows_pitch == 0), SKDSP_ERR_BADARG,
              "fir_ols_up: phases in pairs need float32, real taps, no decimation, and an 8-byte aligned destination (even L) or the strided form (odd L, 7 .. 13)");
     int rc = up_walk(h, 1, x, n, n_hist, L, y, s, 1, rows_pitch);
     if (rc || L % 2 == 0) return rc;

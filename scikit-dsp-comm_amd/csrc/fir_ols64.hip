@@ -19,6 +19,7 @@
 // filters are partitioned by fir_api.hip).  Algorithmic bytes: 32 B per complex128 sample, 16 B per float64 sample.
 // Precision: float64 butterflies, twiddle powers by repeated multiplication (<= 15 products): 1e-14 of the peak.
 #include "skdsp_internal.hpp"
+#include "fir_route.hpp"
 #include <complex>
 #include <vector>
 #include <cmath>
@@ -562,12 +563,6 @@ void fir_ols64_free(Ols64Plan *p)
     delete p;
 }
 
-bool fir_ols64_supported(const FirHandle *h)
-{
-    if (h->ntaps < 2 || h->ntaps - 1 > 2048) return false;
-    return h->dtype == SKDSP_C128 || (h->dtype == SKDSP_F64 && !h->taps_complex);
-}
-
 // Tables of one plan: `up` phase filters (phase q: taps up * b[q + up t]) as `up` consecutive H tables; up = 1: the filter itself.
 static int build_plan64(const FirHandle *h, int up, Ols64Plan **out, bool paired = false)
 {
@@ -644,7 +639,7 @@ int fir_ols64_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, voi
     if (n <= 0) return SKDSP_OK;
     if (dec > 1) n = (n / dec) * dec;
     if (n <= 0) return SKDSP_OK;
-    SK_CHECK(fir_ols64_supported(h), SKDSP_ERR_UNSUPPORTED, "fir_ols64: needs complex128 (or float64 with real taps) and 2..2049 taps");
+    SK_CHECK(fir_ols64_supported(fir_shape_of(h)), SKDSP_ERR_UNSUPPORTED, "fir_ols64: needs complex128 (or float64 with real taps) and 2..2049 taps");
     int rc = ensure_plan64(h);
     if (rc) return rc;
     Ols64Plan *p = h->ols64;
@@ -675,28 +670,14 @@ int fir_ols64_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, voi
 }
 
 // multirate_FIR.up with long phases (see fir_ols.hip, fir_ols_up_launch): complex128, float64 with real taps; 2..2049 taps per phase
-bool fir_ols64_up_supported(const FirHandle *h, int L)
-{
-    if (L < 2 || L > 256) return false;   // (the every-M-th store: L <= 64, checked at launch)
-    const int T = (h->ntaps + L - 1) / L;
-    if (T < 2 || T - 1 > 2048) return false;
-    return h->dtype == SKDSP_C128 || (h->dtype == SKDSP_F64 && !h->taps_complex);
-}
-
-// float64 signals, real taps, even L, no decimation, a 16-byte aligned destination: the phases run in pairs through the complex tile
-bool fir_ols64_up_pairs(const FirHandle *h, int L, int dec, const void *y)
-{
-    return opt().fir_up_pair && h->dtype == SKDSP_F64 && !h->taps_complex && L % 2 == 0 && dec <= 1 && ((uintptr_t)y & 15) == 0;
-}
-
 int fir_ols64_up_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, int L, void *y, hipStream_t s, int dec, int64_t rows_pitch, int paired_in)
 {
     note_path("fir_ols64_up");
     if (n <= 0) return SKDSP_OK;
     SK_CHECK(dec >= 1 && dec <= 4096 && (dec == 1 || L <= 64), SKDSP_ERR_UNSUPPORTED, "fir_ols64_up: L / M = %d / %d (the fused L / M store takes L <= 64, M <= 4096)", L, dec);
-    SK_CHECK(fir_ols64_up_supported(h, L), SKDSP_ERR_UNSUPPORTED, "fir_ols64_up: needs complex128 (or float64 with real taps), 2 <= L <= 256, 2..2049 taps per phase");
+    SK_CHECK(fir_ols64_up_supported(fir_shape_of(h), L), SKDSP_ERR_UNSUPPORTED, "fir_ols64_up: needs complex128 (or float64 with real taps), 2 <= L <= 256, 2..2049 taps per phase");
     const bool paired = paired_in != 0;
-    SK_CHECK(!paired || fir_ols64_up_pairs(h, L, dec, y), SKDSP_ERR_BADARG, "fir_ols64_up: phases in pairs need float64, real taps, an even L, no decimation and a 16-byte aligned destination");
+    SK_CHECK(!paired || fir_ols64_up_pairs(fir_shape_of(h), L, dec, (unsigned)(uintptr_t)y, opt().fir_up_pair), SKDSP_ERR_BADARG, "fir_ols64_up: phases in pairs need float64, real taps, an even L, no decimation and a 16-byte aligned destination");
     const int key = paired ? -L : L;
     Ols64Plan *p = nullptr;
     for (auto &u : h->ols64_up)

@@ -15,6 +15,7 @@
 #include "skdsp_internal.hpp"
 #include "ols4k_tables.hpp"
 #include "tile_walk.hpp"
+#include "fir_route.hpp"
 
 namespace skdsp {
 
@@ -304,17 +305,6 @@ template <bool XR, int G> __global__ __launch_bounds__(256, 2) void up4k_kernel(
     }
 }
 
-// complex64 (any taps) or float32 with real taps; per phase at most 2049 taps (half a tile of overlap)
-bool fir_up4k_supported(const FirHandle *h, int L)
-{
-    // (a plan holds one 32 / 16 KiB table per pass, built on first use under the handle's lock: 256 passes are 8 / 4 MiB and a few ms of host transforms;
-    // beyond that the walk over (tile, phase) pairs and the polyphase kernels serve the call)
-    if (L < 2 || L > 256) return false;
-    const int T = up_taps_per_phase(h->ntaps, L);
-    if (T - 1 > 2048) return false;
-    return h->dtype == SKDSP_C64 || (h->dtype == SKDSP_F32 && !h->taps_complex);
-}
-
 static int up4k_plan(FirHandle *h, int L, Up4kPlan **out)
 {
     return tile_plan(h->up4k, L, out, [&](Up4kPlan &p) {
@@ -337,7 +327,7 @@ int fir_up4k_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, int 
 {
     note_path("fir_up4k");
     if (n <= 0) return SKDSP_OK;
-    SK_CHECK(fir_up4k_supported(h, L), SKDSP_ERR_UNSUPPORTED, "fir_up4k: needs complex64 (or float32 with real taps), 2 <= L <= 4096, at most 2049 taps per phase");
+    SK_CHECK(fir_up4k_supported(fir_shape_of(h), L), SKDSP_ERR_UNSUPPORTED, "fir_up4k: needs complex64 (or float32 with real taps), 2 <= L <= 256, at most 2049 taps per phase");
     Up4kPlan *p = nullptr;
     int rc = up4k_plan(h, L, &p);
     if (rc) return rc;

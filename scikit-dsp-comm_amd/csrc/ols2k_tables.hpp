@@ -61,6 +61,7 @@ inline void append_Hp(const cd *h, int len, std::vector<float4> &Hp)
 // the phase filters of multirate_FIR.up / .dn on this tile (ols_tables.hpp)
 using ols::up_taps_per_phase;
 using ols::up_passes;
+using ols::tile_overlap;
 using ols::dn_taps_per_phase;
 inline void make_up_tables(const double *taps, int ntaps, int comp, int L, bool real_pairs, std::vector<float4> &Hp) { ols::make_up_tables(taps, ntaps, comp, L, real_pairs, Hp, append_Hp); }
 inline void make_dn_tables(const double *taps, int ntaps, int comp, int M, std::vector<float4> &Hp) { ols::make_dn_tables(taps, ntaps, comp, M, Hp, append_Hp); }

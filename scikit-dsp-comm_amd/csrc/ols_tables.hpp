@@ -95,6 +95,13 @@ inline void make_Hp(const double *taps, int ntaps, int comp, std::vector<float4>
 // the interleaved pair (y[i L + 2q], y[i L + 2q + 1]) as one 8-byte element); an odd L leaves the last pass's imaginary part empty.
 inline int up_taps_per_phase(int ntaps, int L) { return (ntaps + L - 1) / L; }
 inline int up_passes(int L, bool real_pairs) { return real_pairs ? (L + 1) / 2 : L; }
+// A persistent walk over tiles of N points: overlap = taps per phase - 1 rounded up to whole blocks (at least one), V = the samples a tile keeps.
+inline void tile_overlap(int taps_per_phase, int block, int N, int *ov, int *V)
+{
+    *ov = ((taps_per_phase - 1 + block - 1) / block) * block;
+    if (*ov == 0) *ov = block;
+    *V = N - *ov;
+}
 // taps: ntaps real (comp = 1) or interleaved complex (comp = 2) doubles
 template <class AppendHp>
 inline void make_up_tables(const double *taps, int ntaps, int comp, int L, bool real_pairs, std::vector<float4> &Hp, AppendHp append_Hp)

@@ -59,9 +59,9 @@ struct Options {
     int iir_dn_t96 = 1;       // the parallel-form .dn of float32 / complex64 signals on 96-sample chunks: 1 where measured to pay (see par_choose in iir_par_plan.hpp), 2 wherever M divides 96, 3 as 1 but M = 2 keeps its gathering in ranges for every cascade, 0 never (A/B switch)
     int iir_dn_compact = 1;   // 0: the parallel-form .dn keeps the image-and-pick store for every M (A/B switch)
     int fir_up_ols_min = 64;  // multirate_FIR.up: phases of at least this many taps MAY go through the overlap-save walk (the cost model
-                              // of fir_up_prefers_ols decides); 0: never; -k: always from k taps per phase on (A/B switch)
+                              // of fir_up_model in fir_route.hpp decides); 0: never; -k: always from k taps per phase on (A/B switch)
     int fir_up_rows_min = -1; // multirate_FIR.up through the overlap-save walk: from this L on the phases leave as rows and a second kernel weaves them
-                              // (-1: the measured crossover per dtype, fir_up_rows in fir_api.hip; 0: never)
+                              // (-1: the measured crossover per dtype, fir_up_rows in fir_route.hpp; 0: never)
     int fir_up_pair = 1;      // 0: float32 .up through the overlap-save walk never pairs its phases (A/B switch)
     int fir_up4k = 1;         // 0: multirate_FIR.up never through the one-workgroup-per-input-tile interpolator (fir_up4k.hip); the older engines instead (A/B switch)
     int fir_up2k = 1;         // the 2048-point tile with all phases per thread (fir_up2k.hip): 1 from five passes on (complex64: L >= 5, float32: L >= 9), 2 always, 0 never (A/B switch)
@@ -194,14 +194,7 @@ template <class P, class Fill> int tile_plan(TilePlans &plans, int key, P **out,
     plans.push_back(std::move(p));
     return SKDSP_OK;
 }
-// The launch arithmetic of a persistent walk over tiles of N points.
-// Overlap = taps per phase - 1 rounded up to whole blocks (at least one), V = the samples a tile keeps.
-inline void tile_overlap(int taps_per_phase, int block, int N, int *ov, int *V)
-{
-    *ov = ((taps_per_phase - 1 + block - 1) / block) * block;
-    if (*ov == 0) *ov = block;
-    *V = N - *ov;
-}
+// The launch arithmetic of a persistent walk over tiles (their overlap: tile_overlap in ols_tables.hpp).
 // 2 workgroups per CU, less the slots option ols_reserve leaves free (where the grid is at least 4 x that), at most one per tile
 inline int64_t persistent_grid(int64_t ntiles)
 {
@@ -231,7 +224,7 @@ struct FirHandle : HandleBase {
     struct MmTab { int L, M, Lp, q, DS, RS, U0, K4; void *At; };
     std::vector<MmTab> mm;
     // bf16x3 Toeplitz-product A-operand tables, keyed by (L, M)  -- fir_bx.hip
-    struct BxTab { int L, M, Lp, q, DS, RS, RT, U0, KB, RSP, KSP; float tap_inv; void *At; };   // RT / KB: row tiles / 32-lag blocks of the table; RSP / KSP: waves they are dealt to
+    struct BxTab { int L, M, Lp, q, DS, RS, RT, U0, KB, RSP, KSP; float tap_inv = 0.0f; void *At = nullptr; };   // the fields of BxGeometry (fir_route.hpp: bx_geometry fills them), the taps' scale and the table
     std::vector<BxTab> bx;
     OlsPlan *ols = nullptr;
     struct OlsUp { int L; OlsPlan *plan; };   // overlap-save plans of multirate_FIR.up, keyed by L (fir_ols_up_launch)
@@ -242,7 +235,7 @@ struct FirHandle : HandleBase {
     Ols64Plan *ols64 = nullptr;
     struct Ols64Up { int L; Ols64Plan *plan; };
     std::vector<Ols64Up> ols64_up;
-    // Filters longer than one kernel launch takes (fir_part_len) run as partial FIRs over consecutive tap segments,
+    // Filters longer than one kernel launch takes (fir_part_len in fir_route.hpp) run as partial FIRs over consecutive tap segments,
     // each applied to the correspondingly delayed input and summed (fir_api.hip): parts[s] holds taps [s seg, (s+1) seg).
     std::vector<FirHandle *> parts;
     int part_seg = 0;
@@ -255,21 +248,18 @@ struct FirHandle : HandleBase {
 // the taps as the careful path reads them (uploaded on first use, under the handle's lock like every other table)
 int fir_careful(FirHandle *h, CarefulFir *out);
 
-// direct-form / polyphase launcher (fir_direct.hip).
+// Which engine a call runs, and whether an engine applies to a shape: fir_route.hpp (standard headers only; the FIR units include it).
+// direct-form / polyphase launcher (fir_direct.hip): the tier fir_direct_tier (fir_route.hpp) names -- fir_bx_launch, fir_mm_launch, or its own kernels.
 //   y[m] = L * sum_t b[phi + L t] * x[i - t],  j = m*M, phi = j mod L, i = j div L,  m in [0, n_out)
-int fir_direct_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, int L, int M, int64_t n_out,
+int fir_direct_launch(FirHandle *h, int tier, const void *x_dev, int64_t n, int64_t n_hist, int L, int M, int64_t n_out,
                       void *y_dev, hipStream_t s);
 // Toeplitz product on the FP32 matrix pipe (fir_mm.hip): float32 / complex64 signals, real taps
-bool fir_mm_supported(const FirHandle *h, int L, int M, int64_t n_out);
 int fir_mm_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, int L, int M, int64_t n_out, void *y_dev,
                   hipStream_t s);
 // Toeplitz product on the BF16 matrix pipe in float32 precision (3-way bf16 split, fir_bx.hip): same coverage, tried first
-bool fir_bx_supported(const FirHandle *h, int L, int M, int64_t n_out);
-int fir_bx_blocks(const FirHandle *h, int L, int M, int *row_tiles = nullptr);  // 32-lag blocks per output tile, 0 = not covered
 int fir_bx_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, int L, int M, int64_t n_out, void *y_dev,
                   hipStream_t s);
 // FFT overlap-save (fir_ols.hip): c64 (and packed f32) .filter
-bool fir_ols_supported(const FirHandle *h);
 int fir_ols_tile_outputs(FirHandle *h, int *V);  // outputs per overlap-save tile (builds the plan if needed)
 int fir_algo_for(const FirHandle *h, int64_t n);  // SKDSP_FIR_OLS / SKDSP_FIR_DIRECT as skdsp_fir_filter_dev would pick
 int fir_ols_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, void *y_dev, hipStream_t s,
@@ -282,30 +272,21 @@ int fir_ols_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, v
 int fir_ols_publish_halo(unsigned *flag, unsigned seq, hipStream_t s);  // one-thread kernel: *flag = seq (agent-scope release)
 void fir_ols_free(OlsPlan *p);
 // multirate_FIR.up as an overlap-save walk over (tile, phase) pairs: complex64, float32 with real taps; 2..4097 taps per phase
-bool fir_ols_up_supported(const FirHandle *h, int L);
-bool fir_ols_up_pairs(const FirHandle *h, int L, int dec, const void *y_dev);   // float32, even L: phases in pairs through the complex tile (8-byte outputs)
 int fir_ols_up_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, int L, void *y_dev, hipStream_t s, int dec = 1,
                       int64_t rows_pitch = 0, int paired = 0);  // dec = M: L / M, floor(n L / M) outputs; rows_pitch > 0: y[phase * rows_pitch + i] instead of
-                                                                 // y[i L + phase]; paired: see fir_ols_up_pairs (rows then hold 8-byte pairs, L / 2 of them)
+                                                                 // y[i L + phase]; paired: see fir_ols_up_pairs in fir_route.hpp (rows then hold 8-byte pairs, L / 2 of them)
 // multirate_FIR.up, even L, tiles of the OUTPUT: the zero-stuffed tile's forward transform from its non-zero columns (fir_ols.hip: ols_rep_kernel)
-bool fir_ols_rep_supported(const FirHandle *h, int L);
 int fir_ols_rep_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, int L, void *y_dev, hipStream_t s);
 // multirate_FIR.up, one workgroup per input tile, all L phases from one forward transform (fir_up4k.hip): complex64, float32 with real
 // taps; at most 2049 taps per phase
-bool fir_up4k_supported(const FirHandle *h, int L);
 int fir_up4k_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, int L, void *y_dev, hipStream_t s);
 // the same with a 2048-point tile and ALL phases of a sample in one thread (fir_up2k.hip): at most 1025 taps per phase
-bool fir_up2k_supported(const FirHandle *h, int L);
 int fir_up2k_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, int L, void *y_dev, hipStream_t s);
 // multirate_FIR.dn, one workgroup per OUTPUT tile: M forward transforms accumulated in the frequency domain, one inverse (fir_dn4k.hip)
-bool fir_dn4k_supported(const FirHandle *h, int M);
 int fir_dn4k_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, int M, void *y_dev, hipStream_t s);
 // FFT overlap-save in float64 (fir_ols64.hip): complex128, and float64 with real taps; 2..2049 taps
-bool fir_ols64_supported(const FirHandle *h);
 int fir_ols64_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, void *y_dev, hipStream_t s, int dec = 1);
 void fir_ols64_free(Ols64Plan *p);
-bool fir_ols64_up_supported(const FirHandle *h, int L);
-bool fir_ols64_up_pairs(const FirHandle *h, int L, int dec, const void *y_dev);
 int fir_ols64_up_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, int L, void *y_dev, hipStream_t s, int dec = 1, int64_t rows_pitch = 0, int paired = 0);
 
 // ---- FIR bank (fir_bank.hip): B frequency-shifted copies of one FIR over ONE input, sigsys.fft_caf (sigsys.py:2696-2781) --------------

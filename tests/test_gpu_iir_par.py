@@ -739,7 +739,7 @@ def test_fir_from_rest_shorter_than_the_filter_runs_on_the_taps_it_reaches():
                                     (np.float32, 2, 512), (np.float32, 16, 64), (np.complex64, 2, 512), (np.complex64, 6, 256), (np.complex64, 16, 256),
                                     (np.complex64, 8, 256), (np.float32, 4, 512)])
 def test_fir_up_default_dispatch_is_near_the_fastest_engine(dt, L, T):
-    """The cost model of fir_api.hip (fir_up_prefers_ols / fir_up_tile_ms) against a stopwatch: for the shapes of profiles/r04/fir_up.txt the engine
+    """The cost model of fir_route.hpp (fir_up_model / fir_up_tile_ms) against a stopwatch: for the shapes of profiles/r04/fir_up.txt the engine
     AUTO takes is within 12 % of the fastest of the four it chooses from -- the polyphase kernels, the walk over (tile, phase) pairs, the
     one-workgroup-per-input-tile interpolators, the output-tile interpolator (even L) -- at 2^25 outputs with a settled clock.  (Round 3 flagged such rows by hand.)"""
     import time

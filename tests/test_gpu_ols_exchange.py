@@ -8,7 +8,7 @@ an IMAGE read that moved across the barrier or the write it has to follow (the b
 behind the set-up barrier, so a table read that moved shows nowhere -- and harms nothing.  Identity with the build before this change is not
 a test's business (it needs that build): profiles/r14/README.md records the byte comparison of bench.py --dump-outputs.
 The engine note of .dn(x, 4) is "fir_ols" for the folded inverse and for the decimating store alike: that ols_fold_kernel runs rests on the
-options set here (fir_dn_fold = 1, fir_dn4k = 0) and on fir_dn_any's rule for a forced algorithm, not on the assertion.
+options set here (fir_dn_fold = 1, fir_dn4k = 0) and on fir_route_dn's rule (csrc/fir_route.hpp) for a forced algorithm, not on the assertion.
 
 Shapes: the smallest that reach an interior tile, both edge tiles and a ragged tail -- 3 V + 100 complex64 samples, 5 V + 17 float32 samples
 (two real tiles ride in one complex tile), V the outputs per tile; 300, 1024 and 4097 taps (a0 = 1, 2, 8 overlap blocks).  For .up the

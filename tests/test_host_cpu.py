@@ -180,6 +180,19 @@ def test_iir_par_plan_decisions_host_run(tmp_path):
     assert out.strip().endswith("OK"), out
 
 
+def test_fir_route_decisions_host_run(tmp_path):
+    """Compiles csrc/fir_route.hpp for the HOST (standard headers only) and runs the FIR routing decision over the whole recorded table
+    tests/fir_routes/mi355x.txt (tools/record_fir_routes.py: every call's engines as the device noted them before the decision was gathered
+    into that header, with the device's CU count): the same engines, a refusal where one was recorded, the cost model evaluated at most
+    once per routed call; and over hand-written cases for what the engine names do not show (pairs, rows and the decimating store of the
+    walk, the workspace slot of the full-rate fallback, segment lengths, heads)."""
+    exe = str(tmp_path / "fir_route_emul")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "scikit-dsp-comm_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "host", "fir_route_emul.cpp"), "-o", exe])
+    out = subprocess.run([exe, os.path.join(ROOT, "tests", "fir_routes", "mi355x.txt")], stdout=subprocess.PIPE).stdout.decode()
+    assert out.strip().endswith("OK"), out[-4000:]
+
+
 def _v32_designs():
     """tests/golden/g18_v32_designs.npz (gen_golden_v32.py): name -> (sos, {chunk length: the three detuned tones the host model ranks worst})."""
     z = np.load(os.path.join(GOLDEN, "g18_v32_designs.npz"))

@@ -1,5 +1,5 @@
 """Developer timing: multirate_FIR.filter -- the direct form (matrix-pipe kernel where it covers the shape) against overlap-save and the
-default dispatch, device-resident signals, 2^26 samples, settled clock: where the crossover of pick_fir_algo (fir_api.hip) comes from.
+default dispatch, device-resident signals, 2^26 samples, settled clock: where the crossover of pick_fir_algo (fir_route.hpp) comes from.
 Run on the GPU box: python tools/time_fir_filter.py [NTAPS ...]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
