@@ -25,6 +25,8 @@
  *     same allocation (x_dev[-n_hist..-1]).  0 = zero initial state, which is
  *     what every reference call uses (lfilter/sosfilt without zi).  The sharded
  *     path uses it for the Ntaps-1 halo received from the left neighbour.
+ *   - a "*_dev" call reads x_dev[-n_hist .. n-1] and nothing else (n_hist = 0 where the entry point takes none; one such
+ *     window per row for the rows forms): whatever lies in front of or behind it in the allocation changes no output bit.
  *   - a handle serialises its own calls.  Calls lock the SLOT they run on (a slot = one GPU binding with its stream
  *     and workspaces): caller threads all use slot 0, so their calls take turns on its stream; the worker threads of
  *     a multi-slot host call run concurrently, one per slot.  ctypes releases the GIL around each call.

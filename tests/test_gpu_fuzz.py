@@ -9,6 +9,7 @@ from scipy import signal
 
 from sk_dsp_comm_amd import _ffi, multirate_helper as mrh, sigsys as ss
 from conftest import rel_err
+from _pads import loud as _loud
 
 pytestmark = pytest.mark.gpu
 
@@ -216,7 +217,8 @@ def test_fuzz_nd_and_streaming(seed):
 @pytest.mark.parametrize("seed", range(max(NSEED // 2, 1)))
 def test_fuzz_device_views_at_odd_offsets(seed):
     """The *_dev entry points on windows of larger device buffers: element-aligned but not 16-byte-aligned inputs and outputs (the vector
-    load / store fast paths must step aside), guard words on both sides of every output must survive."""
+    load / store fast paths must step aside), guard words on both sides of every output must survive, and the loud samples on both sides
+    of the input must not show in the result."""
     rng = np.random.default_rng(5000 + seed)
     for _ in range(8):
         dt = DTYPES[rng.integers(len(DTYPES))]
@@ -234,7 +236,7 @@ def test_fuzz_device_views_at_odd_offsets(seed):
         xbuf = _ffi.DeviceArray(n + 16, dt)
         ybuf = _ffi.DeviceArray(n_out + 32, dt)
         try:
-            xbuf.write(np.concatenate([np.zeros(ox, dt), x, np.zeros(16 - ox, dt)]))
+            xbuf.write(np.concatenate([_loud(ox, dt), x, _loud(16 - ox, dt, ox)]))
             ybuf.write(np.full(n_out + 32, 7.0, dtype=dt))
             xv, yv = xbuf.window(ox, n), ybuf.window(oy, n_out)
             if rng.random() < 0.5:
@@ -286,7 +288,8 @@ def test_fuzz_fir_up_walk_forms(seed):
     """multirate_FIR.up and L / M in the frequency domain, forced (option fir_up_ols_min < 0) so that short phases and short signals take it too:
     the walk over (tile, phase) pairs in every form it has -- strided stores, rows + weave, phases in pairs for real signals (even and odd L),
     the every-M-th store -- and (M = 1) the one-workgroup-per-input-tile interpolators fir_up4k / fir_up2k in theirs, on device windows at
-    random element offsets (aligned and not), guard words around the output, history in front of the input."""
+    random element offsets (aligned and not), guard words around the output, history in front of the input, loud samples in front of
+    the history and behind the window."""
     import contextlib
     rng = np.random.default_rng(7000 + seed)
     for _ in range(10):
@@ -307,7 +310,7 @@ def test_fuzz_fir_up_walk_forms(seed):
         xbuf = _ffi.DeviceArray(n + hist + 8, dt)
         ybuf = _ffi.DeviceArray(n_out + 16, dt)
         try:
-            xbuf.write(np.concatenate([np.zeros(ox, dt), x, np.zeros(8 - ox, dt)]))
+            xbuf.write(np.concatenate([_loud(ox, dt), x, _loud(8 - ox, dt, ox)]))
             ybuf.write(np.full(n_out + 16, 7.0, dtype=dt))
             k = _ffi.FirKernel(b, _ffi.code_of(dt))
             with contextlib.ExitStack() as st:
