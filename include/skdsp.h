@@ -230,6 +230,26 @@ int skdsp_psd_dev(const void *x_dev, int64_t n, int dtype, const double *window,
                   double *S_dev);
 int skdsp_psd(const void *x, int64_t n, int dtype, const double *window, int ns, int n_fft, int64_t step, int64_t nseg, double *S);
 
+/* Viterbi decoding of rate 1/2 and 1/3 convolutional codes, bit for bit fec_conv.FECConv.viterbi_decoder (fec_conv.py:252-499): a
+ * register-exchange decoder of decision depth `depth` (1 ... 128) over the 2^(K-1) states of npoly = 2 or 3 polynomials given as strings
+ * of K = 3 ... 9 binary digits (csrc/viterbi.hip, csrc/viterbi_core.hpp).  A call takes n received values (2 or 3 per symbol) and writes
+ * one byte 0 / 1 per symbol from symbol depth - 1 on: skdsp_viterbi_out_len values.
+ *   metric 0 (hard):    xtype 0, int8 values 0 / 1; n need not be a multiple of the values per symbol (a short last symbol counts as it is)
+ *   metric 1 (soft):    xtype 1, int16 values ALREADY truncated toward zero, |value| <= 4095; levels 0 and 2^quant_level - 1, quant_level 0 ... 12
+ *   metric 2 (unquant): xtype 2, float64 values; levels 0.0 and 1.0
+ * skdsp_viterbi_decode continues from the state the handle's previous decode calls left (as the reference object does) and leaves its own;
+ * skdsp_viterbi_reset returns the handle to rest; a handle that is not at rest refuses to switch between the integer metrics and unquant.
+ * skdsp_viterbi_decode_rows decodes nrow independent rows of n values each (contiguous) from rest in one launch, nrow rows of out_len
+ * bytes, and neither reads nor writes the handle's state.  The handle is freed by skdsp_destroy. */
+int skdsp_viterbi_create(const char *const *polys, int npoly, int depth, skdsp_handle *out);
+int skdsp_viterbi_out_len(skdsp_handle h, int64_t nsym_values, int64_t *n_out);
+int skdsp_viterbi_reset(skdsp_handle h);
+int skdsp_viterbi_decode(skdsp_handle h, const void *x, int64_t n, int xtype, int metric, int quant_level, uint8_t *y);
+int skdsp_viterbi_decode_dev(skdsp_handle h, const void *x_dev, int64_t n, int xtype, int metric, int quant_level, uint8_t *y_dev);
+int skdsp_viterbi_decode_rows(skdsp_handle h, const void *x, int64_t n, int64_t nrow, int xtype, int metric, int quant_level, uint8_t *y);
+int skdsp_viterbi_decode_rows_dev(skdsp_handle h, const void *x_dev, int64_t n, int64_t nrow, int xtype, int metric, int quant_level,
+                                  uint8_t *y_dev);
+
 /* Host-pointer entry points of a float32/complex64 handle deliver y as float64/complex128 (the
  * reference's result dtype, multirate_helper.py:108 etc.): widened on the device before the copy
  * back, so y must hold twice the bytes.  Device-pointer (_dev) entry points are not affected. */

@@ -1,5 +1,5 @@
 // capi.hip -- the one-call wrappers of the extern "C" boundary of libskdsp_hip.so (see include/skdsp.h): FIR bank,
-// resamplers, Farrow resampler, Welch primitive.  The runtime is runtime.hip, the host-pointer chunk pipeline
+// resamplers, Farrow resampler, Welch primitive, Viterbi decoder.  The runtime is runtime.hip, the host-pointer chunk pipeline
 // host_pipe.hip, FIR / IIR dispatch fir_api.hip / iir_api.hip.
 #include "api_internal.hpp"
 
@@ -124,6 +124,86 @@ int skdsp_psd(const void *x, int64_t n, int dtype, const double *window, int ns,
     if ((rc = ws_reserve(1, (size_t)n_fft * sizeof(double) + 256, &S_dev))) return rc;
     if ((rc = psd_launch(x_dev, used, dtype, window, ns, n_fft, step, nseg, (double *)S_dev, ctx().stream))) return rc;
     return stage_out(S, S_dev, (size_t)n_fft * sizeof(double));
+}
+
+// ---------------------------------------------------------------- Viterbi decoder (fec_conv.FECConv.viterbi_decoder)
+int skdsp_viterbi_create(const char *const *polys, int npoly, int depth, skdsp_handle *out)
+{
+    SK_CHECK(out, SKDSP_ERR_BADARG, "viterbi_create: null out");
+    HandleBase *h = nullptr;
+    int rc = viterbi_create(polys, npoly, depth, &h);
+    if (rc) return rc;
+    *out = h;
+    return SKDSP_OK;
+}
+
+int skdsp_viterbi_out_len(skdsp_handle hh, int64_t nsym_values, int64_t *n_out)
+{
+    HandleBase *h = as_handle<HandleBase>(hh, H_VITERBI);
+    SK_CHECK(h, SKDSP_ERR_BADARG, "viterbi_out_len: not a Viterbi handle");
+    return viterbi_out_len(h, nsym_values, n_out);
+}
+
+int skdsp_viterbi_reset(skdsp_handle hh)
+{
+    HandleBase *h = as_handle<HandleBase>(hh, H_VITERBI);
+    SK_CHECK(h, SKDSP_ERR_BADARG, "viterbi_reset: not a Viterbi handle");
+    API_BEGIN;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return viterbi_reset(h, ctx().stream);
+}
+
+static int viterbi_dev(skdsp_handle hh, const void *x_dev, int64_t n, int64_t nrow, int xtype, int metric, int quant_level, uint8_t *y_dev, int stateful)
+{
+    HandleBase *h = as_handle<HandleBase>(hh, H_VITERBI);
+    SK_CHECK(h, SKDSP_ERR_BADARG, "viterbi: not a Viterbi handle");
+    int rc = viterbi_check(h, n, nrow, xtype, metric, quant_level, stateful);   // (argument errors need no device)
+    if (rc) return rc;
+    API_BEGIN;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return viterbi_launch(h, x_dev, n, nrow, xtype, metric, quant_level, y_dev, stateful, ctx().stream);
+}
+
+static int viterbi_host(skdsp_handle hh, const void *x, int64_t n, int64_t nrow, int xtype, int metric, int quant_level, uint8_t *y, int stateful)
+{
+    HandleBase *h = as_handle<HandleBase>(hh, H_VITERBI);
+    SK_CHECK(h, SKDSP_ERR_BADARG, "viterbi: not a Viterbi handle");
+    int rc = viterbi_check(h, n, nrow, xtype, metric, quant_level, stateful);
+    if (rc) return rc;
+    SK_CHECK(x, SKDSP_ERR_BADARG, "viterbi: null pointer");
+    int64_t n_out = 0;
+    if ((rc = viterbi_out_len(h, n, &n_out))) return rc;
+    SK_CHECK(y || n_out == 0, SKDSP_ERR_BADARG, "viterbi: null pointer");
+    if (!stateful && n_out == 0) return SKDSP_OK;
+    API_BEGIN;
+    std::lock_guard<std::mutex> lk(h->mu);
+    const size_t esz = xtype == 0 ? 1 : xtype == 1 ? 2 : 8;
+    void *x_dev = nullptr, *y_dev = nullptr;
+    if ((rc = stage_in(x, (size_t)n * (size_t)nrow * esz, &x_dev))) return rc;
+    if ((rc = ws_reserve(1, (size_t)n_out * (size_t)nrow + 256, &y_dev))) return rc;
+    if ((rc = viterbi_launch(h, x_dev, n, nrow, xtype, metric, quant_level, (uint8_t *)y_dev, stateful, ctx().stream))) return rc;
+    if (n_out == 0) return sync_checked();
+    return stage_out(y, y_dev, (size_t)n_out * (size_t)nrow);
+}
+
+int skdsp_viterbi_decode(skdsp_handle h, const void *x, int64_t n, int xtype, int metric, int quant_level, uint8_t *y)
+{
+    return viterbi_host(h, x, n, 1, xtype, metric, quant_level, y, 1);
+}
+
+int skdsp_viterbi_decode_dev(skdsp_handle h, const void *x_dev, int64_t n, int xtype, int metric, int quant_level, uint8_t *y_dev)
+{
+    return viterbi_dev(h, x_dev, n, 1, xtype, metric, quant_level, y_dev, 1);
+}
+
+int skdsp_viterbi_decode_rows(skdsp_handle h, const void *x, int64_t n, int64_t nrow, int xtype, int metric, int quant_level, uint8_t *y)
+{
+    return viterbi_host(h, x, n, nrow, xtype, metric, quant_level, y, 0);
+}
+
+int skdsp_viterbi_decode_rows_dev(skdsp_handle h, const void *x_dev, int64_t n, int64_t nrow, int xtype, int metric, int quant_level, uint8_t *y_dev)
+{
+    return viterbi_dev(h, x_dev, n, nrow, xtype, metric, quant_level, y_dev, 0);
 }
 
 }  // extern "C"

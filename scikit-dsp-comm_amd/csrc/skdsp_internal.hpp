@@ -140,7 +140,7 @@ inline bool dtype_valid(int dt) { return dt >= 0 && dt <= 3; }
 constexpr int64_t kHeadroomBytes = 65536;
 
 // ------------------------------------------------------------------ handles
-enum HandleKind { H_FIR = 1, H_IIR = 2, H_FIRBANK = 3 };
+enum HandleKind { H_FIR = 1, H_IIR = 2, H_FIRBANK = 3, H_VITERBI = 4 };
 
 struct HandleBase {
     int kind;
@@ -373,5 +373,14 @@ int farrow_launch(const void *x_dev, int64_t n, int dtype, double ts_old, double
 int psd_check(int64_t n, int dtype, const double *window, int ns, int n_fft, int64_t step, int64_t nseg);   // host-only: the argument rules
 int psd_launch(const void *x_dev, int64_t n, int dtype, const double *window, int ns, int n_fft, int64_t step, int64_t nseg,
                double *S_dev, hipStream_t s);
+
+// ---- Viterbi decoder (viterbi.hip): fec_conv.FECConv.viterbi_decoder (fec_conv.py:252-499); the plan and the step are viterbi_core.hpp ----
+// The handle (a HandleBase of kind H_VITERBI) owns the decoder state its stateful calls carry; skdsp_destroy frees it.
+int viterbi_create(const char *const *polys, int npoly, int depth, HandleBase **out);
+int viterbi_out_len(HandleBase *h, int64_t nval, int64_t *n_out);   // host-only
+int viterbi_reset(HandleBase *h, hipStream_t s);
+int viterbi_check(HandleBase *h, int64_t n, int64_t nrow, int xtype, int metric, int quant_level, int stateful);   // host-only: the argument rules
+int viterbi_launch(HandleBase *h, const void *x_dev, int64_t n, int64_t nrow, int xtype, int metric, int quant_level, uint8_t *y_dev, int stateful,
+                   hipStream_t s);
 
 }  // namespace skdsp

@@ -35,6 +35,8 @@ SYMBOLS = [
     "skdsp_sos_filter", "skdsp_sos_up", "skdsp_sos_dn",
     "skdsp_upsample", "skdsp_upsample_dev", "skdsp_downsample", "skdsp_downsample_dev", "skdsp_set_wide_output", "skdsp_destroy",
     "skdsp_farrow_len", "skdsp_farrow_dev", "skdsp_farrow", "skdsp_psd_dev", "skdsp_psd",
+    "skdsp_viterbi_create", "skdsp_viterbi_out_len", "skdsp_viterbi_reset", "skdsp_viterbi_decode", "skdsp_viterbi_decode_dev",
+    "skdsp_viterbi_decode_rows", "skdsp_viterbi_decode_rows_dev",
     "skdsp_dist_unique_id", "skdsp_dist_init", "skdsp_dist_shutdown", "skdsp_dist_comm_count", "skdsp_dist_barrier",
     "skdsp_dist_allreduce_max", "skdsp_dist_allreduce_sum", "skdsp_dist_sendrecv", "skdsp_dist_allgather", "skdsp_dist_halo_exchange", "skdsp_fir_filter_shard_dev",
 ]
@@ -137,6 +139,14 @@ def load():
         if hasattr(L, "skdsp_fir_bank_create"):
             L.skdsp_fir_bank_create.argtypes = [vp, ci, ci, p64, ci, ci, ci, pvp]
             L.skdsp_fir_bank_dev.argtypes = [vp, vp, i64, vp, i64]
+        if hasattr(L, "skdsp_viterbi_create"):
+            L.skdsp_viterbi_create.argtypes = [ctypes.POINTER(ctypes.c_char_p), ci, ci, pvp]
+            L.skdsp_viterbi_out_len.argtypes = [vp, i64, p64]
+            L.skdsp_viterbi_reset.argtypes = [vp]
+            L.skdsp_viterbi_decode.argtypes = [vp, vp, i64, ci, ci, ci, vp]
+            L.skdsp_viterbi_decode_dev.argtypes = [vp, vp, i64, ci, ci, ci, vp]
+            L.skdsp_viterbi_decode_rows.argtypes = [vp, vp, i64, i64, ci, ci, ci, vp]
+            L.skdsp_viterbi_decode_rows_dev.argtypes = [vp, vp, i64, i64, ci, ci, ci, vp]
         L.skdsp_dist_unique_id.argtypes = [vp]
         L.skdsp_dist_init.argtypes = [ci, ci, vp]
         L.skdsp_dist_comm_count.argtypes = [ctypes.POINTER(ci)]
@@ -595,6 +605,57 @@ class FirBank:
         if n < 0 or n > xd.n or row_stride < n or (self.nbands - 1) * row_stride + n > yd.n:
             raise ValueError("FirBank: %d rows of %d samples, %d apart, do not fit the arrays" % (self.nbands, n, row_stride))
         check(load().skdsp_fir_bank_dev(ctypes.c_void_p(self.h), ctypes.c_void_p(xd.ptr), n, ctypes.c_void_p(yd.ptr), row_stride))
+
+
+class ViterbiKernel:
+    """A device Viterbi decoder handle (csrc/viterbi.hip): rate 1/2 or 1/3, K = 3 ... 9, decision depth 1 ... 128.  The handle carries the
+    decoder state of its decode() calls; decode_rows() starts every row from rest and leaves that state alone."""
+    HARD, SOFT, UNQUANT = 0, 1, 2
+    X_DTYPE = {0: np.int8, 1: np.int16, 2: np.float64}   # hard, soft (values already truncated), unquant
+
+    def __init__(self, polys, depth):
+        L = load()
+        arr = (ctypes.c_char_p * len(polys))(*[str(g).encode() for g in polys])
+        h = ctypes.c_void_p(0)
+        check(L.skdsp_viterbi_create(arr, len(polys), int(depth), ctypes.byref(h)))
+        self.h = h.value
+        self._fin = weakref.finalize(self, _destroy, self.h)
+
+    def out_len(self, nval):
+        n = ctypes.c_int64(0)
+        check(load().skdsp_viterbi_out_len(ctypes.c_void_p(self.h), int(nval), ctypes.byref(n)))
+        return n.value
+
+    def reset(self):
+        check(load().skdsp_viterbi_reset(ctypes.c_void_p(self.h)))
+
+    def _x(self, x, metric, ndim):
+        x = np.ascontiguousarray(x, dtype=self.X_DTYPE[metric])
+        if x.ndim != ndim:
+            raise ValueError("ViterbiKernel: the received values must be %d-dimensional" % ndim)
+        return x
+
+    def decode(self, x, metric, quant_level=3):
+        """n received values -> out_len(n) bytes 0 / 1, continuing from the handle's state."""
+        x = self._x(x, metric, 1)
+        y = np.empty(self.out_len(x.size), dtype=np.uint8)
+        check(load().skdsp_viterbi_decode(ctypes.c_void_p(self.h), _ptr(x), x.size, metric, metric, int(quant_level), _ptr(y)))
+        return y
+
+    def decode_rows(self, x, metric, quant_level=3):
+        """(nrow, n) received values -> (nrow, out_len(n)) bytes, every row from rest, one launch."""
+        x = self._x(x, metric, 2)
+        nrow, n = x.shape
+        y = np.empty((nrow, self.out_len(n)), dtype=np.uint8)
+        check(load().skdsp_viterbi_decode_rows(ctypes.c_void_p(self.h), _ptr(x), n, nrow, metric, metric, int(quant_level), _ptr(y)))
+        return y
+
+    def decode_dev(self, x_ptr, n, metric, quant_level, y_ptr):
+        check(load().skdsp_viterbi_decode_dev(ctypes.c_void_p(self.h), ctypes.c_void_p(x_ptr), int(n), metric, metric, int(quant_level), ctypes.c_void_p(y_ptr)))
+
+    def decode_rows_dev(self, x_ptr, n, nrow, metric, quant_level, y_ptr):
+        check(load().skdsp_viterbi_decode_rows_dev(ctypes.c_void_p(self.h), ctypes.c_void_p(x_ptr), int(n), int(nrow), metric, metric, int(quant_level),
+                                                   ctypes.c_void_p(y_ptr)))
 
 
 class IirKernel(_HostCalls):
