@@ -113,28 +113,56 @@ __device__ __forceinline__ float4 vld(const volatile float4 *p)
     return r;
 }
 
+// Addresses of the whole-tile requests: a uniform 64-bit base, advanced on the scalar unit, and ONE 32-bit byte offset per lane (16 t for the 16-byte requests,
+// zero-extended): the scalar-base form of global_load / global_store.  The blocks of a complex tile lie 4096 bytes apart, one more than the instruction's
+// immediate offset reaches, so with a 64-bit lane pointer every request but the first had its own v_add_co_u32 / s_nop 1 / v_addc_co_u32 in front of it
+// (30 vector instructions and 15 two-cycle wait states per tile of the x prefetch alone, issued at raised priority right where the loads should leave).
+// at(d, off): the address d bytes (a constant once the caller is unrolled) behind the start plus the lane's offset.  The base moves in steps of 8192 bytes
+// (s_add_u32 / s_addc_u32) and the immediate covers [-4096, 4096) around it: one step per two blocks of a complex tile.  The empty asm keeps the base in
+// SGPRs -- left to itself hipcc folds base and lane offset back into one 64-bit lane pointer for thirteen of sixteen requests -- and takes it as an integer,
+// so the global address space is spelled out behind it (a pointer that went through an asm is a generic one: flat_load).  The zero-extension of the lane
+// offset has to stand in the basic block of the requests (instruction selection works block by block): callers make their opaque copy of t there.
+#define SK_GLOBAL_PTR(T, p) ((__attribute__((address_space(1))) T *)(p))
+struct ScalarBase {
+    uint64_t b;
+    int g = 0;   // b = start + 8192 g
+    __device__ __forceinline__ explicit ScalarBase(const void *start) : b(reinterpret_cast<uint64_t>(start)) { asm volatile("" : "+s"(b)); }
+    template <class T> __device__ __forceinline__ __attribute__((address_space(1))) T *at(int d, unsigned off)
+    {
+        const int gn = (d + 4096) >> 13;
+        if (gn != g) {
+            b += (uint64_t)(int64_t)(8192 * (gn - g));
+            asm volatile("" : "+s"(b));
+            g = gn;
+        }
+        return reinterpret_cast<__attribute__((address_space(1))) T *>(SK_GLOBAL_PTR(char, b) + off + (d - 8192 * gn));
+    }
+};
+
 // The 16 requests of an interior tile with the cache policy as a compile-time constant: blocks a < KEEP and a >= 16 - KEEP with ordinary loads, the
 // others nontemporal.  Block index AND policy are template arguments, so that each request is one load from the start: written as
 // `if (a < keep || a >= 16 - keep) nv = *src; else nv = __builtin_nontemporal_load(src);` in a loop over a -- with a run-time keep, and just the
 // same with a constant one, since the loop is unrolled later -- hipcc first merges the two loads of one address into ONE ordinary load: no x load
 // has carried the hint since round 6, whatever the option said.
-template <int KEEP, int A> __device__ __forceinline__ void load_tile_block(const v4f_t *src, cf *v)
+template <int KEEP, int A> __device__ __forceinline__ void load_tile_block(ScalarBase &xb, unsigned off, cf *v)
 {
+    const __attribute__((address_space(1))) v4f_t *src = xb.at<const v4f_t>(A * 4096, off);
     v4f_t nv;
-    if constexpr (A < KEEP || A >= 16 - KEEP) nv = src[A * 256];   // (a block a neighbouring tile reads too)
-    else nv = __builtin_nontemporal_load(src + A * 256);
+    if constexpr (A < KEEP || A >= 16 - KEEP) nv = *src;   // (a block a neighbouring tile reads too)
+    else nv = __builtin_nontemporal_load(src);
     const float4 f = make_float4(nv.x, nv.y, nv.z, nv.w);
     v[2 * A] = lo(f);
     v[2 * A + 1] = hi(f);
-    if constexpr (A < 15) load_tile_block<KEEP, A + 1>(src, v);
+    if constexpr (A < 15) load_tile_block<KEEP, A + 1>(xb, off, v);
 }
 template <int KEEP> __device__ __forceinline__ void load_tile_blocks(const cf *x0, int t, cf *v)
 {
-    // opaque copy of t: stops LICM from hoisting 16 loop-invariant 64-bit addresses (which
+    // opaque copy of t: stops LICM from hoisting the loop-invariant lane offset out of the tile loop (as 64-bit addresses they
     // were then spilled and reloaded in front of every load)
     int tt = t;
     asm volatile("" : "+v"(tt));
-    load_tile_block<KEEP, 0>(reinterpret_cast<const v4f_t *>(x0) + (unsigned)tt, v);
+    ScalarBase xb(x0);
+    load_tile_block<KEEP, 0>(xb, 16u * (unsigned)tt, v);
 }
 
 // x[in0 + 512 a + 2 t + e] -> v[2a+e]; zero outside [-n_hist, n)
@@ -214,22 +242,24 @@ template <bool DEC> __device__ __forceinline__ void store_tile(const OlsArgs &A,
         return;
     }
     if (full) {
-        // recompute the per-thread offset here: hoisted out of the tile loop it is a 64-bit VGPR pair
-        // that hipcc spills, and the scratch reload's s_waitcnt vmcnt(0) then drains the whole
-        // x(tile+1) prefetch in front of the stores (vmcnt retires in order)
-        int tt = t;
-        asm volatile("" : "+v"(tt));
-        float4 *yp = reinterpret_cast<float4 *>(A.y + out0 + 2 * tt);
+        cf *y0 = A.y + out0;   // (uniform)
         // one copy of the 16 - a0 stores per possible a0 (compile-time offsets and no predicates): with a run-time a0 hipcc
         // hoisted sixteen (64-bit exec mask, 64-bit offset) pairs out of the tile loop -- 96 SGPRs, parked in VGPR lanes
         // and fetched back with 139 v_readlane per tile
         auto stores = [&](auto a0c) __attribute__((always_inline)) {
             constexpr int A0 = decltype(a0c)::value;
+            // addresses: ScalarBase, as for the loads.  The lane offset is recomputed here, from an opaque copy of t in every copy of the stores (where its
+            // zero-extension has to stand): hoisted out of the tile loop as a 64-bit VGPR pair hipcc spilled it, and the scratch reload's s_waitcnt vmcnt(0)
+            // then drained the whole x(tile+1) prefetch in front of the stores (vmcnt retires in order)
+            int tt = t;
+            asm volatile("" : "+v"(tt));
+            const unsigned off = 16u * (unsigned)tt;
+            ScalarBase yb(y0);
 #pragma unroll
             for (int a = A0; a < 16; ++a) {
                 v4f_t nv;
                 nv.x = v[2 * a].x; nv.y = v[2 * a].y; nv.z = v[2 * a + 1].x; nv.w = v[2 * a + 1].y;
-                __builtin_nontemporal_store(nv, reinterpret_cast<v4f_t *>(yp) + (a - A0) * 256);
+                __builtin_nontemporal_store(nv, yb.at<v4f_t>((a - A0) * 4096, off));
             }
         };
         switch (A.a0) {
@@ -272,12 +302,14 @@ __device__ __forceinline__ void load_tile_real(const OlsArgs &A, int64_t pair, i
     if (interior) {
         int tt = t;
         asm volatile("" : "+v"(tt));
+        const unsigned off = 8u * (unsigned)tt;   // (addresses: ScalarBase, one base per tile of the pair)
+        ScalarBase xa(xr + inA), xb(xr + inB);
 #pragma unroll
         for (int a = 0; a < 16; ++a) {
             // v[2a] = the (column 0, column 1) pair of tile A, v[2a+1] of tile B: exactly what fwd_pass1_real takes
             // (structure of arrays; ols_core.hpp) -- the loaded registers are used where they land
-            const v2f_t ra = __builtin_nontemporal_load(reinterpret_cast<const v2f_t *>(xr + inA) + (unsigned)(a * 256 + tt));
-            const v2f_t rb = __builtin_nontemporal_load(reinterpret_cast<const v2f_t *>(xr + inB) + (unsigned)(a * 256 + tt));
+            const v2f_t ra = __builtin_nontemporal_load(xa.at<const v2f_t>(a * 2048, off));
+            const v2f_t rb = __builtin_nontemporal_load(xb.at<const v2f_t>(a * 2048, off));
             v[2 * a] = make_float2(ra.x, ra.y);
             v[2 * a + 1] = make_float2(rb.x, rb.y);
         }
@@ -334,10 +366,12 @@ template <bool DEC> __device__ __forceinline__ void store_tile_real(const OlsArg
         return;
     }
     if (full) {
-        int tt = t;  // (opaque copy: keeps the 28 store addresses from being hoisted out of the tile loop and spilled)
-        asm volatile("" : "+v"(tt));
         auto stores = [&](auto a0c) __attribute__((always_inline)) {   // (one copy per a0: see store_tile)
             constexpr int A0 = decltype(a0c)::value;
+            int tt = t;  // (opaque copy, in every copy of the stores: see store_tile)
+            asm volatile("" : "+v"(tt));
+            const unsigned off = 8u * (unsigned)tt;
+            ScalarBase ya(yr + outA), yb(yr + outB);
 #pragma unroll
             for (int a = A0; a < 16; ++a) {
                 // v[2a] = (A, B) of column 0, v[2a+1] = (A, B) of column 1: ONE register swap turns the two pairs into
@@ -347,8 +381,8 @@ template <bool DEC> __device__ __forceinline__ void store_tile_real(const OlsArg
                 v2f_t ra, rb;
                 ra.x = a0; ra.y = b0;   // (b0 now holds A of column 1)
                 rb.x = a1; rb.y = b1;   // (a1 now holds B of column 0)
-                __builtin_nontemporal_store(ra, reinterpret_cast<v2f_t *>(yr + outA + 2 * tt) + (a - A0) * 256);
-                __builtin_nontemporal_store(rb, reinterpret_cast<v2f_t *>(yr + outB + 2 * tt) + (a - A0) * 256);
+                __builtin_nontemporal_store(ra, ya.at<v2f_t>((a - A0) * 2048, off));
+                __builtin_nontemporal_store(rb, yb.at<v2f_t>((a - A0) * 2048, off));
             }
         };
         switch (A.a0) {
@@ -391,9 +425,12 @@ __device__ __forceinline__ void load_tile_xr(const OlsArgs &A, int64_t tile, int
     int tt = t;
     asm volatile("" : "+v"(tt));
     if (interior) {
+        asm volatile("" : "+v"(tt));   // (addresses: ScalarBase; the lane offset is formed in this block)
+        const unsigned off = 8u * (unsigned)tt;
+        ScalarBase xb(xr + in0);
 #pragma unroll
         for (int a = 0; a < 16; ++a) {
-            const v2f_t r = __builtin_nontemporal_load(reinterpret_cast<const v2f_t *>(xr + in0) + (unsigned)(a * 256 + tt));
+            const v2f_t r = __builtin_nontemporal_load(xb.at<const v2f_t>(a * 2048, off));
             v[2 * a] = make_float2(r.x, 0.f);
             v[2 * a + 1] = make_float2(r.y, 0.f);
         }
@@ -602,11 +639,13 @@ __global__ __launch_bounds__(256, 2) void ols_tile_kernel(OlsArgs A)
     // (sharded launches walk tile 0 last: walk index w stands for tile w + 1, the last index for tile 0)
     const bool t0_last = A.halo_flag != nullptr;
     // .up: pair w = (input tile w / up, phase w % up); w < 2^31 (checked at launch), so 32-bit divisions
+    // (readfirstlane: hipcc divides on the vector unit, and the quotient of two uniform values has to be in an SGPR where a tile's base address is
+    // handed to ScalarBase)
     auto phys = [&](int64_t w) -> int64_t {
-        if (UP) return (int64_t)((unsigned)w / (unsigned)A.up);
+        if (UP) return (int64_t)__builtin_amdgcn_readfirstlane((unsigned)w / (unsigned)A.up);
         return t0_last ? (w + 1 < A.ntiles ? w + 1 : 0) : w;
     };
-    auto phase_of = [&](int64_t w) -> int { return (int)((unsigned)w % (unsigned)A.up); };
+    auto phase_of = [&](int64_t w) -> int { return (int)__builtin_amdgcn_readfirstlane((unsigned)w % (unsigned)A.up); };
     if (!UP) load_H(t, A.Hp, hh);
     cf v[32];
     if (tile < A.ntiles) {
@@ -880,15 +919,20 @@ __device__ __forceinline__ void load_rep(const OlsArgs &A, int64_t tile, int t, 
     int tt = j0;   // (opaque copy: the addresses are rebuilt per tile instead of living in registers across the tile loop)
     asm volatile("" : "+v"(tt));
     if (interior) {
+        asm volatile("" : "+v"(tt));   // (addresses: ScalarBase; the lane offset is formed in this block)
         if (REAL) {
-            const float *xa = reinterpret_cast<const float *>(A.x) + e0, *xb = xa + VD;
+            const float *xr = reinterpret_cast<const float *>(A.x) + e0;
+            const unsigned off = 4u * (unsigned)tt;
+            ScalarBase xa(xr), xb(xr + VD);
 #pragma unroll
-            for (int a = 0; a < 16; ++a) in[a] = make_float2(__builtin_nontemporal_load(xa + (unsigned)(JA * a + tt)), __builtin_nontemporal_load(xb + (unsigned)(JA * a + tt)));
+            for (int a = 0; a < 16; ++a)
+                in[a] = make_float2(__builtin_nontemporal_load(xa.at<const float>(JA * 4 * a, off)), __builtin_nontemporal_load(xb.at<const float>(JA * 4 * a, off)));
         } else {
-            const v2f_t *xc = reinterpret_cast<const v2f_t *>(A.x) + e0;
+            const unsigned off = 8u * (unsigned)tt;
+            ScalarBase xc(A.x + e0);
 #pragma unroll
             for (int a = 0; a < 16; ++a) {
-                const v2f_t r = __builtin_nontemporal_load(xc + (unsigned)(JA * a + tt));
+                const v2f_t r = __builtin_nontemporal_load(xc.at<const v2f_t>(JA * 8 * a, off));
                 in[a] = make_float2(r.x, r.y);
             }
         }

@@ -364,13 +364,37 @@ template <int K, bool INV> SK_HD cf mul_w8192(cf a)
     // cos/sin(2 pi k / 8192), k = 0..15
     constexpr float C[16] = {1.0f, 0.99999970586288223f, 0.99999882345170188f, 0.99999735276697821f, 0.99999529380957619f, 0.99999264658070719f, 0.9999894110819284f, 0.9999855873151432f, 0.99998117528260111f, 0.99997617498689761f, 0.99997058643097414f, 0.99996440961811828f, 0.9999576445519639f, 0.99995029123649048f, 0.99994234967602391f, 0.999933819875236f};
     constexpr float S[16] = {0.0f, 0.00076699031874270449f, 0.0015339801862847655f, 0.002300969151425805f, 0.0030679567629659761f, 0.0038349425697062275f, 0.0046019261204485705f, 0.0053689069639963425f, 0.0061358846491544753f, 0.0069028587247297558f, 0.007669828739531097f, 0.0084367942423697988f, 0.0092037547820598194f, 0.0099707099074180308f, 0.010737659167264491f, 0.011504602110422714f};
-    // plain scalar arithmetic on purpose: the 15 (cos, sin) pairs then travel as 32-bit LITERALS of v_mul_f32 / v_fmamk_f32
-    // (4 instructions per product) instead of as 30 more loop-invariant SGPRs next to the DFT twiddles -- with them the
-    // kernel needed ~130 SGPRs, hipcc parked the surplus in VGPR lanes and paid two v_readlane per use of ANY spilled
-    // constant (208 per tile).
     if constexpr (K == 0) return a;
+#if defined(__HIP_DEVICE_COMPILE__)
+    // One packed product (v_pk_mul_f32 + v_pk_fma_f32, as cmul_k) whose constants live for the length of the statement only: each of the two
+    // instructions needs ONE of them, broadcast to both halves, so an s_mov of the literal into a scalar temporary stands in front of each.  Nothing
+    // is live across the statement: held as 15 (cos, sin) SGPR pairs next to the DFT twiddles the constants took the kernel to ~130 SGPRs, hipcc
+    // parked the surplus in VGPR lanes and paid two v_readlane per use of ANY spilled constant (208 per tile); written as plain scalar arithmetic
+    // they travelled as literals of v_mul_f32 / v_fmac_f32 at four instructions per product (120 per tile for the two passes).  Operand order:
+    // the sine products are the v_pk_mul, the cosine products the fused add, (a.y s, a.x s) then (a.x c + lo, a.y c - hi) forward and
+    // (a.x c - lo, a.y c + hi) inverse -- the order hipcc had given the scalar form, so that every result keeps its bits.
+    else {
+        constexpr unsigned cb = __builtin_bit_cast(unsigned, C[K]), sb = __builtin_bit_cast(unsigned, S[K]);
+        v2f r;
+        unsigned long long k;
+        if constexpr (INV)
+            asm("s_mov_b64 %1, %4\n\t"
+                "v_pk_mul_f32 %0, %2, %1 op_sel:[1,0] op_sel_hi:[0,0]\n\t"
+                "s_mov_b64 %1, %3\n\t"
+                "v_pk_fma_f32 %0, %2, %1, %0 op_sel_hi:[1,0,1] neg_lo:[0,0,1]"
+                : "=&v"(r), "=&s"(k) : "v"(V(a)), "i"(cb), "i"(sb));
+        else
+            asm("s_mov_b64 %1, %4\n\t"
+                "v_pk_mul_f32 %0, %2, %1 op_sel:[1,0] op_sel_hi:[0,0]\n\t"
+                "s_mov_b64 %1, %3\n\t"
+                "v_pk_fma_f32 %0, %2, %1, %0 op_sel_hi:[1,0,1] neg_hi:[0,0,1]"
+                : "=&v"(r), "=&s"(k) : "v"(V(a)), "i"(cb), "i"(sb));
+        return make_float2(r.x, r.y);
+    }
+#else
     else if constexpr (INV) return make_float2(a.x * C[K] - a.y * S[K], a.y * C[K] + a.x * S[K]);
     else return make_float2(a.x * C[K] + a.y * S[K], a.y * C[K] - a.x * S[K]);
+#endif
 }
 
 // pass 1 + twiddle + exchange-1 write.  thread t = 16 b + q.
