@@ -250,6 +250,19 @@ int skdsp_viterbi_decode_rows(skdsp_handle h, const void *x, int64_t n, int64_t 
 int skdsp_viterbi_decode_rows_dev(skdsp_handle h, const void *x_dev, int64_t n, int64_t nrow, int xtype, int metric, int quant_level,
                                   uint8_t *y_dev);
 
+/* Single-error-correcting block codes with n = 2^j - 1, k = n - j, j = 3 ... 16, bit for bit fec_block.FECHamming and fec_block.FECCyclic
+ * (fec_block.py:61-423), as three tables of j-bit words (csrc/blockcode.hip, csrc/blockcode_core.hpp):
+ *   encode:  p = XOR over { i < k : x[i] = 1 } of enc[i];  code word = x[0..k) followed by bits j-1 ... 0 of p
+ *   decode:  s = XOR over { i < n : c[i] = 1 } of syn[i];  out[i] = c[i] ^ (s == trap[i]),  i < k
+ * One byte 0 / 1 per bit on both sides: encode takes nblocks * k bytes and writes nblocks * n, decode the reverse; nblocks = 0 is a no-op.
+ * The _dev pointers may have any byte alignment; nothing outside the two byte ranges is read or written.  One launch per call.  The handle
+ * is freed by skdsp_destroy. */
+int skdsp_blockcode_create(int n, int k, const uint32_t *enc /*k*/, const uint32_t *syn /*n*/, const uint32_t *trap /*k*/, skdsp_handle *out);
+int skdsp_blockcode_encode(skdsp_handle h, const uint8_t *bits, int64_t nblocks, uint8_t *code);
+int skdsp_blockcode_encode_dev(skdsp_handle h, const uint8_t *bits_dev, int64_t nblocks, uint8_t *code_dev);
+int skdsp_blockcode_decode(skdsp_handle h, const uint8_t *code, int64_t nblocks, uint8_t *bits);
+int skdsp_blockcode_decode_dev(skdsp_handle h, const uint8_t *code_dev, int64_t nblocks, uint8_t *bits_dev);
+
 /* Host-pointer entry points of a float32/complex64 handle deliver y as float64/complex128 (the
  * reference's result dtype, multirate_helper.py:108 etc.): widened on the device before the copy
  * back, so y must hold twice the bytes.  Device-pointer (_dev) entry points are not affected. */

@@ -1,5 +1,5 @@
 // capi.hip -- the one-call wrappers of the extern "C" boundary of libskdsp_hip.so (see include/skdsp.h): FIR bank,
-// resamplers, Farrow resampler, Welch primitive, Viterbi decoder.  The runtime is runtime.hip, the host-pointer chunk pipeline
+// resamplers, Farrow resampler, Welch primitive, Viterbi decoder, block codes.  The runtime is runtime.hip, the host-pointer chunk pipeline
 // host_pipe.hip, FIR / IIR dispatch fir_api.hip / iir_api.hip.
 #include "api_internal.hpp"
 
@@ -205,5 +205,52 @@ int skdsp_viterbi_decode_rows_dev(skdsp_handle h, const void *x_dev, int64_t n, 
 {
     return viterbi_dev(h, x_dev, n, nrow, xtype, metric, quant_level, y_dev, 0);
 }
+
+// ---------------------------------------------------------------- block codes (fec_block.FECHamming, fec_block.FECCyclic)
+int skdsp_blockcode_create(int n, int k, const uint32_t *enc, const uint32_t *syn, const uint32_t *trap, skdsp_handle *out)
+{
+    SK_CHECK(out, SKDSP_ERR_BADARG, "blockcode_create: null out");
+    HandleBase *h = nullptr;
+    int rc = blockcode_create(n, k, enc, syn, trap, &h);
+    if (rc) return rc;
+    *out = h;
+    return SKDSP_OK;
+}
+
+static int blockcode_dev(skdsp_handle hh, int mode, const uint8_t *in_dev, int64_t nblocks, uint8_t *out_dev)
+{
+    HandleBase *h = as_handle<HandleBase>(hh, H_BLOCKCODE);
+    SK_CHECK(h, SKDSP_ERR_BADARG, "blockcode: not a block code handle");
+    int rc = blockcode_check(h, nblocks);   // (argument errors need no device)
+    if (rc || nblocks == 0) return rc;
+    SK_CHECK(in_dev && out_dev, SKDSP_ERR_BADARG, "blockcode: null pointer");
+    API_BEGIN;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return blockcode_launch(h, mode, in_dev, nblocks, out_dev, ctx().stream);
+}
+
+static int blockcode_host(skdsp_handle hh, int mode, const uint8_t *in, int64_t nblocks, uint8_t *out)
+{
+    HandleBase *h = as_handle<HandleBase>(hh, H_BLOCKCODE);
+    SK_CHECK(h, SKDSP_ERR_BADARG, "blockcode: not a block code handle");
+    int rc = blockcode_check(h, nblocks);
+    if (rc || nblocks == 0) return rc;
+    SK_CHECK(in && out, SKDSP_ERR_BADARG, "blockcode: null pointer");
+    API_BEGIN;
+    std::lock_guard<std::mutex> lk(h->mu);
+    int n = 0, k = 0;
+    blockcode_sizes(h, &n, &k);
+    const size_t bytes_in = (size_t)nblocks * (size_t)(mode == 0 ? k : n), bytes_out = (size_t)nblocks * (size_t)(mode == 0 ? n : k);
+    void *in_dev = nullptr, *out_dev = nullptr;
+    if ((rc = stage_in(in, bytes_in, &in_dev))) return rc;
+    if ((rc = ws_reserve(1, bytes_out + 256, &out_dev))) return rc;
+    if ((rc = blockcode_launch(h, mode, (const uint8_t *)in_dev, nblocks, (uint8_t *)out_dev, ctx().stream))) return rc;
+    return stage_out(out, out_dev, bytes_out);
+}
+
+int skdsp_blockcode_encode(skdsp_handle h, const uint8_t *bits, int64_t nblocks, uint8_t *code) { return blockcode_host(h, 0, bits, nblocks, code); }
+int skdsp_blockcode_encode_dev(skdsp_handle h, const uint8_t *bits_dev, int64_t nblocks, uint8_t *code_dev) { return blockcode_dev(h, 0, bits_dev, nblocks, code_dev); }
+int skdsp_blockcode_decode(skdsp_handle h, const uint8_t *code, int64_t nblocks, uint8_t *bits) { return blockcode_host(h, 1, code, nblocks, bits); }
+int skdsp_blockcode_decode_dev(skdsp_handle h, const uint8_t *code_dev, int64_t nblocks, uint8_t *bits_dev) { return blockcode_dev(h, 1, code_dev, nblocks, bits_dev); }
 
 }  // extern "C"

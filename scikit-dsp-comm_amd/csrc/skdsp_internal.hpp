@@ -140,7 +140,7 @@ inline bool dtype_valid(int dt) { return dt >= 0 && dt <= 3; }
 constexpr int64_t kHeadroomBytes = 65536;
 
 // ------------------------------------------------------------------ handles
-enum HandleKind { H_FIR = 1, H_IIR = 2, H_FIRBANK = 3, H_VITERBI = 4 };
+enum HandleKind { H_FIR = 1, H_IIR = 2, H_FIRBANK = 3, H_VITERBI = 4, H_BLOCKCODE = 5 };
 
 struct HandleBase {
     int kind;
@@ -382,5 +382,12 @@ int viterbi_reset(HandleBase *h, hipStream_t s);
 int viterbi_check(HandleBase *h, int64_t n, int64_t nrow, int xtype, int metric, int quant_level, int stateful);   // host-only: the argument rules
 int viterbi_launch(HandleBase *h, const void *x_dev, int64_t n, int64_t nrow, int xtype, int metric, int quant_level, uint8_t *y_dev, int stateful,
                    hipStream_t s);
+
+// ---- block codes (blockcode.hip): fec_block.FECHamming / FECCyclic (fec_block.py:61-423); the plan and the per-block functions are blockcode_core.hpp ----
+// The handle (a HandleBase of kind H_BLOCKCODE) owns the code's three device tables; skdsp_destroy frees it.
+int blockcode_create(int n, int k, const uint32_t *enc, const uint32_t *syn, const uint32_t *trap, HandleBase **out);
+void blockcode_sizes(HandleBase *h, int *n, int *k);   // host-only
+int blockcode_check(HandleBase *h, int64_t nblocks);   // host-only: the argument rules
+int blockcode_launch(HandleBase *h, int mode, const uint8_t *in_dev, int64_t nblocks, uint8_t *out_dev, hipStream_t s);   // mode 0 encode, 1 decode
 
 }  // namespace skdsp

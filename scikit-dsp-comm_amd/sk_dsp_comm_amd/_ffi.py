@@ -37,6 +37,7 @@ SYMBOLS = [
     "skdsp_farrow_len", "skdsp_farrow_dev", "skdsp_farrow", "skdsp_psd_dev", "skdsp_psd",
     "skdsp_viterbi_create", "skdsp_viterbi_out_len", "skdsp_viterbi_reset", "skdsp_viterbi_decode", "skdsp_viterbi_decode_dev",
     "skdsp_viterbi_decode_rows", "skdsp_viterbi_decode_rows_dev",
+    "skdsp_blockcode_create", "skdsp_blockcode_encode", "skdsp_blockcode_encode_dev", "skdsp_blockcode_decode", "skdsp_blockcode_decode_dev",
     "skdsp_dist_unique_id", "skdsp_dist_init", "skdsp_dist_shutdown", "skdsp_dist_comm_count", "skdsp_dist_barrier",
     "skdsp_dist_allreduce_max", "skdsp_dist_allreduce_sum", "skdsp_dist_sendrecv", "skdsp_dist_allgather", "skdsp_dist_halo_exchange", "skdsp_fir_filter_shard_dev",
 ]
@@ -147,6 +148,10 @@ def load():
             L.skdsp_viterbi_decode_dev.argtypes = [vp, vp, i64, ci, ci, ci, vp]
             L.skdsp_viterbi_decode_rows.argtypes = [vp, vp, i64, i64, ci, ci, ci, vp]
             L.skdsp_viterbi_decode_rows_dev.argtypes = [vp, vp, i64, i64, ci, ci, ci, vp]
+        if hasattr(L, "skdsp_blockcode_create"):
+            L.skdsp_blockcode_create.argtypes = [ci, ci, vp, vp, vp, pvp]
+            for name in ("encode", "encode_dev", "decode", "decode_dev"):
+                getattr(L, "skdsp_blockcode_" + name).argtypes = [vp, vp, i64, vp]
         L.skdsp_dist_unique_id.argtypes = [vp]
         L.skdsp_dist_init.argtypes = [ci, ci, vp]
         L.skdsp_dist_comm_count.argtypes = [ctypes.POINTER(ci)]
@@ -331,6 +336,34 @@ class DeviceArray:
     def fill_noise(self, seed, first_index=0):
         check(load().skdsp_fill_noise_dev(ctypes.c_void_p(self.ptr), self.n, self.code, int(seed), int(first_index)))
         return self
+
+    def free(self):
+        self._fin()
+
+
+class DeviceBytes:
+    """nbytes of HBM addressed by the byte (the bit streams of BlockCodeKernel's *_dev calls, at any alignment): ptr is 256-byte aligned."""
+
+    def __init__(self, nbytes):
+        self.nbytes = int(nbytes)
+        base = ctypes.c_void_p(0)
+        check(load().skdsp_malloc(ctypes.byref(base), self.nbytes))
+        self.ptr = base.value
+        self._fin = weakref.finalize(self, _free_dev, self.ptr)
+
+    def write(self, a, at=0):
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        if at < 0 or at + a.size > self.nbytes:
+            raise ValueError("write outside the device bytes")
+        check(load().skdsp_memcpy_h2d(ctypes.c_void_p(self.ptr + int(at)), _ptr(a), a.nbytes))
+
+    def read(self, at=0, count=None):
+        count = self.nbytes - int(at) if count is None else int(count)
+        if at < 0 or at + count > self.nbytes:
+            raise ValueError("read outside the device bytes")
+        out = np.empty(count, dtype=np.uint8)
+        check(load().skdsp_memcpy_d2h(_ptr(out), ctypes.c_void_p(self.ptr + int(at)), out.nbytes))
+        return out
 
     def free(self):
         self._fin()
@@ -656,6 +689,43 @@ class ViterbiKernel:
     def decode_rows_dev(self, x_ptr, n, nrow, metric, quant_level, y_ptr):
         check(load().skdsp_viterbi_decode_rows_dev(ctypes.c_void_p(self.h), ctypes.c_void_p(x_ptr), int(n), int(nrow), metric, metric, int(quant_level),
                                                    ctypes.c_void_p(y_ptr)))
+
+
+class BlockCodeKernel:
+    """A device block-code handle (csrc/blockcode.hip): n = 2^j - 1, k = n - j, j = 3 ... 16, the code given as its three tables of j-bit
+    words (fec_block.py: the table form).  Bits are bytes 0 / 1 on both sides; every call is one launch."""
+
+    def __init__(self, n, k, enc, syn, trap):
+        self.n, self.k = int(n), int(k)
+        enc, syn, trap = (np.ascontiguousarray(t, dtype=np.uint32) for t in (enc, syn, trap))
+        if enc.shape != (self.k,) or syn.shape != (self.n,) or trap.shape != (self.k,):
+            raise ValueError("BlockCodeKernel: the tables hold k, n and k words")
+        h = ctypes.c_void_p(0)
+        check(load().skdsp_blockcode_create(self.n, self.k, _ptr(enc), _ptr(syn), _ptr(trap), ctypes.byref(h)))
+        self.h = h.value
+        self._fin = weakref.finalize(self, _destroy, self.h)
+
+    def _run(self, fn, x, per_in, per_out):
+        x = np.ascontiguousarray(x, dtype=np.uint8)
+        if x.ndim != 2 or x.shape[1] != per_in:
+            raise ValueError("BlockCodeKernel: the bits must be (nblocks, %d) bytes" % per_in)
+        y = np.empty((x.shape[0], per_out), dtype=np.uint8)
+        check(fn(ctypes.c_void_p(self.h), _ptr(x), x.shape[0], _ptr(y)))
+        return y
+
+    def encode(self, bits):
+        """(nblocks, k) bytes 0 / 1 -> (nblocks, n) bytes"""
+        return self._run(load().skdsp_blockcode_encode, bits, self.k, self.n)
+
+    def decode(self, code):
+        """(nblocks, n) bytes 0 / 1 -> (nblocks, k) bytes"""
+        return self._run(load().skdsp_blockcode_decode, code, self.n, self.k)
+
+    def encode_dev(self, bits_ptr, nblocks, code_ptr):
+        check(load().skdsp_blockcode_encode_dev(ctypes.c_void_p(self.h), ctypes.c_void_p(bits_ptr), int(nblocks), ctypes.c_void_p(code_ptr)))
+
+    def decode_dev(self, code_ptr, nblocks, bits_ptr):
+        check(load().skdsp_blockcode_decode_dev(ctypes.c_void_p(self.h), ctypes.c_void_p(code_ptr), int(nblocks), ctypes.c_void_p(bits_ptr)))
 
 
 class IirKernel(_HostCalls):
