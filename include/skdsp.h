@@ -263,6 +263,35 @@ int skdsp_blockcode_encode_dev(skdsp_handle h, const uint8_t *bits_dev, int64_t 
 int skdsp_blockcode_decode(skdsp_handle h, const uint8_t *code, int64_t nblocks, uint8_t *bits);
 int skdsp_blockcode_decode_dev(skdsp_handle h, const uint8_t *code_dev, int64_t nblocks, uint8_t *bits_dev);
 
+/* The FEC chain around the Viterbi decoder (csrc/convcode.hip, csrc/convcode_core.hpp): fec_conv.FECConv.conv_encoder, puncture and
+ * depuncture (fec_conv.py:501-712) over the rows of a frame set, and the count behind digitalcom.bit_errors (digitalcom.py:353-415).
+ * Bits are bytes 0 / 1.  The _dev pointers may have any byte alignment (puncture / depuncture: the element's); nothing outside a row's
+ * own bytes is read or written; n = 0 and nrow = 0 are valid and launch nothing.
+ *   encode_rows:  nrow rows of n bits -> nrow rows of R n code bits [G1 G2 (G3)] per input bit, the polynomials as for skdsp_viterbi_create
+ *                 (the same masks, the reference's rate-1/2 rule included).  A state is one byte: the reference's state string of K - 1
+ *                 digits (newest first) read as a binary number.  nstates_in = 0 (rest), 1 (one for all rows) or nrow; states_out (nrow
+ *                 bytes, may be null) receives each row's final state.  In the _dev form both state arrays are device pointers.
+ *   puncture_rows / depuncture_rows:  rows of n elements of elem_bytes = 1, 2, 4 or 8; digit k of a pattern string is bit k of its mask,
+ *                 L_pp <= 64 digits, both masks with the same number of ones; the reference's truncation rule per row
+ *                 (skdsp_puncture_out_len / skdsp_depuncture_out_len).  erase: HOST pointer to one element, already in the element type.
+ *   bit_count_rows:  counts[r] = the number of i < n with tx[r tx_stride + i] != rx[r rx_stride + i] (invert: with ==), int64; strides
+ *                 in bytes, start offsets folded into the pointers; exact and identical from run to run. */
+int skdsp_convcode_create(const char *const *polys, int npoly, skdsp_handle *out);
+int skdsp_convcode_encode_rows(skdsp_handle h, const uint8_t *bits, int64_t n, int64_t nrow, const uint8_t *states_in, int64_t nstates_in, uint8_t *code,
+                               uint8_t *states_out);
+int skdsp_convcode_encode_rows_dev(skdsp_handle h, const uint8_t *bits_dev, int64_t n, int64_t nrow, const uint8_t *states_in_dev, int64_t nstates_in,
+                                   uint8_t *code_dev, uint8_t *states_out_dev);
+int skdsp_puncture_out_len(int64_t n, uint64_t mask1, uint64_t mask2, int L_pp, int64_t *n_out);
+int skdsp_depuncture_out_len(int64_t n, uint64_t mask1, uint64_t mask2, int L_pp, int64_t *n_out);
+int skdsp_puncture_rows(const void *x, int64_t n, int64_t nrow, int elem_bytes, uint64_t mask1, uint64_t mask2, int L_pp, void *y);
+int skdsp_puncture_rows_dev(const void *x_dev, int64_t n, int64_t nrow, int elem_bytes, uint64_t mask1, uint64_t mask2, int L_pp, void *y_dev);
+int skdsp_depuncture_rows(const void *x, int64_t n, int64_t nrow, int elem_bytes, uint64_t mask1, uint64_t mask2, int L_pp, const void *erase, void *y);
+int skdsp_depuncture_rows_dev(const void *x_dev, int64_t n, int64_t nrow, int elem_bytes, uint64_t mask1, uint64_t mask2, int L_pp, const void *erase,
+                              void *y_dev);
+int skdsp_bit_count_rows(const uint8_t *tx, int64_t tx_stride, const uint8_t *rx, int64_t rx_stride, int64_t n, int64_t nrow, int invert, int64_t *counts);
+int skdsp_bit_count_rows_dev(const uint8_t *tx_dev, int64_t tx_stride, const uint8_t *rx_dev, int64_t rx_stride, int64_t n, int64_t nrow, int invert,
+                             int64_t *counts_dev);
+
 /* Host-pointer entry points of a float32/complex64 handle deliver y as float64/complex128 (the
  * reference's result dtype, multirate_helper.py:108 etc.): widened on the device before the copy
  * back, so y must hold twice the bytes.  Device-pointer (_dev) entry points are not affected. */

@@ -1,5 +1,5 @@
 // capi.hip -- the one-call wrappers of the extern "C" boundary of libskdsp_hip.so (see include/skdsp.h): FIR bank,
-// resamplers, Farrow resampler, Welch primitive, Viterbi decoder, block codes.  The runtime is runtime.hip, the host-pointer chunk pipeline
+// resamplers, Farrow resampler, Welch primitive, Viterbi decoder, block codes, the FEC chain around the decoder.  The runtime is runtime.hip, the host-pointer chunk pipeline
 // host_pipe.hip, FIR / IIR dispatch fir_api.hip / iir_api.hip.
 #include "api_internal.hpp"
 
@@ -252,5 +252,152 @@ int skdsp_blockcode_encode(skdsp_handle h, const uint8_t *bits, int64_t nblocks,
 int skdsp_blockcode_encode_dev(skdsp_handle h, const uint8_t *bits_dev, int64_t nblocks, uint8_t *code_dev) { return blockcode_dev(h, 0, bits_dev, nblocks, code_dev); }
 int skdsp_blockcode_decode(skdsp_handle h, const uint8_t *code, int64_t nblocks, uint8_t *bits) { return blockcode_host(h, 1, code, nblocks, bits); }
 int skdsp_blockcode_decode_dev(skdsp_handle h, const uint8_t *code_dev, int64_t nblocks, uint8_t *bits_dev) { return blockcode_dev(h, 1, code_dev, nblocks, bits_dev); }
+
+// ---------------------------------------------------------------- the FEC chain around the decoder (FECConv.conv_encoder / puncture / depuncture, digitalcom.bit_errors)
+int skdsp_convcode_create(const char *const *polys, int npoly, skdsp_handle *out)
+{
+    SK_CHECK(out, SKDSP_ERR_BADARG, "convcode_create: null out");
+    HandleBase *h = nullptr;
+    int rc = convcode_create(polys, npoly, &h);
+    if (rc) return rc;
+    *out = h;
+    return SKDSP_OK;
+}
+
+int skdsp_convcode_encode_rows_dev(skdsp_handle hh, const uint8_t *bits_dev, int64_t n, int64_t nrow, const uint8_t *states_in_dev, int64_t nstates_in,
+                                   uint8_t *code_dev, uint8_t *states_out_dev)
+{
+    HandleBase *h = as_handle<HandleBase>(hh, H_CONVCODE);
+    SK_CHECK(h, SKDSP_ERR_BADARG, "convcode: not a convolutional code handle");
+    int rc = convcode_check(h, n, nrow, nstates_in);   // (argument errors need no device)
+    if (rc || nrow == 0) return rc;
+    SK_CHECK(nstates_in == 0 || states_in_dev, SKDSP_ERR_BADARG, "convcode: null initial states");
+    SK_CHECK(n == 0 || (bits_dev && code_dev), SKDSP_ERR_BADARG, "convcode: null pointer");
+    if (n == 0 && !states_out_dev) return SKDSP_OK;
+    API_BEGIN;
+    return convcode_launch(h, bits_dev, n, nrow, states_in_dev, nstates_in, code_dev, states_out_dev, ctx().stream);
+}
+
+int skdsp_convcode_encode_rows(skdsp_handle hh, const uint8_t *bits, int64_t n, int64_t nrow, const uint8_t *states_in, int64_t nstates_in, uint8_t *code,
+                               uint8_t *states_out)
+{
+    HandleBase *h = as_handle<HandleBase>(hh, H_CONVCODE);
+    SK_CHECK(h, SKDSP_ERR_BADARG, "convcode: not a convolutional code handle");
+    int rc = convcode_check(h, n, nrow, nstates_in);
+    if (rc || nrow == 0) return rc;
+    SK_CHECK(nstates_in == 0 || states_in, SKDSP_ERR_BADARG, "convcode: null initial states");
+    int K = 0, R = 0;
+    convcode_sizes(h, &K, &R);
+    for (int64_t r = 0; r < nstates_in; ++r)
+        SK_CHECK(states_in[r] < (1 << (K - 1)), SKDSP_ERR_BADARG, "convcode: state %d of row %lld does not fit the %d state bits", (int)states_in[r], (long long)r, K - 1);
+    if (n == 0) {   // nothing to encode: the states pass through
+        for (int64_t r = 0; states_out && r < nrow; ++r) states_out[r] = nstates_in == 0 ? 0 : states_in[nstates_in == 1 ? 0 : r];
+        return SKDSP_OK;
+    }
+    SK_CHECK(bits && code, SKDSP_ERR_BADARG, "convcode: null pointer");
+    API_BEGIN;
+    // workspace 0: the bits; workspace 1: the code bits, then the states in (nrow bytes) and out (nrow bytes), each from a 256-byte boundary
+    const size_t nbits = (size_t)n * (size_t)nrow, ncode = nbits * (size_t)R, st_off = round_up(ncode, 256), st_bytes = round_up((size_t)nrow, 256);
+    void *bits_dev = nullptr, *out_dev = nullptr;
+    if ((rc = stage_in(bits, nbits, &bits_dev))) return rc;
+    if ((rc = ws_reserve(1, st_off + 2 * st_bytes + 256, &out_dev))) return rc;
+    uint8_t *code_dev = (uint8_t *)out_dev, *sin_dev = code_dev + st_off, *sout_dev = sin_dev + st_bytes;
+    if (nstates_in) SK_HIP(hipMemcpyAsync(sin_dev, states_in, (size_t)nstates_in, hipMemcpyHostToDevice, ctx().stream));
+    if ((rc = convcode_launch(h, (const uint8_t *)bits_dev, n, nrow, sin_dev, nstates_in, code_dev, states_out ? sout_dev : nullptr, ctx().stream))) return rc;
+    if (states_out) SK_HIP(hipMemcpyAsync(states_out, sout_dev, (size_t)nrow, hipMemcpyDeviceToHost, ctx().stream));
+    return stage_out(code, code_dev, ncode);
+}
+
+int skdsp_puncture_out_len(int64_t n, uint64_t mask1, uint64_t mask2, int L_pp, int64_t *n_out)
+{
+    SK_CHECK(n_out, SKDSP_ERR_BADARG, "puncture_out_len: null n_out");
+    return gather_check(0, n, 0, 1, mask1, mask2, L_pp, n_out);
+}
+
+int skdsp_depuncture_out_len(int64_t n, uint64_t mask1, uint64_t mask2, int L_pp, int64_t *n_out)
+{
+    SK_CHECK(n_out, SKDSP_ERR_BADARG, "depuncture_out_len: null n_out");
+    return gather_check(1, n, 0, 1, mask1, mask2, L_pp, n_out);
+}
+
+static int gather_dev(int dep, const void *x_dev, int64_t n, int64_t nrow, int elem_bytes, uint64_t mask1, uint64_t mask2, int L_pp, const void *erase, void *y_dev)
+{
+    int64_t n_out = 0;
+    int rc = gather_check(dep, n, nrow, elem_bytes, mask1, mask2, L_pp, &n_out);   // (argument errors need no device)
+    if (rc) return rc;
+    SK_CHECK(!dep || erase, SKDSP_ERR_BADARG, "depuncture: null erase value");
+    if (nrow == 0 || n_out == 0) return SKDSP_OK;
+    SK_CHECK(x_dev && y_dev, SKDSP_ERR_BADARG, "%s: null pointer", dep ? "depuncture" : "puncture");
+    SK_CHECK(elem_aligned(x_dev, y_dev, elem_bytes), SKDSP_ERR_BADARG, "%s: the pointers must be aligned to the element", dep ? "depuncture" : "puncture");
+    API_BEGIN;
+    return gather_launch(dep, x_dev, n, nrow, elem_bytes, mask1, mask2, L_pp, erase, y_dev, ctx().stream);
+}
+
+static int gather_host(int dep, const void *x, int64_t n, int64_t nrow, int elem_bytes, uint64_t mask1, uint64_t mask2, int L_pp, const void *erase, void *y)
+{
+    int64_t n_out = 0;
+    int rc = gather_check(dep, n, nrow, elem_bytes, mask1, mask2, L_pp, &n_out);
+    if (rc) return rc;
+    SK_CHECK(!dep || erase, SKDSP_ERR_BADARG, "depuncture: null erase value");
+    if (nrow == 0 || n_out == 0) return SKDSP_OK;
+    SK_CHECK(x && y, SKDSP_ERR_BADARG, "%s: null pointer", dep ? "depuncture" : "puncture");
+    API_BEGIN;
+    const size_t bytes_in = (size_t)n * (size_t)nrow * (size_t)elem_bytes, bytes_out = (size_t)n_out * (size_t)nrow * (size_t)elem_bytes;
+    void *x_dev = nullptr, *y_dev = nullptr;
+    if ((rc = stage_in(x, bytes_in, &x_dev))) return rc;
+    if ((rc = ws_reserve(1, bytes_out + 256, &y_dev))) return rc;
+    if ((rc = gather_launch(dep, x_dev, n, nrow, elem_bytes, mask1, mask2, L_pp, erase, y_dev, ctx().stream))) return rc;
+    return stage_out(y, y_dev, bytes_out);
+}
+
+int skdsp_puncture_rows(const void *x, int64_t n, int64_t nrow, int elem_bytes, uint64_t mask1, uint64_t mask2, int L_pp, void *y)
+{
+    return gather_host(0, x, n, nrow, elem_bytes, mask1, mask2, L_pp, nullptr, y);
+}
+int skdsp_puncture_rows_dev(const void *x_dev, int64_t n, int64_t nrow, int elem_bytes, uint64_t mask1, uint64_t mask2, int L_pp, void *y_dev)
+{
+    return gather_dev(0, x_dev, n, nrow, elem_bytes, mask1, mask2, L_pp, nullptr, y_dev);
+}
+int skdsp_depuncture_rows(const void *x, int64_t n, int64_t nrow, int elem_bytes, uint64_t mask1, uint64_t mask2, int L_pp, const void *erase, void *y)
+{
+    return gather_host(1, x, n, nrow, elem_bytes, mask1, mask2, L_pp, erase, y);
+}
+int skdsp_depuncture_rows_dev(const void *x_dev, int64_t n, int64_t nrow, int elem_bytes, uint64_t mask1, uint64_t mask2, int L_pp, const void *erase, void *y_dev)
+{
+    return gather_dev(1, x_dev, n, nrow, elem_bytes, mask1, mask2, L_pp, erase, y_dev);
+}
+
+int skdsp_bit_count_rows_dev(const uint8_t *tx_dev, int64_t tx_stride, const uint8_t *rx_dev, int64_t rx_stride, int64_t n, int64_t nrow, int invert,
+                             int64_t *counts_dev)
+{
+    int rc = bitcount_check(tx_stride, rx_stride, n, nrow);   // (argument errors need no device)
+    if (rc || nrow == 0) return rc;
+    SK_CHECK(counts_dev && ((uintptr_t)counts_dev & 7) == 0, SKDSP_ERR_BADARG, "bit_count: the counts must be an 8-byte aligned pointer");
+    SK_CHECK(n == 0 || (tx_dev && rx_dev), SKDSP_ERR_BADARG, "bit_count: null pointer");
+    API_BEGIN;
+    return bitcount_launch(tx_dev, tx_stride, rx_dev, rx_stride, n, nrow, invert, counts_dev, ctx().stream);
+}
+
+// host form: both streams are copied whole -- (nrow - 1) stride + n bytes each
+int skdsp_bit_count_rows(const uint8_t *tx, int64_t tx_stride, const uint8_t *rx, int64_t rx_stride, int64_t n, int64_t nrow, int invert, int64_t *counts)
+{
+    int rc = bitcount_check(tx_stride, rx_stride, n, nrow);
+    if (rc || nrow == 0) return rc;
+    SK_CHECK(counts, SKDSP_ERR_BADARG, "bit_count: null counts");
+    if (n == 0) {
+        for (int64_t r = 0; r < nrow; ++r) counts[r] = 0;
+        return SKDSP_OK;
+    }
+    SK_CHECK(tx && rx, SKDSP_ERR_BADARG, "bit_count: null pointer");
+    API_BEGIN;
+    const size_t tx_bytes = (size_t)((nrow - 1) * tx_stride + n), rx_bytes = (size_t)((nrow - 1) * rx_stride + n), cnt_off = round_up(rx_bytes, 256);
+    void *tx_dev = nullptr, *rx_dev = nullptr;
+    if ((rc = ws_reserve(1, cnt_off + (size_t)nrow * sizeof(int64_t) + 256, &rx_dev))) return rc;
+    if ((rc = stage_in(tx, tx_bytes, &tx_dev))) return rc;
+    SK_HIP(hipMemcpyAsync(rx_dev, rx, rx_bytes, hipMemcpyHostToDevice, ctx().stream));
+    int64_t *counts_dev = reinterpret_cast<int64_t *>((char *)rx_dev + cnt_off);
+    if ((rc = bitcount_launch((const uint8_t *)tx_dev, tx_stride, (const uint8_t *)rx_dev, rx_stride, n, nrow, invert, counts_dev, ctx().stream))) return rc;
+    return stage_out(counts, counts_dev, (size_t)nrow * sizeof(int64_t));
+}
 
 }  // extern "C"

@@ -140,7 +140,7 @@ inline bool dtype_valid(int dt) { return dt >= 0 && dt <= 3; }
 constexpr int64_t kHeadroomBytes = 65536;
 
 // ------------------------------------------------------------------ handles
-enum HandleKind { H_FIR = 1, H_IIR = 2, H_FIRBANK = 3, H_VITERBI = 4, H_BLOCKCODE = 5 };
+enum HandleKind { H_FIR = 1, H_IIR = 2, H_FIRBANK = 3, H_VITERBI = 4, H_BLOCKCODE = 5, H_CONVCODE = 6 };
 
 struct HandleBase {
     int kind;
@@ -389,5 +389,19 @@ int blockcode_create(int n, int k, const uint32_t *enc, const uint32_t *syn, con
 void blockcode_sizes(HandleBase *h, int *n, int *k);   // host-only
 int blockcode_check(HandleBase *h, int64_t nblocks);   // host-only: the argument rules
 int blockcode_launch(HandleBase *h, int mode, const uint8_t *in_dev, int64_t nblocks, uint8_t *out_dev, hipStream_t s);   // mode 0 encode, 1 decode
+
+// ---- the FEC chain around the decoder (convcode.hip): conv_encoder / puncture / depuncture over rows and the count of digitalcom.bit_errors; the plans are convcode_core.hpp ----
+// The handle (a HandleBase of kind H_CONVCODE) holds the encoder's masks only (no device memory); skdsp_destroy frees it.
+int convcode_create(const char *const *polys, int npoly, HandleBase **out);   // host-only
+void convcode_sizes(HandleBase *h, int *K, int *R);                           // host-only
+int convcode_check(HandleBase *h, int64_t n, int64_t nrow, int64_t nstates_in);   // host-only: the argument rules
+int convcode_launch(HandleBase *h, const uint8_t *bits_dev, int64_t n, int64_t nrow, const uint8_t *states_in_dev, int64_t nstates_in, uint8_t *code_dev,
+                    uint8_t *states_out_dev, hipStream_t s);
+int gather_check(int depuncture, int64_t n, int64_t nrow, int elem_bytes, uint64_t mask1, uint64_t mask2, int L_pp, int64_t *n_out);   // host-only; n_out: elements per output row
+int gather_launch(int depuncture, const void *x_dev, int64_t n, int64_t nrow, int elem_bytes, uint64_t mask1, uint64_t mask2, int L_pp, const void *erase_host,
+                  void *y_dev, hipStream_t s);
+int bitcount_check(int64_t tx_stride, int64_t rx_stride, int64_t n, int64_t nrow);   // host-only
+int bitcount_launch(const uint8_t *tx_dev, int64_t tx_stride, const uint8_t *rx_dev, int64_t rx_stride, int64_t n, int64_t nrow, int invert, int64_t *counts_dev,
+                    hipStream_t s);
 
 }  // namespace skdsp

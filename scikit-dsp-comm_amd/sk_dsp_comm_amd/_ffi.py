@@ -38,6 +38,8 @@ SYMBOLS = [
     "skdsp_viterbi_create", "skdsp_viterbi_out_len", "skdsp_viterbi_reset", "skdsp_viterbi_decode", "skdsp_viterbi_decode_dev",
     "skdsp_viterbi_decode_rows", "skdsp_viterbi_decode_rows_dev",
     "skdsp_blockcode_create", "skdsp_blockcode_encode", "skdsp_blockcode_encode_dev", "skdsp_blockcode_decode", "skdsp_blockcode_decode_dev",
+    "skdsp_convcode_create", "skdsp_convcode_encode_rows", "skdsp_convcode_encode_rows_dev", "skdsp_puncture_out_len", "skdsp_depuncture_out_len",
+    "skdsp_puncture_rows", "skdsp_puncture_rows_dev", "skdsp_depuncture_rows", "skdsp_depuncture_rows_dev", "skdsp_bit_count_rows", "skdsp_bit_count_rows_dev",
     "skdsp_dist_unique_id", "skdsp_dist_init", "skdsp_dist_shutdown", "skdsp_dist_comm_count", "skdsp_dist_barrier",
     "skdsp_dist_allreduce_max", "skdsp_dist_allreduce_sum", "skdsp_dist_sendrecv", "skdsp_dist_allgather", "skdsp_dist_halo_exchange", "skdsp_fir_filter_shard_dev",
 ]
@@ -152,6 +154,14 @@ def load():
             L.skdsp_blockcode_create.argtypes = [ci, ci, vp, vp, vp, pvp]
             for name in ("encode", "encode_dev", "decode", "decode_dev"):
                 getattr(L, "skdsp_blockcode_" + name).argtypes = [vp, vp, i64, vp]
+        if hasattr(L, "skdsp_convcode_create"):
+            u64 = ctypes.c_uint64
+            L.skdsp_convcode_create.argtypes = [ctypes.POINTER(ctypes.c_char_p), ci, pvp]
+            L.skdsp_convcode_encode_rows.argtypes = L.skdsp_convcode_encode_rows_dev.argtypes = [vp, vp, i64, i64, vp, i64, vp, vp]
+            L.skdsp_puncture_out_len.argtypes = L.skdsp_depuncture_out_len.argtypes = [i64, u64, u64, ci, p64]
+            L.skdsp_puncture_rows.argtypes = L.skdsp_puncture_rows_dev.argtypes = [vp, i64, i64, ci, u64, u64, ci, vp]
+            L.skdsp_depuncture_rows.argtypes = L.skdsp_depuncture_rows_dev.argtypes = [vp, i64, i64, ci, u64, u64, ci, vp, vp]
+            L.skdsp_bit_count_rows.argtypes = L.skdsp_bit_count_rows_dev.argtypes = [vp, i64, vp, i64, i64, i64, ci, vp]
         L.skdsp_dist_unique_id.argtypes = [vp]
         L.skdsp_dist_init.argtypes = [ci, ci, vp]
         L.skdsp_dist_comm_count.argtypes = [ctypes.POINTER(ci)]
@@ -726,6 +736,130 @@ class BlockCodeKernel:
 
     def decode_dev(self, code_ptr, nblocks, bits_ptr):
         check(load().skdsp_blockcode_decode_dev(ctypes.c_void_p(self.h), ctypes.c_void_p(code_ptr), int(nblocks), ctypes.c_void_p(bits_ptr)))
+
+
+MAX_PATTERN = 64
+
+
+def pattern_masks(puncture_pattern):
+    """(mask1, mask2, L_pp) of a puncture pattern (two strings of 0 / 1): digit k is bit k.  ValueError for what the kernels do not serve --
+    more than 64 digits, unequal lengths, unequal numbers of ones (the reference cannot serve the last two either), no ones at all."""
+    if len(puncture_pattern) != 2:
+        raise ValueError("a puncture pattern is two strings of 0 / 1 (the G1 and the G2 stream)")
+    p1, p2 = (str(p) for p in puncture_pattern)
+    if set(p1 + p2) - {'0', '1'}:
+        raise ValueError("a puncture pattern is two strings of 0 / 1")
+    if len(p1) != len(p2):
+        raise ValueError("the two puncture patterns must have the same length (got %d and %d digits)" % (len(p1), len(p2)))
+    if not 1 <= len(p1) <= MAX_PATTERN:
+        raise ValueError("puncture patterns of 1 ... %d digits are served (got %d)" % (MAX_PATTERN, len(p1)))
+    if p1.count('1') != p2.count('1') or p1.count('1') == 0:
+        raise ValueError("the two puncture patterns must keep the same, non-zero number of bits (got %d and %d)" % (p1.count('1'), p2.count('1')))
+    return int(p1[::-1], 2), int(p2[::-1], 2), len(p1)
+
+
+def puncture_out_len(n, puncture_pattern, depuncture=False):
+    """Elements per output row of puncture_rows / depuncture_rows for rows of n elements: the C library's own length function."""
+    m1, m2, L_pp = pattern_masks(puncture_pattern)
+    out = ctypes.c_int64(0)
+    fn = load().skdsp_depuncture_out_len if depuncture else load().skdsp_puncture_out_len
+    check(fn(int(n), m1, m2, L_pp, ctypes.byref(out)))
+    return out.value
+
+
+def _rows2d(x, what):
+    x = np.ascontiguousarray(x)
+    if x.ndim != 2:
+        raise ValueError("%s: a 2-D array, one frame per row" % what)
+    if x.dtype.itemsize not in (1, 2, 4, 8) or x.dtype.kind not in "biuf":
+        raise ValueError("%s: elements of 1, 2, 4 or 8 bytes (got %s)" % (what, x.dtype))
+    return x
+
+
+def puncture_rows(x, puncture_pattern):
+    """(nrow, n) elements of 1, 2, 4 or 8 bytes -> (nrow, puncture_out_len(n)) of the same dtype (csrc/convcode.hip: puncture_kernel)"""
+    x = _rows2d(x, "puncture_rows")
+    m1, m2, L_pp = pattern_masks(puncture_pattern)
+    y = np.empty((x.shape[0], puncture_out_len(x.shape[1], puncture_pattern)), dtype=x.dtype)
+    check(load().skdsp_puncture_rows(_ptr(x), x.shape[1], x.shape[0], x.dtype.itemsize, m1, m2, L_pp, _ptr(y)))
+    return y
+
+
+def depuncture_rows(x, puncture_pattern, erase):
+    """(nrow, n) elements -> (nrow, depuncture_out_len(n)) of the same dtype; erase is converted to that dtype the way NumPy's astype does
+    (float -> integer: toward zero)."""
+    x = _rows2d(x, "depuncture_rows")
+    m1, m2, L_pp = pattern_masks(puncture_pattern)
+    e = np.array([erase]).astype(x.dtype)
+    y = np.empty((x.shape[0], puncture_out_len(x.shape[1], puncture_pattern, True)), dtype=x.dtype)
+    check(load().skdsp_depuncture_rows(_ptr(x), x.shape[1], x.shape[0], x.dtype.itemsize, m1, m2, L_pp, _ptr(e), _ptr(y)))
+    return y
+
+
+def puncture_rows_dev(x_ptr, n, nrow, elem_bytes, puncture_pattern, y_ptr):
+    m1, m2, L_pp = pattern_masks(puncture_pattern)
+    check(load().skdsp_puncture_rows_dev(ctypes.c_void_p(x_ptr), int(n), int(nrow), int(elem_bytes), m1, m2, L_pp, ctypes.c_void_p(y_ptr)))
+
+
+def depuncture_rows_dev(x_ptr, n, nrow, dtype, puncture_pattern, erase, y_ptr):
+    """dtype: the elements' NumPy dtype (erase is converted to it on the host)"""
+    m1, m2, L_pp = pattern_masks(puncture_pattern)
+    e = np.array([erase]).astype(dtype)
+    check(load().skdsp_depuncture_rows_dev(ctypes.c_void_p(x_ptr), int(n), int(nrow), e.dtype.itemsize, m1, m2, L_pp, _ptr(e), ctypes.c_void_p(y_ptr)))
+
+
+def bit_count_rows(tx, rx, invert=False, n=None):
+    """Two 2-D byte arrays with the same number of rows -> int64[nrow]: the positions among the first n (default: the narrower width) of
+    row r where tx and rx differ (invert: agree) (csrc/convcode.hip: bitcount_kernel)"""
+    tx, rx = np.ascontiguousarray(tx, dtype=np.uint8), np.ascontiguousarray(rx, dtype=np.uint8)
+    if tx.ndim != 2 or rx.ndim != 2 or tx.shape[0] != rx.shape[0]:
+        raise ValueError("bit_count_rows: two 2-D arrays with the same number of rows")
+    n = min(tx.shape[1], rx.shape[1]) if n is None else int(n)
+    if n < 0 or n > min(tx.shape[1], rx.shape[1]):
+        raise ValueError("bit_count_rows: n beyond a row")
+    counts = np.zeros(tx.shape[0], dtype=np.int64)
+    check(load().skdsp_bit_count_rows(_ptr(tx), tx.shape[1], _ptr(rx), rx.shape[1], n, tx.shape[0], int(bool(invert)), _ptr(counts)))
+    return counts
+
+
+def bit_count_rows_dev(tx_ptr, tx_stride, rx_ptr, rx_stride, n, nrow, invert, counts_ptr):
+    """Device pointers; the strides are bytes from row to row, a start offset is part of the pointer; counts: nrow int64, 8-byte aligned."""
+    check(load().skdsp_bit_count_rows_dev(ctypes.c_void_p(tx_ptr), int(tx_stride), ctypes.c_void_p(rx_ptr), int(rx_stride), int(n), int(nrow), int(bool(invert)),
+                                          ctypes.c_void_p(counts_ptr)))
+
+
+class ConvCodeKernel:
+    """A convolutional encoder handle (csrc/convcode.hip): rate 1/2 or 1/3, K = 3 ... 9, the polynomials read as ViterbiKernel reads them.
+    Bits are bytes 0 / 1; a state is the reference's state string (K - 1 digits, newest first) read as a binary number, one byte per row."""
+
+    def __init__(self, polys):
+        arr = (ctypes.c_char_p * len(polys))(*[str(g).encode() for g in polys])
+        h = ctypes.c_void_p(0)
+        check(load().skdsp_convcode_create(arr, len(polys), ctypes.byref(h)))
+        self.h = h.value
+        self.R, self.K = len(polys), len(str(polys[0]))
+        self._fin = weakref.finalize(self, _destroy, self.h)
+
+    def encode_rows(self, bits, states=None):
+        """(nrow, n) bytes 0 / 1, states: None (rest) or uint8[1 | nrow] -> ((nrow, R n) bytes, uint8[nrow] final states)"""
+        bits = np.ascontiguousarray(bits, dtype=np.uint8)
+        if bits.ndim != 2:
+            raise ValueError("ConvCodeKernel: the bits must be (nrow, n) bytes")
+        nrow, n = bits.shape
+        st = np.zeros(0, dtype=np.uint8) if states is None else np.ascontiguousarray(states, dtype=np.uint8).reshape(-1)
+        code, out = np.empty((nrow, self.R * n), dtype=np.uint8), np.zeros(nrow, dtype=np.uint8)
+        check(load().skdsp_convcode_encode_rows(ctypes.c_void_p(self.h), _ptr(bits), n, nrow, _ptr(st), st.size, _ptr(code), _ptr(out)))
+        return code, out
+
+    def encode_rows_dev(self, bits_ptr, n, nrow, states_in_ptr, nstates_in, code_ptr, states_out_ptr):
+        """Device pointers throughout; states_in_ptr / states_out_ptr may be 0 (rest / not wanted)."""
+        check(load().skdsp_convcode_encode_rows_dev(ctypes.c_void_p(self.h), ctypes.c_void_p(bits_ptr), int(n), int(nrow), ctypes.c_void_p(states_in_ptr or None),
+                                                    int(nstates_in), ctypes.c_void_p(code_ptr), ctypes.c_void_p(states_out_ptr or None)))
+
+    puncture_rows = staticmethod(puncture_rows)
+    puncture_rows_dev = staticmethod(puncture_rows_dev)
+    depuncture_rows = staticmethod(depuncture_rows)
+    depuncture_rows_dev = staticmethod(depuncture_rows_dev)
 
 
 class IirKernel(_HostCalls):

@@ -8,15 +8,20 @@ the GPU (sigsys.pulse_shape -> multirate_FIR.up -> fir_direct.hip / fir_ols.hip)
   qam_bb, mpsk_bb, gmsk_bb, rz_bits, time_delay (constant delay)         digitalcom.py:418-492, 613-667, 585-610, 998-1048, 1089-1131
   farrow_resample(x, fs_old, fs_new, i_ord, alpha)                       digitalcom.py:53-235
   my_psd(x, NFFT, Fs)                                                    digitalcom.py:1051-1086  (sigsys.my_psd: csrc/psd.hip)
+  bit_errors(tx_data, rx_data, n_corr, n_transient)                      digitalcom.py:353-415    (the count: csrc/convcode.hip)
 
 farrow_resample, the arbitrary-ratio resampler, is its own engine (csrc/farrow.hip): each output is a 4-tap FIR whose taps
 are polynomials in a fractional delay, evaluated on the GPU for all outputs at once (the reference loops over them in Python).
 """
 import math
+import warnings
+from logging import getLogger
 
 import numpy as np
 
 from . import _ffi, config
+
+log = getLogger(__name__)
 
 from .sigsys import upsample, downsample, cic, rc_imp, sqrt_rc_imp, pulse_shape, _pulse  # noqa: F401  (re-exported like digitalcom.py:40-47)
 
@@ -242,3 +247,130 @@ def time_delay(x, d, n=4):
     w0 = np.array([0, 0, 1., 0])
     v3, v2, v1, v0 = w3 @ taps, w2 @ taps, w1 @ taps, w0 @ taps
     return ((v3 * mu + v2) * mu + v1) * mu + v0
+
+
+# ------------------------------------------------------------------------------------------------ bit_errors (digitalcom.py:353-415)
+MAX_N_CORR = 65536
+
+
+def _bits_1d(x, name):
+    x = np.asarray(x)
+    if x.ndim != 1:
+        raise ValueError("bit_errors: %s must be a one-dimensional sequence of bits" % name)
+    if x.size and np.any((x != 0) & (x != 1)):
+        raise ValueError("bit_errors: %s must hold bits 0 / 1 only" % name)
+    return x.astype(np.uint8)
+
+
+def _check_n_corr(n_corr, n_transient):
+    if int(n_corr) != n_corr or n_corr < 1:
+        raise ValueError("bit_errors: n_corr must be a positive integer (got %r)" % (n_corr,))
+    if n_corr % 2:
+        warnings.warn("n_corr needs to be even")
+        raise ValueError("bit_errors: n_corr must be even (got %d): the reference centres lag 0 at n_corr / 2" % n_corr)
+    if n_corr > MAX_N_CORR:
+        raise ValueError("bit_errors: n_corr of at most %d is served (got %d)" % (MAX_N_CORR, n_corr))
+    if int(n_transient) != n_transient or n_transient < 0:
+        raise ValueError("bit_errors: n_transient must be a non-negative integer (got %r)" % (n_transient,))
+    return int(n_corr), int(n_transient)
+
+
+def bit_errors_search(tx_head, rx_head, n_corr):
+    """(kmax, taumax) of the reference's lag and sign search over the first n_corr bits of each stream (bits 0 / 1, zero-padded as +-1
+    sequences if shorter), in exact integer arithmetic: the circular correlation of two +-1 / 0 sequences of n_corr <= 65536 values is an
+    integer of magnitude <= n_corr, a float64 FFT gets it to within 1e-9, and rounding to the nearest integer restores it.  R1 = -R0;
+    phase 0 unless phase 1's maximum is STRICTLY larger; the first index attaining the maximum; lag 0 sits at n_corr / 2 after fftshift.
+    Where the exact maximum is attained more than once the reference's pick depends on its FFT's rounding noise; this picks by that order."""
+    a, b = np.zeros(n_corr), np.zeros(n_corr)
+    t, r = np.asarray(tx_head[:n_corr], dtype=np.int64), np.asarray(rx_head[:n_corr], dtype=np.int64)
+    a[:t.size], b[:r.size] = 2 * t - 1, 2 * r - 1
+    R0 = np.fft.fftshift(np.rint(np.fft.ifft(np.fft.fft(b) * np.conj(np.fft.fft(a))).real).astype(np.int64))
+    R1 = -R0
+    kmax = 1 if R1.max() > R0.max() else 0
+    R = R1 if kmax else R0
+    return kmax, int(np.argmax(R)) - n_corr // 2
+
+
+def _overlap(n_tx, n_rx, taumax):
+    """(tx start, rx start, Bit_count) of the reference's trimming (digitalcom.py:402-411), lengths after the transient"""
+    if taumax < 0:
+        t0, r0 = min(-taumax, n_tx), 0
+    else:
+        t0, r0 = 0, min(taumax, n_rx)
+    return t0, r0, min(n_tx - t0, n_rx - r0)
+
+
+def bit_errors_host(tx_data, rx_data, n_corr=1024, n_transient=0):
+    """bit_errors in NumPy (no GPU): the yardstick of bit_errors."""
+    n_corr, n_transient = _check_n_corr(n_corr, n_transient)
+    tx, rx = _bits_1d(tx_data, "tx_data")[n_transient:], _bits_1d(rx_data, "rx_data")[n_transient:]
+    if tx.size == 0 or rx.size == 0:
+        raise ValueError("bit_errors: no bits behind the transient")
+    kmax, taumax = bit_errors_search(tx, rx, n_corr)
+    log.info('kmax =  %d, taumax = %d' % (kmax, taumax))
+    t0, r0, count = _overlap(tx.size, rx.size, taumax)
+    return count, np.sum((tx[t0:t0 + count] ^ rx[r0:r0 + count] ^ kmax).astype(np.int64))
+
+
+def bit_errors(tx_data, rx_data, n_corr=1024, n_transient=0):
+    """(Bit_count, Bit_errors) = bit_errors(tx_data, rx_data, n_corr=1024, n_transient=0), digitalcom.py:353-415: the delay between the two
+    0 / 1 streams and a sign inversion of rx are found from the first n_corr bits behind the transient (bit_errors_search: on the host, exact
+    integers), then the differing bits are counted over the whole overlap on the GPU (csrc/convcode.hip: bitcount_kernel, the lag as the two
+    start offsets, the sign as `invert`).  Returns (int, numpy.int64) like the reference.
+
+    tx_data / rx_data: sequences of bits, or _ffi.DeviceBytes (one byte per bit, all nbytes of it): then only the 2 n_corr bytes of the
+    search and the 8 bytes of the count cross to the host.
+
+    Deliberate differences (tests/golden/g21_conventions.json): values other than 0 / 1, an odd n_corr (after the reference's warning) and
+    n_corr > 65536 raise ValueError; a tie of the exact correlation maximum is broken by the order above, not by rounding noise."""
+    n_corr, n_transient = _check_n_corr(n_corr, n_transient)
+    streams = (tx_data,) if tx_data is rx_data else (tx_data, rx_data)      # tx is rx: one stream, one copy
+    dev = [isinstance(v, _ffi.DeviceBytes) for v in streams]
+    host, heads, lens = [], [], []
+    for v, on_dev, name in zip(streams, dev, ("tx_data", "rx_data")):      # every argument check before the device is touched
+        if on_dev:
+            host.append(None)
+            lens.append(v.nbytes - n_transient)
+        else:
+            host.append(_bits_1d(v, name)[n_transient:])
+            lens.append(host[-1].size)
+    if min(lens) <= 0:
+        raise ValueError("bit_errors: no bits behind the transient")
+    bufs = []
+    for v, bits, n, name in zip(streams, host, lens, ("tx_data", "rx_data")):
+        if bits is None:
+            heads.append(v.read(n_transient, min(n, n_corr)))
+            if np.any(heads[-1] > 1):
+                raise ValueError("bit_errors: %s must hold bits 0 / 1 only" % name)
+            bufs.append((v, n_transient))
+        else:
+            heads.append(bits[:n_corr])
+            d = _ffi.DeviceBytes(n)
+            d.write(bits)
+            bufs.append((d, 0))
+    if len(streams) == 1:
+        bufs, heads, lens = bufs * 2, heads * 2, lens * 2
+    kmax, taumax = bit_errors_search(heads[0], heads[1], n_corr)
+    log.info('kmax =  %d, taumax = %d' % (kmax, taumax))
+    t0, r0, count = _overlap(lens[0], lens[1], taumax)
+    cnt = _ffi.DeviceBytes(8)
+    _ffi.bit_count_rows_dev(bufs[0][0].ptr + bufs[0][1] + t0, 0, bufs[1][0].ptr + bufs[1][1] + r0, 0, count, 1, kmax, cnt.ptr)
+    errors = cnt.read().view(np.int64)[0]
+    cnt.free()
+    for (d, _), bits in zip(bufs[:len(streams)], host):
+        if bits is not None:
+            d.free()
+    return count, errors
+
+
+def bit_errors_rows(tx2d, rx2d):
+    """Beyond the reference: (bits_per_row, errors int64[nrow]) over the first min(width) columns of every row, no lag search -- row r of
+    FECConv.viterbi_decoder_rows is aligned with tx[r, :nsym - Depth + 1] by construction.  One launch of the count kernel."""
+    tx, rx = np.asarray(tx2d), np.asarray(rx2d)
+    if tx.ndim != 2 or rx.ndim != 2 or tx.shape[0] != rx.shape[0]:
+        raise ValueError("bit_errors_rows: two 2-D arrays with the same number of rows")
+    for v in (tx, rx):
+        if v.size and np.any((v != 0) & (v != 1)):
+            raise ValueError("bit_errors_rows: bits 0 / 1 only")
+    n = min(tx.shape[1], rx.shape[1])
+    return n, _ffi.bit_count_rows(tx.astype(np.uint8), rx.astype(np.uint8), False, n)

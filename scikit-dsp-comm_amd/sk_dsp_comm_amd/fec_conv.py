@@ -7,6 +7,9 @@
                            (viterbi_decoder_rows_host: the same over many rows at once)
     reset                  beyond the reference: back to rest
     conv_encoder, puncture, depuncture   NumPy on the host by design (like sigsys.cic), bit-exact with the reference
+    conv_encoder_rows, puncture_rows, depuncture_rows   beyond the reference: the same three over the rows of a frame set on the GPU
+                           (csrc/convcode.hip), each row equal to the 1-D method's result; with digitalcom.bit_errors(_rows) the BER loop
+                           encode -> puncture -> channel -> depuncture -> viterbi_decoder_rows -> count runs on device kernels throughout
 
 The decoder is a register-exchange decoder: each of the 2^(K-1) states carries its last Depth decided bits; a step copies the
 surviving predecessor's history (d1 <= d2 keeps the even predecessor) and shifts the state's input bit in; from step Depth - 1 on
@@ -80,6 +83,7 @@ class FECConv(object):
             return w
         self._bits1, self._bits2 = word(self._p0), word(self._p1)
         self._kern = None
+        self._enc_kern = None
         self._host_reset()
 
     # ------------------------------------------------------------------ state
@@ -269,6 +273,75 @@ class FECConv(object):
         y[:, [k for k, g in enumerate(puncture_pattern[0]) if g == '1'], 0] = s[:, :, 0]
         y[:, [k for k, g in enumerate(puncture_pattern[1]) if g == '1'], 1] = s[:, :, 1]
         return y.reshape(-1)
+
+    # ------------------------------------------------------------------ the same three over the rows of a frame set, on the GPU
+    def _encoder(self):
+        if self._enc_kern is None:
+            self._enc_kern = _ffi.ConvCodeKernel(self.G_polys)
+        return self._enc_kern
+
+    def conv_encoder_rows(self, bits2d, state=None):
+        """Beyond the reference: code2d, states = conv_encoder_rows(bits2d, state=None).  Row r of code2d (float64, (nrow, R n)) and
+        states[r] are conv_encoder(bits2d[r], state_r); state is None (every row from rest), one string for all rows, or a sequence of nrow
+        strings.  One launch over (row, run of bits) pairs (csrc/convcode.hip): a 1-row array is the long-stream form."""
+        K, R = self.constraint_length, self.rate.denominator
+        u = np.asarray(bits2d)
+        if u.ndim != 2:
+            raise ValueError("conv_encoder_rows takes a 2-D array, one frame per row; conv_encoder encodes one stream")
+        nrow, n = u.shape
+        if u.size and np.any((u != 0) & (u != 1)):
+            raise ValueError("conv_encoder_rows: the input must hold bits 0 / 1")
+        if state is None:
+            states = ['0' * (K - 1)]
+        elif isinstance(state, str):
+            states = [state]
+        else:
+            states = list(state)
+            if len(states) != nrow:
+                raise ValueError("conv_encoder_rows: one state, or one per row (got %d for %d rows)" % (len(states), nrow))
+        for s in states:
+            if not isinstance(s, str) or len(s) != K - 1 or set(s) - {'0', '1'}:
+                raise ValueError("conv_encoder_rows: a state must be a string of %d binary digits" % (K - 1))
+        if nrow == 0 or n == 0:
+            return np.zeros((nrow, R * n)), [states[r if len(states) > 1 else 0] for r in range(nrow)]
+        code, out = self._encoder().encode_rows(u.astype(np.uint8), np.array([int(s, 2) for s in states], dtype=np.uint8))
+        return code.astype(np.float64), [binary(int(v), K - 1) for v in out]
+
+    def puncture_rows(self, code2d, puncture_pattern=('110', '101')):
+        """Beyond the reference: row r of the result is puncture(code2d[r], puncture_pattern), in code2d's dtype (elements of 1, 2, 4 or 8
+        bytes); the truncation warnings of the 1-D method, once per call.  Patterns of at most 64 digits, equally long, with the same
+        number of ones (else ValueError)."""
+        x = np.asarray(code2d)
+        if x.ndim != 2:
+            raise ValueError("puncture_rows takes a 2-D array, one frame per row; puncture takes one stream")
+        _ffi.pattern_masks(puncture_pattern)
+        L_pp = len(puncture_pattern[0])
+        n_words = x.shape[1] // 2
+        if 2 * n_words != x.shape[1]:
+            warnings.warn('Number of code bits must be even!')
+            warnings.warn('Truncating bits to be compatible.')
+        if L_pp * (n_words // L_pp) != n_words:
+            warnings.warn('Code bit length is not a multiple pp = %d!' % L_pp)
+            warnings.warn('Truncating bits to be compatible.')
+        return _ffi.puncture_rows(x, puncture_pattern)
+
+    def depuncture_rows(self, soft2d, puncture_pattern=('110', '101'), erase_value=3.5):
+        """Beyond the reference: row r of the result (float64) is depuncture(soft2d[r], puncture_pattern, erase_value); the truncation
+        warnings of the 1-D method, once per call."""
+        x = np.asarray(soft2d)
+        if x.ndim != 2:
+            raise ValueError("depuncture_rows takes a 2-D array, one frame per row; depuncture takes one stream")
+        _ffi.pattern_masks(puncture_pattern)
+        L_pp1 = sum(1 for g in puncture_pattern[0] if g == '1')
+        n_words = x.shape[1] // 2
+        if 2 * n_words != x.shape[1]:
+            warnings.warn('Number of soft bits must be even!')
+            warnings.warn('Truncating bits to be compatible.')
+        if L_pp1 * (n_words // L_pp1) != n_words:
+            warnings.warn('Number of soft bits per puncture period is %d' % L_pp1)
+            warnings.warn('The number of soft bits is not a multiple')
+            warnings.warn('Truncating soft bits to be compatible.')
+        return _ffi.depuncture_rows(x.astype(np.float64), puncture_pattern, float(erase_value))
 
     # ------------------------------------------------------------------ plots: out of scope
     def trellis_plot(self, fsize=(6, 4)):
