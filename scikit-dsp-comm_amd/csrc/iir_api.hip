@@ -1,82 +1,315 @@
-// iir_api.hip -- IIR dispatch and handle creation behind the extern "C" boundary (see include/skdsp.h).  The numerical
-// host code of handle creation (factorisation, probes) is iir_design.hpp, which needs no device.
+// iir_api.hip -- IIR handle creation and dispatch behind the extern "C" boundary (see include/skdsp.h), and all of the IIR host side that is
+// not a launch: the plan of the cascade scans on the device, the workspaces, the state transfer, and iir_run, which executes the ONE routing
+// decision of a call (iir_route.hpp).  The numerical host code needs no device: iir_design.hpp (factorisation, probes), iir_scan_plan.hpp.
 #include "api_internal.hpp"
+#include "iir_common.hpp"
 #include "iir_design.hpp"
+#include "iir_route.hpp"
 #include <cstring>
 
 namespace skdsp {
 
-// IIR on an interleaved-or-real device vector (handles the complex -> 2 planes detour).
-// tmp slot 3 holds the planes.  y may alias x.
-static int iir_any_dev(IirHandle *h, const void *x_dev, int64_t n, void *y_dev, const double *zi = nullptr, double *zf = nullptr)
+static_assert(SKDSP_F32 == kIirF32 && SKDSP_C64 == kIirC64 && SKDSP_F64 == kIirF64 && SKDSP_C128 == kIirC128, "iir_route.hpp mirrors the dtype codes");
+
+IirHandle::~IirHandle()
+{
+    if (plan) iir_free(plan);
+    if (par) iir_par_free(par);
+    for (IirHandle *g : groups) delete g;
+    if (group_tmp) (void)hipFree(group_tmp);
+    delete twin64;
+    if (seq_coef_dev) (void)hipFree(seq_coef_dev);
+    if (twin_in) (void)hipFree(twin_in);
+    if (twin_out) (void)hipFree(twin_out);
+}
+
+void iir_free(IirPlan *p)
+{
+    if (!p) return;
+    for (void *d : {(void *)p->pw_dev, (void *)p->pwa_dev, (void *)p->lb_dev, (void *)p->lbk_dev, (void *)p->gt_dev, (void *)p->state_dev, (void *)p->v_dev,
+                    (void *)p->agg_dev, (void *)p->lbg_dev, (void *)p->ticket_dev})
+        if (d) (void)hipFree(d);
+    delete p;
+}
+
+// ---- the plan of the cascade scans: the numbers are iir_scan_plan.hpp, here their device copies ---------------------------------
+static int ensure_plan(IirHandle *h)
+{
+    if (h->plan) return SKDSP_OK;
+    IirPlan *p = new IirPlan();
+    p->nsec = h->nsec; p->order = h->order; p->D = h->nsec * h->order;
+    const int D = p->D;
+    p->A_host = scan_A_host(h->coef.data(), h->nsec, h->order);
+    hipError_t e;
+    if ((e = hipMalloc((void **)&p->pw_dev, (size_t)kPowers * D * D * 8)) != hipSuccess ||
+        (e = hipMalloc((void **)&p->pwa_dev, (size_t)8 * 4 * 64 * 8)) != hipSuccess ||
+        (e = hipMalloc((void **)&p->lb_dev, (size_t)8 * D * D * 8)) != hipSuccess ||
+        (e = hipMalloc((void **)&p->lbk_dev, (size_t)32 * D * D * 8)) != hipSuccess ||
+        (e = hipMalloc((void **)&p->state_dev, (size_t)4 * D * 8)) != hipSuccess ||
+        (e = hipMalloc((void **)&p->agg_dev, (size_t)2 * 2 * kMaxW * D * 8)) != hipSuccess) {
+        iir_free(p);
+        return hip_fail(e, "hipMalloc(iir plan)", __FILE__, __LINE__);
+    }
+    h->plan = p;
+    return SKDSP_OK;
+}
+
+// a buffer that only grows; what ran on the stream may still read the old one
+static int grow(void *&p, size_t &have, size_t need, hipStream_t s)
+{
+    if (need <= have) return SKDSP_OK;
+    if (p) {
+        SK_HIP(hipStreamSynchronize(s));
+        SK_HIP(hipFree(p));
+        p = nullptr; have = 0;
+    }
+    SK_HIP(hipMalloc(&p, need));
+    have = need;
+    return SKDSP_OK;
+}
+
+// the tables of chunk length T on the device (cached: one chunk length at a time)
+static int ensure_powers(IirHandle *h, int64_t T, hipStream_t s)
+{
+    IirPlan *p = h->plan;
+    if (p->cached_T == T) return SKDSP_OK;
+    const ScanTables t = scan_tables(h->coef.data(), h->nsec, h->order, p->A_host, T, dtype_double(h->dtype));
+    SK_HIP(hipMemcpyAsync(p->lbk_dev, t.lbk.data(), t.lbk.size() * 8, hipMemcpyHostToDevice, s));
+    p->gt_T = -1;
+    if (t.gt_T == T) {
+        void *gt = p->gt_dev;
+        const int rc = grow(gt, p->gt_cap, t.gt.size() * 8, s);
+        p->gt_dev = (double *)gt;
+        if (rc) return rc;
+        SK_HIP(hipMemcpyAsync(p->gt_dev, t.gt.data(), t.gt.size() * 8, hipMemcpyHostToDevice, s));
+        p->gt_T = T;
+    }
+    p->n_lv = t.n_lv;
+    p->n_lb = t.n_lb;
+    SK_HIP(hipMemcpyAsync(p->lb_dev, t.lb.data(), t.lb.size() * 8, hipMemcpyHostToDevice, s));
+    SK_HIP(hipMemcpyAsync(p->pw_dev, t.pw.data(), t.pw.size() * 8, hipMemcpyHostToDevice, s));
+    SK_HIP(hipMemcpyAsync(p->pwa_dev, t.pwa.data(), t.pwa.size() * 8, hipMemcpyHostToDevice, s));
+    SK_HIP(hipStreamSynchronize(s));  // t is a local
+    p->cached_T = T;
+    return SKDSP_OK;
+}
+
+// ---- one decision per call (iir_route.hpp), and what it asks ----------------------------------------------------------------------
+struct IirQueries {
+    hipStream_t s;
+    ParChoice par(IirHandle *h, bool interleaved, int nrow, int dec, int up, int64_t n) { return iir_par_takes(h, n, nrow, dec, interleaved, up, s); }
+    int fused_cached(IirHandle *h, bool interleaved, int &fstate, int &fnlv)
+    {
+        const int rc = ensure_plan(h);
+        if (rc) return rc;
+        fstate = interleaved ? h->plan->fused_state_c : h->plan->fused_state;   // applicability only (cached); the policy is per call
+        fnlv = interleaved ? h->plan->fused_nlv_c : h->plan->fused_nlv;
+        return SKDSP_OK;
+    }
+    void fused_remember(IirHandle *h, bool interleaved, int fstate, int fnlv)
+    {
+        (interleaved ? h->plan->fused_state_c : h->plan->fused_state) = fstate;
+        (interleaved ? h->plan->fused_nlv_c : h->plan->fused_nlv) = fnlv;
+    }
+    int scan_facts(IirHandle *h, int64_t T, ScanFacts &f)
+    {
+        const int rc = ensure_powers(h, T, s);
+        f = ScanFacts{h->plan->n_lv, h->plan->n_lb, h->plan->gt_T};
+        return rc;
+    }
+};
+typedef IirStep<IirHandle> Step;
+
+// the single pass or the two-pass scan of one handle: tables, chunk states, the state transfer, the launch.
+// zi / zf: [nbatch][D] host states in the caller's factorisation
+static int scan_step(const Step &st, const void *x, void *y, const double *zi_host, double *zf_host, hipStream_t s)
+{
+    IirHandle *h = st.h;
+    const bool fused = st.engine == kEngFused, dbl = dtype_double(h->dtype);
+    const int nbatch = st.nrow, dec = st.dec;
+    const int64_t n = st.n;
+    int rc = ensure_plan(h);
+    if (rc) return rc;
+    IirPlan *p = h->plan;
+    const int D = p->D;
+    const int64_t T = fused ? fused_chunk(dbl, st.interleaved) : st.geom.T;
+    if ((rc = ensure_powers(h, T, s))) return rc;   // (a no-op where the route asked for these tables last)
+    void *v = p->v_dev;
+    rc = grow(v, p->v_cap, fused ? 0 : (size_t)nbatch * D * st.geom.J * 8, s);
+    p->v_dev = (double *)v;
+    if (rc) return rc;
+    SK_CHECK(dec <= 1 || (zf_host == nullptr && (st.interleaved || nbatch == 1)), SKDSP_ERR_UNSUPPORTED,
+             "iir: decimating store needs a real or interleaved complex signal and no state output");
+    SK_CHECK(nbatch >= 1 && nbatch <= 2, SKDSP_ERR_BADARG, "iir: batch must be 1 or 2");
+    const double *zi_dev = nullptr;
+    double *zf_dev = zf_host ? p->state_dev + 2 * D : nullptr;
+    if (zi_host) {
+        std::vector<double> zi_int;  // the caller's DF2T states in the internal factorisation (IirHandle::state_scale)
+        if (!h->state_scale.empty()) {
+            zi_int.resize((size_t)nbatch * D);
+            for (int b = 0; b < nbatch; ++b)
+                for (int d = 0; d < D; ++d) zi_int[(size_t)b * D + d] = zi_host[(size_t)b * D + d] * h->state_scale[d];
+            zi_host = zi_int.data();
+        }
+        SK_HIP(hipMemcpyAsync(p->state_dev, zi_host, (size_t)nbatch * D * 8, hipMemcpyHostToDevice, s));
+        if (!zi_int.empty()) SK_HIP(hipStreamSynchronize(s));  // zi_int is a local
+        zi_dev = p->state_dev;
+    }
+    if (fused) {
+        rc = iir_fused_launch(h, x, n, nbatch, st.x_stride, y, zi_dev, zf_dev, s, dec, st.interleaved);
+    } else {
+        IirArgs a;
+        a.x = x; a.y = y; a.n = n; a.T = T; a.J = st.geom.J; a.batch_stride = st.x_stride;
+        a.il = st.interleaved ? 1 : 0;
+        a.pw = p->pw_dev; a.v = p->v_dev;
+        a.agg = p->agg_dev;
+        a.carry = p->agg_dev + (size_t)2 * kMaxW * D;
+        a.lbmat = p->lb_dev;
+        a.n_lb = st.fast ? 0 : p->n_lb;   // (aggregate-free mode: K3 reads the carries)
+        a.n_lv = p->n_lv < 8 ? p->n_lv : 8;
+        a.zi = zi_dev; a.zf = zf_dev;
+        a.dec = dec > 1 ? dec : 1;
+        a.n_keep = (n / a.dec) * a.dec;
+        a.dec_dq = scan_dec_dq(st.interleaved, dbl, T, a.dec);
+        a.dec_dr = scan_dec_dr(st.interleaved, dbl, T, a.dec);
+        const ScanLaunch L{h->coef.data(), h->nsec, h->order, p->gt_dev, p->lbk_dev, p->n_lv, p->gt_T, nbatch, st.geom.W, ctx().num_cus,
+                           ScanForm{st.fast, h->unit_tail, scan_k1(st.fast, st.interleaved, D, T)}};
+        rc = dbl ? iir_scan_launch_f64(L, a, s) : iir_scan_launch_f32(L, a, s);
+        if (!rc) note_path("iir_scan");   // (recorded once the two-pass kernels WERE launched: the other engines note themselves)
+    }
+    if (rc) return rc;
+    if (zf_host) {
+        SK_HIP(hipMemcpyAsync(zf_host, zf_dev, (size_t)nbatch * D * 8, hipMemcpyDeviceToHost, s));
+        SK_HIP(hipStreamSynchronize(s));
+        if (!h->state_scale.empty())
+            for (int b = 0; b < nbatch; ++b)
+                for (int d = 0; d < D; ++d) zf_host[(size_t)b * D + d] /= h->state_scale[d];
+    }
+    return SKDSP_OK;
+}
+
+// one step of a route on row `row` of the call
+static int run_step(const Step &st, const IirCall &c, size_t esz, const void *x_dev, void *y_dev, int64_t row, const double *zi, double *zf)
 {
     hipStream_t s = ctx().stream;
+    IirHandle *h = st.h;
+    auto at = [&](const IirBuf<IirHandle> &b, void **out) -> int {
+        auto owned = [&](void *&p, size_t &have) {   // a buffer of the handle b.owner
+            const int rc = grow(p, have, (size_t)b.bytes, s);
+            *out = p;
+            return rc;
+        };
+        switch (b.kind) {
+        case kBufX: *out = (char *)const_cast<void *>(x_dev) + (size_t)row * c.x_stride * esz; return SKDSP_OK;
+        case kBufY: *out = (char *)y_dev + (size_t)row * c.y_stride * esz; return SKDSP_OK;
+        case kBufPlanes: return ws_reserve(3, (size_t)b.bytes, out);
+        case kBufFull: return ws_reserve(2, (size_t)b.bytes, out);
+        case kBufGroupTmp: return owned(b.owner->group_tmp, b.owner->group_tmp_bytes);
+        case kBufTwinIn: return owned(b.owner->twin_in, b.owner->twin_in_bytes);
+        default: return owned(b.owner->twin_out, b.owner->twin_out_bytes);
+        }
+    };
+    void *src = nullptr, *dst = nullptr;
+    int rc;
+    if ((rc = at(st.src, &src)) || (rc = at(st.dst, &dst))) return rc;
+    const size_t rsz = dtype_double(h->dtype) ? 8 : 4;
+    auto im_of = [&](void *re, int64_t n) { return (void *)((char *)re + (size_t)(n + 63) / 64 * 64 * rsz); };
+    switch (st.engine) {
+    case kEngPar: return iir_par_launch(h, st.par, src, st.n, st.nrow, st.x_stride, st.y_stride, dst, s, st.dec, st.interleaved, st.up);
+    case kEngWiden: return convert_launch(src, dst, st.n, true, s);
+    case kEngNarrow: return convert_launch(src, dst, st.n, false, s);
+    case kEngZeroStuff: return upsample_launch(src, st.n, st.up, h->dtype, (double)st.up, dst, s);
+    case kEngZeroStuffPlanes: return upsample_planes_launch(src, st.n, st.up, h->dtype, (double)st.up, dst, im_of(dst, st.n * st.up), s);
+    case kEngDeinterleave: return deinterleave_launch(src, st.n, h->dtype, dst, im_of(dst, st.n), s);
+    case kEngInterleave: return interleave_launch(src, im_of(src, st.n), st.n, h->dtype, dst, s);
+    case kEngDownsample: return downsample_launch(src, st.n, st.dec, 0, h->dtype, dst, s);
+    default: break;
+    }
+    // iir_seq, iir_fused, the two-pass scan: they take and leave states -- of a group, its sections' slice of the caller's vectors
+    const int Dg = h->nsec * h->order;
+    const bool whole = Dg == st.state_D;
+    std::vector<double> zi_g, zf_g;
+    const double *zi_p = st.zi ? zi : nullptr;
+    double *zf_p = st.zf ? zf : nullptr;
+    if (zi_p && !whole) {
+        zi_g.resize((size_t)st.nrow * Dg);
+        for (int b = 0; b < st.nrow; ++b) memcpy(zi_g.data() + (size_t)b * Dg, zi + (size_t)b * st.state_D + h->order * st.state_first, (size_t)Dg * 8);
+        zi_p = zi_g.data();
+    }
+    if (zf_p && !whole) {
+        zf_g.assign((size_t)st.nrow * Dg, 0.0);
+        zf_p = zf_g.data();
+    }
+    if (st.engine == kEngSeq) rc = iir_seq_launch(h, src, st.n, st.nrow, st.x_stride, st.y_stride, dst, s, zi_p, zf_p, st.dec);
+    else rc = scan_step(st, src, dst, zi_p, zf_p, s);
+    if (rc) return rc;
+    if (zf_p && !whole)
+        for (int b = 0; b < st.nrow; ++b) memcpy(zf + (size_t)b * st.state_D + h->order * st.state_first, zf_g.data() + (size_t)b * Dg, (size_t)Dg * 8);
+    return SKDSP_OK;
+}
+
+// decide, then execute.  x / y: device vectors (y may alias x for .filter); zi / zf: the caller's host states
+static int iir_run(IirHandle *h, IirCall c, const void *x_dev, void *y_dev, const double *zi = nullptr, double *zf = nullptr)
+{
+    c.zi = zi != nullptr; c.zf = zf != nullptr;
+    c.num_cus = ctx().num_cus;
+    const IirRouteOptions o{opt().iir_par, opt().iir_planar, opt().iir_up_fused, opt().iir_dn_full, opt().iir_two_pass, opt().iir_no_mfma};
+    IirQueries q{ctx().stream};
+    const IirRoute<IirHandle> r = iir_route(h, c, o, q);
+    SK_CHECK(r.status != kIirNoRoute, SKDSP_ERR_UNSUPPORTED, "iir: no engine takes this call");
+    if (r.status) return r.status;   // (a query failed and said why)
+    const size_t esz = dtype_size(h->dtype);
+    for (size_t i = 0; i < r.steps.size();) {
+        const size_t block = r.steps[i].block > 0 ? (size_t)r.steps[i].block : 1;
+        const int64_t rows = r.steps[i].block > 0 ? c.nrow : 1;
+        for (int64_t row = 0; row < rows; ++row)
+            for (size_t j = i; j < i + block; ++j)
+                if (int rc = run_step(r.steps[j], c, esz, x_dev, y_dev, row, zi, zf)) return rc;
+        i += block;
+    }
+    return SKDSP_OK;
+}
+
+// IIR on an interleaved-or-real device vector.  y may alias x.
+static int iir_any_dev(IirHandle *h, const void *x_dev, int64_t n, void *y_dev, const double *zi = nullptr, double *zf = nullptr)
+{
     if (n <= 0) {
         const size_t zb = (size_t)(dtype_complex(h->dtype) ? 2 : 1) * h->nsec * h->order * 8;
         if (zf && zi) memcpy(zf, zi, zb);
         else if (zf) memset(zf, 0, zb);
         return SKDSP_OK;
     }
-    if (!dtype_complex(h->dtype)) return iir_launch_planar(h, x_dev, n, 1, 0, y_dev, s, zi, zf);
-    const bool planar_only = opt().iir_planar != 0;  // developer A/B switch (and the tests)
-    if (!planar_only && !h->groups.empty() && !h->twin64 && !zi && !zf && opt().iir_par > 0) {
-        // more than 8 biquads on a complex signal: group after group in place behind the first, each through the parallel form on the
-        // interleaved samples where it applies (else whatever that group's own dispatch takes) -- not the whole cascade through two planes
-        for (size_t gi = 0; gi < h->groups.size(); ++gi) {
-            IirHandle *g = h->groups[gi];
-            const void *src = gi == 0 ? x_dev : y_dev;
-            int rc = iir_par_launch(g, src, n, 1, 0, 0, y_dev, s, 1, 1, 1);
-            if (rc == 1) rc = iir_any_dev(g, src, n, y_dev);
-            if (rc) return rc;
-        }
-        return SKDSP_OK;
-    }
-    if (!planar_only) {
-        // decaying filters: both components stay interleaved end to end (iir_k1c / iir_k3c kernels)
-        const int r1 = iir_launch_planar(h, x_dev, n, 2, 0, y_dev, s, zi, zf, 1);
-        if (r1 != 1) return r1;
-    }
-    const size_t rsz = dtype_double(h->dtype) ? 8 : 4;
-    const int64_t stride = (int64_t)round_up((size_t)n, 64);
-    void *planes = nullptr;
-    int rc = ws_reserve(3, (size_t)2 * stride * rsz, &planes);
-    if (rc) return rc;
-    void *re = planes, *im = (char *)planes + (size_t)stride * rsz;
-    if ((rc = deinterleave_launch(x_dev, n, h->dtype, re, im, s))) return rc;
-    if ((rc = iir_launch_planar(h, planes, n, 2, stride, planes, s, zi, zf))) return rc;
-    return interleave_launch(re, im, n, h->dtype, y_dev, s);
+    IirCall c;
+    c.kind = kIirFilter; c.n = n;
+    return iir_run(h, c, x_dev, y_dev, zi, zf);
 }
 
-// y = filter(L * upsample(x, L)).  Real: zero-stuff straight into y, then filter in place.  Complex:
-// zero-stuff straight into the two planes the scan works on (no stuffed interleaved copy, no
-// deinterleave pass), filter, interleave into y.
+// y = filter(L * upsample(x, L))
 static int iir_up_any(IirHandle *h, const void *x_dev, int64_t n, int L, void *y_dev)
 {
-    hipStream_t s = ctx().stream;
-    const int64_t nl = n * L;
-    if (nl <= 0) return SKDSP_OK;
-    int rc;
-    if (!dtype_complex(h->dtype)) {
-        // the parallel-form kernel zero-stuffs while it stages a segment: the L-fold signal is never written (1 = not applicable)
-        if (L > 1 && opt().iir_par && opt().iir_up_fused && h->order == 2) {
-            rc = iir_par_launch(h, x_dev, nl, 1, 0, 0, y_dev, s, 1, 0, L);
-            if (rc != 1) return rc;
-        }
-        if ((rc = upsample_launch(x_dev, n, L, h->dtype, (double)L, y_dev, s))) return rc;
-        return iir_any_dev(h, y_dev, nl, y_dev);
-    }
-    if (L > 1 && opt().iir_par && opt().iir_up_fused && h->order == 2 && !opt().iir_planar) {   // (interleaved in, interleaved out)
-        rc = iir_par_launch(h, x_dev, nl, 1, 0, 0, y_dev, s, 1, 1, L);
-        if (rc != 1) return rc;
-    }
-    const size_t rsz = dtype_double(h->dtype) ? 8 : 4;
-    const int64_t stride = (int64_t)round_up((size_t)nl, 64);
-    void *planes = nullptr;
-    if ((rc = ws_reserve(3, (size_t)2 * stride * rsz, &planes))) return rc;
-    void *re = planes, *im = (char *)planes + (size_t)stride * rsz;
-    if ((rc = upsample_planes_launch(x_dev, n, L, h->dtype, (double)L, re, im, s))) return rc;
-    if ((rc = iir_launch_planar(h, planes, nl, 2, stride, planes, s))) return rc;
-    return interleave_launch(re, im, nl, h->dtype, y_dev, s);
+    if (n * L <= 0) return SKDSP_OK;
+    IirCall c;
+    c.kind = kIirUp; c.n = n; c.rate = L;
+    return iir_run(h, c, x_dev, y_dev);
+}
+
+// y = downsample(filter(x), M) on device vectors (both the _dev and the host-pointer entry use it)
+static int iir_dn_any(IirHandle *h, const void *x_dev, int64_t n, int M, void *y_dev)
+{
+    if (n <= 0) return SKDSP_OK;
+    IirCall c;
+    c.kind = kIirDn; c.n = n; c.rate = M;
+    return iir_run(h, c, x_dev, y_dev);
+}
+
+static int iir_rows_dev(IirHandle *h, const void *x_dev, int64_t n, int64_t nrow, int64_t x_stride, int64_t y_stride, void *y_dev)
+{
+    if (n <= 0 || nrow <= 0) return SKDSP_OK;
+    SK_CHECK(x_stride >= n && y_stride >= n, SKDSP_ERR_BADARG, "iir_filter_rows: row stride below the row length");
+    SK_CHECK(nrow < (1 << 24), SKDSP_ERR_BADARG, "iir_filter_rows: too many rows");
+    IirCall c;
+    c.kind = kIirRows; c.n = n; c.nrow = nrow; c.x_stride = x_stride; c.y_stride = y_stride;
+    return iir_run(h, c, x_dev, y_dev);
 }
 
 }  // namespace skdsp
@@ -226,42 +459,6 @@ int skdsp_sos_par_info(const double *sos, int nsec, double *out, int *accepted)
     return iir_par_expand_host(coef.data(), nsec, out, accepted);
 }
 
-// rows of one launch (parallel form) or, where that does not apply, row by row through the cascade kernels
-static int iir_rows_dev(IirHandle *h, const void *x_dev, int64_t n, int64_t nrow, int64_t x_stride, int64_t y_stride, void *y_dev)
-{
-    if (n <= 0 || nrow <= 0) return SKDSP_OK;
-    SK_CHECK(x_stride >= n && y_stride >= n, SKDSP_ERR_BADARG, "iir_filter_rows: row stride below the row length");
-    SK_CHECK(nrow < (1 << 24), SKDSP_ERR_BADARG, "iir_filter_rows: too many rows");
-    const size_t esz = dtype_size(h->dtype);
-    // the reference's recursion takes all rows in ONE launch (one wave per row), not one single-wave kernel per row in stream order
-    if (h->seq && !dtype_complex(h->dtype)) return iir_seq_launch(h, x_dev, n, (int)nrow, x_stride, y_stride, y_dev, ctx().stream);
-    if (!h->groups.empty() && !dtype_complex(h->dtype) && opt().iir_par > 0) {
-        // groups of sections (more than 8 biquads): every group over all rows in one launch where its parallel form applies, in place behind the first
-        for (size_t gi = 0; gi < h->groups.size(); ++gi) {
-            IirHandle *g = h->groups[gi];
-            const void *src = gi == 0 ? x_dev : y_dev;
-            const int64_t ss = gi == 0 ? x_stride : y_stride;
-            int rc = iir_par_launch(g, src, n, (int)nrow, ss, y_stride, y_dev, ctx().stream);
-            if (rc == 1) {
-                for (int64_t r = 0; r < nrow; ++r)
-                    if ((rc = iir_any_dev(g, (const char *)src + (size_t)r * ss * esz, n, (char *)y_dev + (size_t)r * y_stride * esz))) return rc;
-            } else if (rc) {
-                return rc;
-            }
-        }
-        return SKDSP_OK;
-    }
-    if (!dtype_complex(h->dtype) && opt().iir_par > 0) {
-        const int r = iir_par_launch(h, x_dev, n, (int)nrow, x_stride, y_stride, y_dev, ctx().stream);
-        if (r != 1) return r;
-    }
-    for (int64_t r = 0; r < nrow; ++r) {
-        const int rc = iir_any_dev(h, (const char *)x_dev + (size_t)r * x_stride * esz, n, (char *)y_dev + (size_t)r * y_stride * esz);
-        if (rc) return rc;
-    }
-    return SKDSP_OK;
-}
-
 int skdsp_iir_filter_rows_dev(skdsp_handle hh, const void *x_dev, int64_t n, int64_t nrow, int64_t x_stride, int64_t y_stride, void *y_dev)
 {
     API_BEGIN;
@@ -314,25 +511,6 @@ int skdsp_iir_up_dev(skdsp_handle hh, const void *x_dev, int64_t n, int L, void 
     SK_CHECK(L >= 1, SKDSP_ERR_BADARG, "iir_up: L must be >= 1");
     std::lock_guard<std::mutex> lk(h->mu);
     return iir_up_any(h, x_dev, n, L, y_dev);
-}
-
-// y = downsample(filter(x), M) on device vectors (both the _dev and the host-pointer entry use it)
-static int iir_dn_any(IirHandle *h, const void *x_dev, int64_t n, int M, void *y_dev)
-{
-    if (n <= 0) return SKDSP_OK;
-    // K3 stores every M-th output itself -- the full-rate result never reaches HBM
-    if (M > 1 && M <= 4096 && !opt().iir_dn_full) {
-        if (!dtype_complex(h->dtype)) return iir_launch_planar(h, x_dev, n, 1, 0, y_dev, ctx().stream, nullptr, nullptr, 0, M);
-        if (!opt().iir_planar) {  // interleaved complex kernels (decaying filters); 1 = not applicable
-            const int r1 = iir_launch_planar(h, x_dev, n, 2, 0, y_dev, ctx().stream, nullptr, nullptr, 1, M);
-            if (r1 != 1) return r1;
-        }
-    }
-    void *full = nullptr;
-    int rc = ws_reserve(2, (size_t)n * dtype_size(h->dtype) + 256, &full);
-    if (rc) return rc;
-    if ((rc = iir_any_dev(h, x_dev, n, full))) return rc;
-    return downsample_launch(full, n, M, 0, h->dtype, y_dev, ctx().stream);
 }
 
 int skdsp_iir_dn_dev(skdsp_handle hh, const void *x_dev, int64_t n, int M, void *y_dev)

@@ -1,18 +1,13 @@
-// iir_common.hpp -- declarations shared by the IIR scan translation units (iir_scan.hip: K1 / carries / K3 and the
-// host side; iir_fused.hip: the single-pass scan).  gfx950 only.
+// iir_common.hpp -- declarations shared by the IIR scan translation units (iir_scan.hip: K1 / carries / K3; iir_fused.hip: the
+// single-pass scan) and the host side that plans and launches them (iir_api.hip).  gfx950 only.
 #pragma once
 #include "skdsp_internal.hpp"
+#include "iir_scan_plan.hpp"   // the constants (kIirThreads, kPiece, kMmPiece, kMaxPairs, kMaxW, kPowers) and the rules of a launch
 #include <type_traits>
 #include <cmath>
 #include <cstring>
 
 namespace skdsp {
-
-constexpr int kIirThreads = 256;
-constexpr int kPiece = 32;          // samples per thread per staged piece
-constexpr int kMaxPairs = 12288;    // K2 capacity: workgroups x state dimension (one 96 KiB LDS image)
-constexpr int kMaxW = 512;          // workgroups (of 256 chunks) per vector (1024 measured slower: more scan, same occupancy)
-constexpr int kPowers = 19;         // M^(2^l), l = 0..18
 
 struct IirPlan {
     int nsec, order, D;
@@ -42,6 +37,41 @@ struct IirPlan {
     unsigned long long ticket_count[2] = {0, 0};  // their values (a launch adds nseg to each dispenser it uses)
     unsigned epoch = 0;
 };
+
+struct IirArgs {
+    const void *x;
+    void *y;
+    int64_t n;
+    int64_t T;        // chunk length (multiple of 32)
+    int64_t J;        // number of chunks
+    int64_t batch_stride;  // elements between batch items (planar complex = 2 items)
+    int il;               // 1: x / y are interleaved complex (aggregate-free mode only; iir_k1c / iir_k3c kernels)
+    const double *pw; // matrix powers
+    double *v;        // [batch][D][J]
+    double *agg;      // [batch][W][D]  workgroup aggregates (K1 out)
+    const double *carry;  // [batch][W][D]  workgroup carry-in (K3 in), used when n_lb == 0
+    const double *lbmat;  // [n_lb-1][D][D]: (M^256)^k, k = 1..n_lb-1
+    int n_lb;             // > 0: carry = sum_{k<n_lb} (M^256)^k agg[wg-1-k] computed in K3 (no K2 launch)
+    int n_lv;             // chunk-level scan levels whose power M^(2^l) is not yet negligible (<= 8)
+    const double *zi;     // [batch][D] initial state (streaming; null = rest, what the reference uses)
+    double *zf;           // [batch][D] state after sample n-1 (null = not wanted)
+    int dec;              // > 1: K3 stores only y[k * dec] (at y[k]), k < n_keep / dec  (.dn: no full-rate result in HBM)
+    int dec_dq, dec_dr;   // (32 T) div / mod dec: index step between a thread's staged segments
+    int64_t n_keep;       // (n / dec) * dec
+};
+
+// a two-pass launch (iir_scan.hip: iir_scan_launch_f32 / _f64) besides the kernels' own arguments
+struct ScanLaunch {
+    const double *coef;          // the handle's sections
+    int nsec, order;
+    const double *gt, *lbk;      // the plan's G table and chunk look-back powers (aggregate-free mode)
+    int n_lv;                    // ... and its scan depth, with gt_T what admits that mode
+    int64_t gt_T;
+    int nbatch, W, num_cus;
+    ScanForm form;
+};
+int iir_scan_launch_f32(const ScanLaunch &L, IirArgs &a, hipStream_t s);
+int iir_scan_launch_f64(const ScanLaunch &L, IirArgs &a, hipStream_t s);
 
 template <int NSEC, int ORD> struct Coef { double c[NSEC * (2 * ORD + 1)]; };
 
@@ -115,7 +145,7 @@ __device__ __forceinline__ void wave_lds_sync()
 
 
 // single-pass scan (iir_fused.hip); T = 128 (float) / 64 (double) samples per chunk; the plan's powers and G table
-// must already be those of that chunk length (ensure_powers in iir_scan.hip)
+// must already be those of that chunk length (ensure_powers in iir_api.hip)
 int iir_fused_launch(IirHandle *h, const void *x, int64_t n, int nbatch, int64_t batch_stride, void *y, const double *zi_dev,
                      double *zf_dev, hipStream_t s, int dec = 1,
                      int interleaved = 0);  // 1: x / y interleaved complex (chunks of 64 / 32 complex samples), nbatch = 2

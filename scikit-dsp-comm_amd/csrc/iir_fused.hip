@@ -926,6 +926,11 @@ static int launch_fused(IirHandle *h, const void *x, int64_t n, int nbatch, int6
 int iir_fused_launch(IirHandle *h, const void *x, int64_t n, int nbatch, int64_t batch_stride, void *y, const double *zi_dev,
                      double *zf_dev, hipStream_t s, int dec, int interleaved)
 {
+    // the rule of iir_scan_plan.hpp: biquads, at most 8, and the plan's tables are those of the single-pass chunk length and vanish over a segment
+    const IirPlan *p = h->plan;
+    const int64_t Tf = fused_chunk(dtype_double(h->dtype), interleaved != 0);
+    SK_CHECK(h->order == 2 && h->nsec <= 8 && p && p->cached_T == Tf && fused_applies(ScanFacts{p->n_lv, p->n_lb, p->gt_T}, Tf), SKDSP_ERR_UNSUPPORTED,
+             "iir_fused: the single-pass scan does not take this call");
     note_path("iir_fused");
     return dtype_double(h->dtype) ? launch_fused<double>(h, x, n, nbatch, batch_stride, y, zi_dev, zf_dev, s, dec, interleaved)
                                   : launch_fused<float>(h, x, n, nbatch, batch_stride, y, zi_dev, zf_dev, s, dec, interleaved);

@@ -1284,7 +1284,7 @@ template <int TT, bool UPJ, int UPS> static int par_launch_dtype(bool dbl, bool 
 static int launch_par(IirHandle *h, ParPlan *p, const ParChoice &c, bool dbl, bool interleaved, const void *x, int64_t n, int nrow, int64_t x_stride,
                       int64_t y_stride, void *y, hipStream_t s, int dec, int up)
 {
-    note_path("iir_par");   // (here, not in iir_par_launch: that function returns 1 -- nothing launched -- for every call the parallel form does not take)
+    note_path("iir_par");
     ParTables &tb = p->tab[c.slot];
     const int T = tb.T;
     const size_t elem = dbl ? 8 : 4;
@@ -1363,26 +1363,34 @@ static int launch_par(IirHandle *h, ParPlan *p, const ParChoice &c, bool dbl, bo
     return SKDSP_OK;
 }
 
-// returns 1 when the parallel form does not apply to this handle / call (nothing was launched)
-int iir_par_launch(IirHandle *h, const void *x, int64_t n, int nrow, int64_t x_stride, int64_t y_stride, void *y, hipStream_t s, int dec,
-                   int interleaved, int up)
+// Does the parallel form take this call, and how (status 0; otherwise the call goes to the cascade kernels): the plan on first use, then par_choose.
+ParChoice iir_par_takes(IirHandle *h, int64_t n, int nrow, int dec, int interleaved, int up, hipStream_t s)
 {
-    if (h->order != 2 || !par_call_shape_ok(h->nsec, interleaved != 0, nrow, dec, up, n)) return 1;
+    ParChoice no;
+    if (h->order != 2 || !par_call_shape_ok(h->nsec, interleaved != 0, nrow, dec, up, n)) return no;
     const bool dbl = dtype_double(h->dtype);
 #ifdef SK_PAR_DEV_F32REAL   // (developer builds have the float32 real kernels only: every other signal takes the cascade kernels)
-    if (dbl || interleaved) return 1;
+    if (dbl || interleaved) return no;
 #endif
     if (!h->par) {
         h->par = new ParPlan();
         h->par->state = par_expand(h->coef.data(), h->nsec, h->par->e) ? 1 : -1;
     }
     ParPlan *p = h->par;
-    if (p->state != 1) return 1;
+    if (p->state != 1) return no;   // (poles shared between sections, slow decay, ...)
     const ParOptions o{opt().iir_dn_t96, opt().iir_up_jump, opt().iir_up_lean, opt().iir_dn_compact, opt().iir_par_v32};
-    const ParChoice c = par_choose(h->nsec, dbl, interleaved != 0, nrow, dec, up, n, o, [&](int slot) { return par_slot_K(*p, slot, s); });
-    if (c.status) return c.status;
-    if (interleaved) return launch_par(h, p, c, dbl, true, x, n, 1, 0, 0, y, s, dec, up);
-    return launch_par(h, p, c, dbl, false, x, n, nrow, x_stride, y_stride, y, s, dec, up);
+    return par_choose(h->nsec, dbl, interleaved != 0, nrow, dec, up, n, o, [&](int slot) { return par_slot_K(*p, slot, s); });
+}
+
+// the launch of a choice iir_par_takes made for this handle and this call
+int iir_par_launch(IirHandle *h, const ParChoice &c, const void *x, int64_t n, int nrow, int64_t x_stride, int64_t y_stride, void *y, hipStream_t s, int dec,
+                   int interleaved, int up)
+{
+    SK_CHECK(c.status == 0 && h->par && h->par->state == 1 && h->par->tab[c.slot].T != 0, SKDSP_ERR_UNSUPPORTED,
+             "iir_par: the parallel form does not take this call");
+    const bool dbl = dtype_double(h->dtype);
+    if (interleaved) return launch_par(h, h->par, c, dbl, true, x, n, 1, 0, 0, y, s, dec, up);
+    return launch_par(h, h->par, c, dbl, false, x, n, nrow, x_stride, y_stride, y, s, dec, up);
 }
 
 }  // namespace skdsp

@@ -38,35 +38,13 @@
 
 
 // SK_SCAN_PART: this file is compiled twice so that its ~150 kernel instantiations (the long pole of the build: 136 s in one
-// piece) compile side by side: 1 = host side + the float32 kernels (build/iir_scan.o), 2 = the float64 kernels and their dispatch
-// only (build/iir_scan_f64.o); 0 = everything in one object (variant builds)
+// piece) compile side by side: 1 = the float32 kernels and their launch (build/iir_scan.o), 2 = the float64 ones
+// (build/iir_scan_f64.o); 0 = everything in one object (variant builds).  There is no host code here but the launch.
 #ifndef SK_SCAN_PART
 #define SK_SCAN_PART 0
 #endif
 
 namespace skdsp {
-
-struct IirArgs {
-    const void *x;
-    void *y;
-    int64_t n;
-    int64_t T;        // chunk length (multiple of 32)
-    int64_t J;        // number of chunks
-    int64_t batch_stride;  // elements between batch items (planar complex = 2 items)
-    int il;               // 1: x / y are interleaved complex (aggregate-free mode only; iir_k1c / iir_k3c kernels)
-    const double *pw; // matrix powers
-    double *v;        // [batch][D][J]
-    double *agg;      // [batch][W][D]  workgroup aggregates (K1 out)
-    const double *carry;  // [batch][W][D]  workgroup carry-in (K3 in), used when n_lb == 0
-    const double *lbmat;  // [n_lb-1][D][D]: (M^256)^k, k = 1..n_lb-1
-    int n_lb;             // > 0: carry = sum_{k<n_lb} (M^256)^k agg[wg-1-k] computed in K3 (no K2 launch)
-    int n_lv;             // chunk-level scan levels whose power M^(2^l) is not yet negligible (<= 8)
-    const double *zi;     // [batch][D] initial state (streaming; null = rest, what the reference uses)
-    double *zf;           // [batch][D] state after sample n-1 (null = not wanted)
-    int dec;              // > 1: K3 stores only y[k * dec] (at y[k]), k < n_keep / dec  (.dn: no full-rate result in HBM)
-    int dec_dq, dec_dr;   // (32 T) div / mod dec: index step between a thread's staged segments
-    int64_t n_keep;       // (n / dec) * dec
-};
 
 // Kernel body shared by K1 (WRITE=false) and K3 (WRITE=true).
 template <int NSEC, int ORD, typename IO, bool WRITE, bool UNIT = false>
@@ -328,7 +306,7 @@ __global__ __launch_bounds__(kIirThreads) void iir_chunk_kernel(IirArgs a, Coef<
 // x[chunk l & 15][k0 + (l >> 4)]; C: col = lane & 15, row = (lane >> 4) + 4 reg).  The samples of the
 // wave's 16 chunks are staged per 128-sample piece in a wave-private LDS image (row pitch 132 words:
 // the 64 B-operand reads of a step hit 64 distinct banks), so there is no workgroup barrier at all.
-constexpr int kMmPiece = 128;                 // samples of every chunk staged at a time
+static_assert(kMmPiece == 128, "the staging below is laid out for 128-sample pieces (iir_scan_plan.hpp: kMmPiece)");
 constexpr int kMmPitch = kMmPiece + 4;        // in 4-byte words (float); doubles use 2 words per sample
 
 // NT = 1: D <= 16 states (<= 8 biquads); NT = 2: up to 32 states in two 16-row tiles sharing the B operand.
@@ -904,494 +882,89 @@ __global__ __launch_bounds__(1024) void iir_wg_scan_kernel(const double *__restr
     for (int p = tid; p < npairs; p += 1024) out[p] = vb[p];
 }
 
-// ------------------------------------------------------------------ host side
-#if SK_SCAN_PART != 2
-bool iir_shape_supported(int nsec, int order)
-{
-    return order == 2 && nsec >= 1 && nsec <= 12;   // (one group: longer cascades are split by the handle)
-}
-
-IirHandle::~IirHandle()
-{
-    if (plan) iir_free(plan);
-    if (par) iir_par_free(par);
-    for (IirHandle *g : groups) delete g;
-    if (group_tmp) (void)hipFree(group_tmp);
-    delete twin64;
-    if (seq_coef_dev) (void)hipFree(seq_coef_dev);
-    if (twin_in) (void)hipFree(twin_in);
-    if (twin_out) (void)hipFree(twin_out);
-}
-
-void iir_free(IirPlan *p)
-{
-    if (!p) return;
-    if (p->pw_dev) (void)hipFree(p->pw_dev);
-    if (p->pwa_dev) (void)hipFree(p->pwa_dev);
-    if (p->lb_dev) (void)hipFree(p->lb_dev);
-    if (p->lbk_dev) (void)hipFree(p->lbk_dev);
-    if (p->gt_dev) (void)hipFree(p->gt_dev);
-    if (p->state_dev) (void)hipFree(p->state_dev);
-    if (p->v_dev) (void)hipFree(p->v_dev);
-    if (p->agg_dev) (void)hipFree(p->agg_dev);
-    if (p->lbg_dev) (void)hipFree(p->lbg_dev);
-    if (p->ticket_dev) (void)hipFree(p->ticket_dev);
-    delete p;
-}
-
-// one cascade step on the host (long double) -- used to build the transition matrix
-static void host_step(const IirHandle *h, std::vector<long double> &z, long double x)
-{
-    const int ORD = h->order;
-    for (int s = 0; s < h->nsec; ++s) {
-        const double *c = h->coef.data() + (size_t)s * (2 * ORD + 1);
-        const long double xn = x;
-        const long double yv = (long double)c[0] * xn + z[s * ORD];
-        for (int k = 1; k < ORD; ++k) z[s * ORD + k - 1] = (long double)c[k] * xn - (long double)c[ORD + k] * yv + z[s * ORD + k];
-        z[s * ORD + ORD - 1] = (long double)c[ORD] * xn - (long double)c[2 * ORD] * yv;
-        x = yv;
-    }
-}
-
-static void matmul_ld(const std::vector<long double> &A, const std::vector<long double> &B, std::vector<long double> &C, int D)
-{
-    std::vector<long double> R((size_t)D * D, 0.0L);
-    for (int i = 0; i < D; ++i)
-        for (int k = 0; k < D; ++k) {
-            const long double a = A[(size_t)i * D + k];
-            if (a == 0.0L) continue;
-            for (int j = 0; j < D; ++j) R[(size_t)i * D + j] += a * B[(size_t)k * D + j];
-        }
-    C.swap(R);
-}
-
-static int ensure_plan(IirHandle *h)
-{
-    if (h->plan) return SKDSP_OK;
-    IirPlan *p = new IirPlan();
-    p->nsec = h->nsec; p->order = h->order; p->D = h->nsec * h->order;
-    const int D = p->D;
-    // one-step transition: column i = state after a zero-input step from e_i
-    p->A_host.assign((size_t)D * D, 0.0);
-    for (int i = 0; i < D; ++i) {
-        std::vector<long double> z(D, 0.0L);
-        z[i] = 1.0L;
-        host_step(h, z, 0.0L);
-        for (int r = 0; r < D; ++r) p->A_host[(size_t)r * D + i] = (double)z[r];
-    }
-    hipError_t e;
-    if ((e = hipMalloc((void **)&p->pw_dev, (size_t)kPowers * D * D * 8)) != hipSuccess ||
-        (e = hipMalloc((void **)&p->pwa_dev, (size_t)8 * 4 * 64 * 8)) != hipSuccess ||
-        (e = hipMalloc((void **)&p->lb_dev, (size_t)8 * D * D * 8)) != hipSuccess ||
-        (e = hipMalloc((void **)&p->lbk_dev, (size_t)32 * D * D * 8)) != hipSuccess ||
-        (e = hipMalloc((void **)&p->state_dev, (size_t)4 * D * 8)) != hipSuccess ||
-        (e = hipMalloc((void **)&p->agg_dev, (size_t)2 * 2 * kMaxW * D * 8)) != hipSuccess) {
-        iir_free(p);
-        return hip_fail(e, "hipMalloc(iir plan)", __FILE__, __LINE__);
-    }
-    h->plan = p;
-    return SKDSP_OK;
-}
-
-// matrix powers M^(2^l), M = A^T, l = 0..16, for chunk length T (cached)
-static int ensure_powers(IirHandle *h, int64_t T, hipStream_t s)
-{
-    IirPlan *p = h->plan;
-    if (p->cached_T == T) return SKDSP_OK;
-    const int D = p->D;
-    std::vector<long double> base((size_t)D * D), M((size_t)D * D, 0.0L);
-    for (size_t i = 0; i < base.size(); ++i) base[i] = p->A_host[i];
-    for (int i = 0; i < D; ++i) M[(size_t)i * D + i] = 1.0L;
-    // M = A^T by binary exponentiation
-    int64_t e = T;
-    std::vector<long double> sq = base;
-    while (e) {
-        if (e & 1) matmul_ld(M, sq, M, D);
-        e >>= 1;
-        if (e) matmul_ld(sq, sq, sq, D);
-    }
-    {   // M^k, k = 0..31, transposed so that lane k reads entry (i,j) at [(i*D+j)*32 + k]
-        std::vector<long double> Pk((size_t)D * D, 0.0L);
-        for (int i = 0; i < D; ++i) Pk[(size_t)i * D + i] = 1.0L;
-        std::vector<double> lbk((size_t)32 * D * D);
-        for (int k = 0; k < 32; ++k) {
-            for (size_t i = 0; i < (size_t)D * D; ++i) lbk[i * 32 + k] = std::isfinite((double)Pk[i]) ? (double)Pk[i] : 0.0;
-            matmul_ld(Pk, M, Pk, D);
-        }
-        SK_HIP(hipMemcpyAsync(p->lbk_dev, lbk.data(), lbk.size() * 8, hipMemcpyHostToDevice, s));
-        SK_HIP(hipStreamSynchronize(s));
-    }
-    p->gt_T = -1;
-    if (D <= 32 && (T % kMmPiece == 0 || T == 64 || T == 32)) {
-        // G[:, k] = A^(T-1-k) b, b = the state one sample x = 1 leaves behind; stored as the MFMA A operand
-        // of step s = k / 4: lane l holds row l & 15, column 4 s + (l >> 4)
-        std::vector<long double> g(D, 0.0L);
-        host_step(h, g, 1.0L);
-        const int NT = D > 16 ? 2 : 1;
-        std::vector<double> gt((size_t)NT * T * 16, 0.0);
-        for (int64_t k = T - 1; k >= 0; --k) {
-            for (int d = 0; d < D; ++d) {
-                const long double v = g[d];
-                gt[(size_t)(d / 16) * T * 16 + (size_t)(k / 4) * 64 + (size_t)(k % 4) * 16 + (d % 16)] =
-                    std::isfinite((double)v) ? (double)v : 0.0;
-            }
-            host_step(h, g, 0.0L);  // g <- A g
-        }
-        if (gt.size() * 8 > p->gt_cap) {
-            if (p->gt_dev) SK_HIP(hipFree(p->gt_dev));
-            p->gt_dev = nullptr; p->gt_cap = 0;
-            SK_HIP(hipMalloc((void **)&p->gt_dev, gt.size() * 8));
-            p->gt_cap = gt.size() * 8;
-        }
-        SK_HIP(hipMemcpyAsync(p->gt_dev, gt.data(), gt.size() * 8, hipMemcpyHostToDevice, s));
-        SK_HIP(hipStreamSynchronize(s));
-        p->gt_T = T;
-    }
-    // A transition power counts as vanished when its largest entry is below `negl`: 1e-30 for float64 signals (nothing a
-    // float64 recurrence could resolve), 1e-18 for float32 signals (the dropped term is under a tenth of an ulp of the
-    // float64 STATE it would be added to, and eleven orders below the float32 rounding of the output) -- for the config-4
-    // cascade (pole radius 0.99465) that is 60 chunks of 128 samples instead of 101: one scan level less.
-    const long double negl = dtype_double(h->dtype) ? 1e-30L : 1e-18L;
-    std::vector<double> pw((size_t)kPowers * D * D);
-    p->n_lv = kPowers;
-    for (int l = 0; l < kPowers; ++l) {
-        long double mx = 0.0L;
-        for (auto v : M) mx = fabsl(v) > mx ? fabsl(v) : mx;
-        if (std::isfinite((double)mx) && mx < negl && l < p->n_lv) p->n_lv = l;
-        for (size_t i = 0; i < (size_t)D * D; ++i) {
-            long double v = M[i];
-            if (!std::isfinite((double)v)) v = 0.0L;  // unstable filter overflow: the reference overflows too
-            pw[(size_t)l * D * D + i] = (double)v;
-        }
-        if (l + 1 < kPowers) matmul_ld(M, M, M, D);
-    }
-    // carry look-back: (M^256)^k until every entry is below 1e-30 (its contribution is then far
-    // under one ulp of anything the float64 recurrence itself could resolve)
-    {
-        std::vector<long double> Mw((size_t)D * D), Pk;
-        for (size_t i = 0; i < (size_t)D * D; ++i) Mw[i] = pw[(size_t)8 * D * D + i];
-        Pk = Mw;
-        std::vector<double> lb((size_t)8 * D * D, 0.0);
-        p->n_lb = 0;
-        for (int k = 1; k <= 8; ++k) {  // Pk = Mw^k
-            long double mx = 0.0L;
-            for (auto v : Pk) mx = fabsl(v) > mx ? fabsl(v) : mx;
-            if (!(mx >= negl)) { p->n_lb = k; break; }  // terms k.. are negligible: keep k terms (0..k-1)
-            if (k == 8) break;
-            for (size_t i = 0; i < (size_t)D * D; ++i) lb[(size_t)(k - 1) * D * D + i] = (double)Pk[i];
-            matmul_ld(Pk, Mw, Pk, D);
-        }
-        SK_HIP(hipMemcpyAsync(p->lb_dev, lb.data(), lb.size() * 8, hipMemcpyHostToDevice, s));
-        SK_HIP(hipStreamSynchronize(s));
-    }
-    SK_HIP(hipMemcpyAsync(p->pw_dev, pw.data(), pw.size() * 8, hipMemcpyHostToDevice, s));
-    std::vector<double> pwa((size_t)8 * 4 * 64, 0.0);
-    if (D <= 16) {  // the same powers as A operands of v_mfma_f64_16x16x4: step r of level l, lane t: M_l[t & 15][4 r + (t >> 4)]
-        for (int l = 0; l < 8; ++l)
-            for (int r = 0; r < 4; ++r)
-                for (int t = 0; t < 64; ++t) {
-                    const int row = t & 15, col = 4 * r + (t >> 4);
-                    if (row < D && col < D) pwa[((size_t)l * 4 + r) * 64 + t] = pw[(size_t)l * D * D + (size_t)row * D + col];
-                }
-    }
-    SK_HIP(hipMemcpyAsync(p->pwa_dev, pwa.data(), pwa.size() * 8, hipMemcpyHostToDevice, s));
-    SK_HIP(hipStreamSynchronize(s));  // pw / pwa are stack-lifetime host buffers
-    p->cached_T = T;
-    return SKDSP_OK;
-}
-
-#endif  // SK_SCAN_PART != 2
-
+// ------------------------------------------------------------------ launch
+// The two-pass sequence for finished arguments and a decided form (iir_common.hpp: ScanLaunch; the decision is iir_route.hpp, the plan and
+// the arguments are made by iir_api.hip).  What is asked for must be what the rules of iir_scan_plan.hpp allow.
 template <int NSEC, int ORD, typename IO>
-static int launch_shape(IirHandle *h, IirArgs &a, int nbatch, int W, hipStream_t s)
+static int launch_shape(const ScanLaunch &L, IirArgs &a, hipStream_t s)
 {
     constexpr int D = NSEC * ORD;
     Coef<NSEC, ORD> cf;
-    std::memcpy(cf.c, h->coef.data(), sizeof(cf.c));
-    IirPlan *p = h->plan;
-    double *agg = p->agg_dev;
-    double *carry = p->agg_dev + (size_t)2 * kMaxW * D;
-    a.agg = agg;
-    a.carry = carry;
-    a.lbmat = p->lb_dev;
-    a.n_lb = p->n_lb;
-    a.n_lv = p->n_lv < 8 ? p->n_lv : 8;
-    // aggregate-free mode: matrix-pipe K1, carries from the chunk states themselves, unchanged K3
-    const bool fast = p->n_lv <= 5 && D <= 32 && ORD == 2 && a.T % kMmPiece == 0 && p->gt_T == a.T && !opt().iir_no_mfma;
+    std::memcpy(cf.c, L.coef, sizeof(cf.c));
+    const int nbatch = L.nbatch, W = L.W;
+    const bool fast = L.form.fast, unit = NSEC >= 2 && L.form.unit_tail;
+    const ScanFacts facts{L.n_lv, a.n_lb, L.gt_T};
+    SK_CHECK(L.form.k1 == scan_k1(fast, a.il != 0, D, a.T) && (!fast || scan_fast(facts, D, ORD, a.T, 0)) &&
+                 (!a.il || (nbatch == 2 && scan_interleaved_applies(fast, a.T))),
+             SKDSP_ERR_UNSUPPORTED, "iir_scan: the two-pass kernels asked for do not take this call (%d sections, chunks of %lld)", NSEC, (long long)a.T);
+    const int64_t waves = (a.J + 15) / 16;
     if (a.il) {
-        if (!fast || a.T % 64 != 0) return 1;  // not applicable (error codes are negative): the caller takes the planar detour
-        const int64_t waves = (a.J + 15) / 16;
         if (D <= 16)
             hipLaunchKernelGGL((iir_k1c_mfma_kernel<IO, 1>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, (const IO *)a.x, a.n, a.T,
-                               a.J, (const double *)p->gt_dev, a.v, D);
+                               a.J, L.gt, a.v, D);
         else
             hipLaunchKernelGGL((iir_k1c_mfma_kernel<IO, 2>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, (const IO *)a.x, a.n, a.T,
-                               a.J, (const double *)p->gt_dev, a.v, D);
+                               a.J, L.gt, a.v, D);
         SK_HIP(hipGetLastError());
-        hipLaunchKernelGGL((iir_carry_kernel<D, ORD>), dim3(W, 2), dim3(256), 0, s, (const double *)a.v, (const double *)p->lbk_dev, a.J,
-                           a.zi, carry);
-        a.n_lb = 0;
-        if (NSEC >= 2 && h->unit_tail) hipLaunchKernelGGL((iir_k3c_kernel<NSEC, ORD, IO, (NSEC >= 2)>), dim3(W), dim3(kIirThreads), 0, s, a, cf);
+        hipLaunchKernelGGL((iir_carry_kernel<D, ORD>), dim3(W, 2), dim3(256), 0, s, (const double *)a.v, L.lbk, a.J, a.zi, (double *)a.carry);
+        if (unit) hipLaunchKernelGGL((iir_k3c_kernel<NSEC, ORD, IO, (NSEC >= 2)>), dim3(W), dim3(kIirThreads), 0, s, a, cf);
         else hipLaunchKernelGGL((iir_k3c_kernel<NSEC, ORD, IO>), dim3(W), dim3(kIirThreads), 0, s, a, cf);
         SK_HIP(hipGetLastError());
         return SKDSP_OK;
     }
     if (fast) {
-        const int64_t waves = (a.J + 15) / 16;
-        const bool no_k1r = false;
-        const int np = (int)(a.T / kMmPiece);
-        if (D <= 16 && !no_k1r && (np == 1 || np == 2 || np == 4) && a.T == (int64_t)np * kMmPiece) {
-            // G in registers: persistent workgroups (3 per CU), each iteration 4 / np groups of 16 chunks
+        if (L.form.k1 == kK1Regs) {
+            // G in registers: persistent workgroups (2 per CU), each iteration 4 / np groups of 16 chunks
+            const int np = (int)(a.T / kMmPiece);
             const int64_t ngroups = waves, per_wg = 4 / np;
             const int wgs_per_cu = 2;
-            const unsigned grid = (unsigned)std::min<int64_t>((ngroups + per_wg - 1) / per_wg, (int64_t)wgs_per_cu * ctx().num_cus);
-#define SK_K1R(NP) hipLaunchKernelGGL((iir_k1r_kernel<IO, NP>), dim3(grid, nbatch), dim3(256), 0, s, (const IO *)a.x, a.n, a.J, a.batch_stride, (const double *)p->gt_dev, a.v, D)
+            const unsigned grid = (unsigned)std::min<int64_t>((ngroups + per_wg - 1) / per_wg, (int64_t)wgs_per_cu * L.num_cus);
+#define SK_K1R(NP) hipLaunchKernelGGL((iir_k1r_kernel<IO, NP>), dim3(grid, nbatch), dim3(256), 0, s, (const IO *)a.x, a.n, a.J, a.batch_stride, L.gt, a.v, D)
             if (np == 1) SK_K1R(1);
             else if (np == 2) SK_K1R(2);
             else SK_K1R(4);
 #undef SK_K1R
         } else if (D <= 16)
             hipLaunchKernelGGL((iir_k1_mfma_kernel<IO, 1>), dim3((unsigned)((waves + 3) / 4), nbatch), dim3(256), 0, s, (const IO *)a.x,
-                               a.n, a.T, a.J, a.batch_stride, (const double *)p->gt_dev, a.v, D);
+                               a.n, a.T, a.J, a.batch_stride, L.gt, a.v, D);
         else
             hipLaunchKernelGGL((iir_k1_mfma_kernel<IO, 2>), dim3((unsigned)((waves + 3) / 4), nbatch), dim3(256), 0, s, (const IO *)a.x,
-                               a.n, a.T, a.J, a.batch_stride, (const double *)p->gt_dev, a.v, D);
+                               a.n, a.T, a.J, a.batch_stride, L.gt, a.v, D);
         SK_HIP(hipGetLastError());
-        hipLaunchKernelGGL((iir_carry_kernel<D, ORD>), dim3(W, nbatch), dim3(256), 0, s, (const double *)a.v, (const double *)p->lbk_dev,
-                           a.J, a.zi, carry);
-        a.n_lb = 0;  // K3 reads the carries
+        hipLaunchKernelGGL((iir_carry_kernel<D, ORD>), dim3(W, nbatch), dim3(256), 0, s, (const double *)a.v, L.lbk, a.J, a.zi, (double *)a.carry);
     } else {
         hipLaunchKernelGGL((iir_chunk_kernel<NSEC, ORD, IO, false>), dim3(W, nbatch), dim3(kIirThreads), 0, s, a, cf);
     }
     SK_HIP(hipGetLastError());
-    if (p->n_lb == 0 && !fast) {  // slowly decaying / marginally stable filter: full scan of the workgroup aggregates
-        hipLaunchKernelGGL((iir_wg_scan_kernel<D>), dim3(nbatch), dim3(1024), 0, s, (const double *)agg, (const double *)p->pw_dev, W, carry, a.zi);
+    if (a.n_lb == 0 && !fast) {  // slowly decaying / marginally stable filter: full scan of the workgroup aggregates
+        hipLaunchKernelGGL((iir_wg_scan_kernel<D>), dim3(nbatch), dim3(1024), 0, s, (const double *)a.agg, a.pw, W, (double *)a.carry, a.zi);
         SK_HIP(hipGetLastError());
     }
-    if (NSEC >= 2 && h->unit_tail) hipLaunchKernelGGL((iir_chunk_kernel<NSEC, ORD, IO, true, (NSEC >= 2)>), dim3(W, nbatch), dim3(kIirThreads), 0, s, a, cf);
+    if (unit) hipLaunchKernelGGL((iir_chunk_kernel<NSEC, ORD, IO, true, (NSEC >= 2)>), dim3(W, nbatch), dim3(kIirThreads), 0, s, a, cf);
     else hipLaunchKernelGGL((iir_chunk_kernel<NSEC, ORD, IO, true>), dim3(W, nbatch), dim3(kIirThreads), 0, s, a, cf);
     SK_HIP(hipGetLastError());
     return SKDSP_OK;
 }
 
 template <typename IO>
-static int dispatch_shape(IirHandle *h, IirArgs &a, int nbatch, int W, hipStream_t s)
+static int dispatch_shape(const ScanLaunch &L, IirArgs &a, hipStream_t s)
 {
-#define SK_SOS(N) case N: return launch_shape<N, 2, IO>(h, a, nbatch, W, s);
-    if (h->order == 2) {
-        switch (h->nsec) {
+#define SK_SOS(N) case N: return launch_shape<N, 2, IO>(L, a, s);
+    if (L.order == 2) {
+        switch (L.nsec) {
             SK_SOS(1) SK_SOS(2) SK_SOS(3) SK_SOS(4) SK_SOS(5) SK_SOS(6) SK_SOS(7) SK_SOS(8) SK_SOS(9) SK_SOS(10) SK_SOS(11) SK_SOS(12)
         }
     }
 #undef SK_SOS
-    SK_CHECK(false, SKDSP_ERR_UNSUPPORTED, "iir: unsupported cascade shape (%d sections of order %d)", h->nsec, h->order);
+    SK_CHECK(false, SKDSP_ERR_UNSUPPORTED, "iir: unsupported cascade shape (%d sections of order %d)", L.nsec, L.order);
 }
 
-// the float64 half of the dispatch lives in its own object (SK_SCAN_PART)
-int iir_dispatch_shape_f64(IirHandle *h, IirArgs &a, int nbatch, int W, hipStream_t s);
-#if SK_SCAN_PART != 1
-int iir_dispatch_shape_f64(IirHandle *h, IirArgs &a, int nbatch, int W, hipStream_t s) { return dispatch_shape<double>(h, a, nbatch, W, s); }
+// each precision's kernels live in an object of their own (SK_SCAN_PART): what this object instantiates
+#if SK_SCAN_PART == 0 || SK_SCAN_PART == 1
+int iir_scan_launch_f32(const ScanLaunch &L, IirArgs &a, hipStream_t s) { return dispatch_shape<float>(L, a, s); }
 #endif
-
-#if SK_SCAN_PART != 2
-// x_dev/y_dev: real planar arrays (float or double per h->dtype's precision); complex
-// callers deinterleave first (iir_api.hip) and pass nbatch = 2 with batch_stride.
-int iir_launch_planar(IirHandle *h, const void *x, int64_t n, int nbatch, int64_t batch_stride, void *y, hipStream_t s,
-                      const double *zi_host, double *zf_host, int interleaved, int dec)
-{
-    if (n <= 0) {
-        if (zf_host) {
-            if (zi_host) memcpy(zf_host, zi_host, (size_t)nbatch * h->nsec * h->order * 8);
-            else memset(zf_host, 0, (size_t)nbatch * h->nsec * h->order * 8);
-        }
-        return SKDSP_OK;
-    }
-    if (h->seq) {   // an ill-conditioned cascade: the reference's own recursion (iir_seq.hip)
-        if (interleaved) return 1;
-        return iir_seq_launch(h, x, n, nbatch, batch_stride, batch_stride, y, s, zi_host, zf_host, dec);
-    }
-    if (h->twin64) {
-        // the float64 detour (see IirHandle::twin64): planar float32 in, planar float32 out
-        if (interleaved) return 1;
-        const int64_t tot = nbatch > 1 ? batch_stride * nbatch : n;
-        auto grow = [&](void *&p, size_t &have, size_t need) -> int {
-            if (need <= have) return SKDSP_OK;
-            if (p) {
-                SK_HIP(hipStreamSynchronize(s));
-                SK_HIP(hipFree(p));
-                p = nullptr; have = 0;
-            }
-            SK_HIP(hipMalloc(&p, need));
-            have = need;
-            return SKDSP_OK;
-        };
-        int rc = grow(h->twin_in, h->twin_in_bytes, (size_t)tot * 8 + 256);
-        if (rc) return rc;
-        if ((rc = convert_launch(x, h->twin_in, tot, true, s))) return rc;
-        void *o64 = h->twin_in;
-        int64_t out_tot = tot;
-        if (dec > 1) {   // (one real row: the kept outputs go to a buffer of their own)
-            out_tot = n / dec;
-            if ((rc = grow(h->twin_out, h->twin_out_bytes, (size_t)out_tot * 8 + 256))) return rc;
-            o64 = h->twin_out;
-        }
-        if ((rc = iir_launch_planar(h->twin64, h->twin_in, n, nbatch, batch_stride, o64, s, zi_host, zf_host, 0, dec))) return rc;
-        return convert_launch(o64, y, out_tot, false, s);
-    }
-    if (!h->groups.empty()) {
-        // consecutive groups of sections, each through this function: group 0 reads x, the others filter y in place; a decimating call keeps
-        // the full-rate signal of all groups but the last in a buffer of the handle; the states are per section, so a group takes its slice
-        if (interleaved) return 1;   // (the caller's planar form splits; an interleaved group chain could stop half-way through "not applicable")
-        const int D = h->nsec * 2;
-        const size_t esz = dtype_double(h->dtype) ? 8 : 4;
-        void *mid = y;
-        if (dec > 1) {
-            const size_t need = (size_t)(nbatch > 1 ? batch_stride * nbatch : n) * esz + 256;
-            if (need > h->group_tmp_bytes) {
-                if (h->group_tmp) {
-                    SK_HIP(hipStreamSynchronize(s));
-                    SK_HIP(hipFree(h->group_tmp));
-                    h->group_tmp = nullptr; h->group_tmp_bytes = 0;
-                }
-                SK_HIP(hipMalloc(&h->group_tmp, need));
-                h->group_tmp_bytes = need;
-            }
-            mid = h->group_tmp;
-        }
-        std::vector<double> zi_g, zf_g;
-        for (size_t gi = 0; gi < h->groups.size(); ++gi) {
-            IirHandle *g = h->groups[gi];
-            const bool last = gi + 1 == h->groups.size();
-            const int Dg = g->nsec * 2;
-            const double *zi_p = nullptr;
-            double *zf_p = nullptr;
-            if (zi_host) {
-                zi_g.resize((size_t)nbatch * Dg);
-                for (int b = 0; b < nbatch; ++b) memcpy(zi_g.data() + (size_t)b * Dg, zi_host + (size_t)b * D + 2 * g->group_first, (size_t)Dg * 8);
-                zi_p = zi_g.data();
-            }
-            if (zf_host) {
-                zf_g.assign((size_t)nbatch * Dg, 0.0);
-                zf_p = zf_g.data();
-            }
-            const int rc = iir_launch_planar(g, gi == 0 ? x : mid, n, nbatch, batch_stride, last ? y : mid, s, zi_p, zf_p, 0, last ? dec : 1);
-            if (rc) return rc;
-            if (zf_host)
-                for (int b = 0; b < nbatch; ++b) memcpy(zf_host + (size_t)b * D + 2 * g->group_first, zf_g.data() + (size_t)b * Dg, (size_t)Dg * 8);
-        }
-        return SKDSP_OK;
-    }
-    // Parallel form (iir_par.hip): the same transfer function as independent two-state branches, every wave its own segment.
-    // No state crosses these calls (scipy's zi / zf live in the cascade's coordinates: such calls keep the kernels below).
-    if (zi_host == nullptr && zf_host == nullptr && opt().iir_par > 0 && h->order == 2 && h->nsec <= 8 &&
-        (interleaved || dec <= 1 || nbatch == 1)) {
-        // (interleaved complex: re and im are two independent real signals on one memory stream: lanes alternate between them;
-        // with dec > 1 only where a segment's kept outputs fit the wave's stage image -- else 1 comes back)
-        const int r = interleaved ? iir_par_launch(h, x, n, 1, 0, 0, y, s, dec, 1)
-                                  : iir_par_launch(h, x, n, nbatch, batch_stride, batch_stride, y, s, dec);
-        if (r != 1) return r;   // (1 = not applicable: poles shared between sections, slow decay, ...)
-    }
-    int rc = ensure_plan(h);
-    if (rc) return rc;
-    IirPlan *p = h->plan;
-    const int D = p->D;
-    // Single-pass scan (one launch, x read once): real signals, <= 8 biquads whose transition over one 256-chunk segment
-    // is below 1e-30 (n_lb == 1 for the segment's chunk length), enough segments to fill the chip.
-    bool fused = false;
-    {
-        // chunk length: 128 float32 / 64 float64 samples (real), 64 complex64 / 32 complex128 samples (interleaved)
-        const int64_t Tf = (dtype_double(h->dtype) ? 64 : 128) / (interleaved ? 2 : 1);
-        int &fstate = interleaved ? p->fused_state_c : p->fused_state;   // applicability only (cached); the policy is per call
-        int &fnlv = interleaved ? p->fused_nlv_c : p->fused_nlv;
-        const bool wanted = h->order == 2 && D <= 16 && opt().iir_two_pass <= 0 && fstate >= 0 &&
-                            (dec <= 1 || ((nbatch == 1 || interleaved) && zf_host == nullptr)) &&
-                            n >= Tf * kIirThreads * (int64_t)ctx().num_cus;
-        if (wanted && fstate == 0) {
-            rc = ensure_powers(h, Tf, s);
-            if (rc) return rc;
-            fstate = (p->n_lb == 1 && p->gt_T == Tf) ? 1 : -1;
-            fnlv = p->n_lv;
-        }
-        if (wanted && fstate == 1) {
-            // Real signals: the single pass wins or ties everywhere it applies (tools/ab_iir.py, 2^26, same box): low-pass designs
-            // 0.11-0.13 vs 0.15 ms, float64 0.19-0.28 vs 0.36-0.42 ms; the 8-biquad elliptic band-pass of BASELINE config 4
-            // (6 scan levels of a 16 x 16 transition per 128-sample chunk) 0.175 vs 0.184 ms since its scan runs on the
-            // matrix pipe (iir_fused.hip: 0.197 ms with the per-thread VALU scan) -- and it moves 8 instead of 12 bytes per sample.
-            // interleaved complex64 (two scans per 64-sample chunk): 0.22-0.29 vs 0.42-0.45 ms for low-pass designs (<= 4
-            // levels), 0.56 vs 0.46 ms for the config-4 cascade (7 levels): those stay two-pass unless iir_two_pass = -1
-            fused = !(interleaved && !dtype_double(h->dtype) && fnlv >= 6 && opt().iir_two_pass >= 0);
-            if (fused) {
-                rc = ensure_powers(h, Tf, s);   // (a no-op unless a two-pass call re-made the tables for its chunk length)
-                if (rc) return rc;
-            }
-        }
-    }
-    int maxW = kMaxPairs / D;
-    if (maxW > kMaxW) maxW = kMaxW;
-    const int64_t maxChunks = (int64_t)maxW * kIirThreads;
-    int64_t T = (n + maxChunks - 1) / maxChunks;
-    T = ((T + kPiece - 1) / kPiece) * kPiece;
-    if (T < kPiece) T = kPiece;
-    if (T >= kMmPiece) T = ((T + kMmPiece - 1) / kMmPiece) * kMmPiece;  // whole 128-sample pieces for the matrix-pipe K1
-    const int64_t J = (n + T - 1) / T;
-    const int W = (int)((J + kIirThreads - 1) / kIirThreads);
-    if (!fused) {
-        rc = ensure_powers(h, T, s);
-        if (rc) return rc;
-    }
-    const size_t need = fused ? 0 : (size_t)nbatch * D * J * 8;
-    if (need > p->v_cap) {
-        if (p->v_dev) SK_HIP(hipFree(p->v_dev));
-        p->v_dev = nullptr; p->v_cap = 0;
-        SK_HIP(hipMalloc((void **)&p->v_dev, need));
-        p->v_cap = need;
-    }
-    IirArgs a;
-    a.x = x; a.y = y; a.n = n; a.T = T; a.J = J; a.batch_stride = batch_stride;
-    a.il = interleaved ? 1 : 0;
-    a.pw = p->pw_dev; a.v = p->v_dev; a.agg = nullptr; a.carry = nullptr; a.lbmat = nullptr; a.n_lb = 0; a.n_lv = 8;
-    a.zi = nullptr; a.zf = nullptr;
-    a.dec = dec > 1 ? dec : 1;
-    a.n_keep = (n / a.dec) * a.dec;
-    {
-        // rows between a thread's staged segments x T (the interleaved complex kernel stages 8 segments per row piece)
-        const int64_t step = (interleaved ? kIirThreads / 8 : kIirThreads / (kPiece / (16 / (dtype_double(h->dtype) ? 8 : 4)))) * T;
-        a.dec_dq = (int)(step / a.dec);
-        a.dec_dr = (int)(step % a.dec);
-    }
-    SK_CHECK(a.dec == 1 || (zf_host == nullptr && (interleaved || nbatch == 1)), SKDSP_ERR_UNSUPPORTED,
-             "iir: decimating store needs a real or interleaved complex signal and no state output");
-    std::vector<double> zi_int;  // the caller's DF2T states in the internal factorisation (IirHandle::state_scale)
-    if (zi_host) {
-        if (!h->state_scale.empty()) {
-            zi_int.resize((size_t)nbatch * D);
-            for (int b = 0; b < nbatch; ++b)
-                for (int d = 0; d < D; ++d) zi_int[(size_t)b * D + d] = zi_host[(size_t)b * D + d] * h->state_scale[d];
-            zi_host = zi_int.data();
-        }
-        SK_HIP(hipMemcpyAsync(p->state_dev, zi_host, (size_t)nbatch * D * 8, hipMemcpyHostToDevice, s));
-        if (!zi_int.empty()) SK_HIP(hipStreamSynchronize(s));  // zi_int is a local
-        a.zi = p->state_dev;
-    }
-    if (zf_host) a.zf = p->state_dev + 2 * D;
-    SK_CHECK(nbatch >= 1 && nbatch <= 2, SKDSP_ERR_BADARG, "iir: batch must be 1 or 2");
-    if (fused) {
-        rc = iir_fused_launch(h, x, n, nbatch, batch_stride, y, a.zi, a.zf, s, dec, interleaved);
-    } else {
-        rc = dtype_double(h->dtype) ? iir_dispatch_shape_f64(h, a, nbatch, W, s) : dispatch_shape<float>(h, a, nbatch, W, s);
-    }
-    if (rc) return rc;  // (1 = interleaved path not applicable, nothing was launched)
-    if (!fused) note_path("iir_scan");   // (recorded once the two-pass kernels WERE launched: iir_seq, the twin, the groups, iir_par and iir_fused note themselves)
-    if (zf_host) {
-        SK_HIP(hipMemcpyAsync(zf_host, p->state_dev + 2 * D, (size_t)nbatch * D * 8, hipMemcpyDeviceToHost, s));
-        SK_HIP(hipStreamSynchronize(s));
-        if (!h->state_scale.empty())
-            for (int b = 0; b < nbatch; ++b)
-                for (int d = 0; d < D; ++d) zf_host[(size_t)b * D + d] /= h->state_scale[d];
-    }
-    return SKDSP_OK;
-}
-
-#endif  // SK_SCAN_PART != 2
+#if SK_SCAN_PART == 0 || SK_SCAN_PART == 2
+int iir_scan_launch_f64(const ScanLaunch &L, IirArgs &a, hipStream_t s) { return dispatch_shape<double>(L, a, s); }
+#endif
 
 }  // namespace skdsp

@@ -296,7 +296,7 @@ int fir_bank_create(const void *taps, int ntaps, int taps_complex, const int64_t
 int fir_bank_launch(HandleBase *h, const void *x_dev, int64_t n, void *y_dev, int64_t row_stride, hipStream_t s);   // row j at y + j row_stride, n outputs each, from rest
 
 // ---- IIR -----------------------------------------------------------------
-struct IirPlan;  // iir_scan.hip
+struct IirPlan;  // iir_common.hpp
 struct IirHandle : HandleBase {
     int nsec = 0;   // number of cascaded sections
     int order = 0;  // order of each section (2 for SOS, K-1 for a transfer function)
@@ -331,24 +331,24 @@ struct IirHandle : HandleBase {
     size_t group_tmp_bytes = 0;
     ~IirHandle();
 };
-// x/y: real planar arrays in the handle's precision; complex callers pass nbatch=2 planes
-// (re, im) batch_stride elements apart.  In-place (y == x) is allowed.
-int iir_launch_planar(IirHandle *h, const void *x_dev, int64_t n, int nbatch, int64_t batch_stride, void *y_dev, hipStream_t s,
-                      const double *zi_host = nullptr, double *zf_host = nullptr,  // [nbatch][D] states (streaming)
-                      int interleaved = 0,   // 1: x / y interleaved complex, nbatch = 2; returns 1 if not applicable
-                      int dec = 1);          // > 1 (real signals): y receives only every dec-th output (n / dec samples)
+// Which engines a call runs is ONE decision (iir_route.hpp, standard headers only), made before the call's first kernel and executed by
+// iir_api.hip (iir_run), which also owns the plans, the workspaces and the state transfer.  The units below only launch: an engine that is
+// asked for a call it does not take returns SKDSP_ERR_UNSUPPORTED.  x / y: real rows or planes in the handle's precision (complex through
+// two planes: nrow = 2), or interleaved complex where an engine says so.  In-place (y == x) is allowed.
 void iir_free(IirPlan *p);
 // the reference's recursion, one wave per row (iir_seq.hip): handles with h->seq set
 int iir_seq_launch(IirHandle *h, const void *x_dev, int64_t n, int nrow, int64_t x_stride, int64_t y_stride, void *y_dev, hipStream_t s,
                    const double *zi_host = nullptr, double *zf_host = nullptr, int dec = 1);
 // Parallel-form single-pass scan (iir_par.hip): real signals, <= 8 biquads with simple poles, zero initial state, no state
-// output; nrow rows x_stride / y_stride elements apart in one launch.  Returns 1 when it does not apply (nothing launched).
-int iir_par_launch(IirHandle *h, const void *x_dev, int64_t n, int nrow, int64_t x_stride, int64_t y_stride, void *y_dev, hipStream_t s,
+// output; nrow rows x_stride / y_stride elements apart in one launch.  iir_par_takes: does it take this call (ParChoice::status == 0), and how
+// (the plan and its tables on first use); iir_par_launch: the launch of such a choice.
+struct ParChoice;   // iir_par_plan.hpp
+ParChoice iir_par_takes(IirHandle *h, int64_t n, int nrow, int dec, int interleaved, int up, hipStream_t s);
+int iir_par_launch(IirHandle *h, const ParChoice &c, const void *x_dev, int64_t n, int nrow, int64_t x_stride, int64_t y_stride, void *y_dev, hipStream_t s,
                    int dec = 1, int interleaved = 0,    // interleaved = 1: x / y interleaved complex, n complex samples, one row
                    int up = 1);                         // up > 1: x holds n / up samples, the launch filters up * upsample(x, up) (n outputs)
 int iir_par_expand_host(const double *coef, int nsec, double *out, int *accepted);   // host-only (tests): [c0, (a1,a2,r0,r1) x nsec, kappa, ir_err, v32_err at 128, at 96]: 5 + 4 nsec doubles
 void iir_par_free(ParPlan *p);
-bool iir_shape_supported(int nsec, int order);
 
 // ---- resamplers (resample.hip) ---------------------------------------------
 int upsample_launch(const void *x_dev, int64_t n, int L, int dtype, double scale, void *y_dev, hipStream_t s);

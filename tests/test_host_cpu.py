@@ -193,6 +193,30 @@ def test_fir_route_decisions_host_run(tmp_path):
     assert out.strip().endswith("OK"), out[-4000:]
 
 
+def test_iir_scan_plan_host_run(tmp_path):
+    """Compiles csrc/iir_scan_plan.hpp for the HOST (standard headers only) and runs the plan of the cascade scans on cascades whose
+    transition powers are known in closed form: every table entry by entry and layout by layout, the scan and look-back depths against
+    both negligibility limits, the block-triangular shape of the powers, the call geometry on both sides of each rounding rule, and the
+    rules that admit the matrix-pipe K1, the interleaved two-pass kernels and the single pass on both sides of each condition."""
+    exe = str(tmp_path / "iir_scan_plan_emul")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "scikit-dsp-comm_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "host", "iir_scan_plan_emul.cpp"), "-o", exe])
+    out = subprocess.run([exe], stdout=subprocess.PIPE).stdout.decode()
+    assert out.strip().endswith("OK"), out
+
+
+def test_iir_route_decisions_host_run(tmp_path):
+    """Compiles csrc/iir_route.hpp for the HOST (standard headers only) and runs the IIR routing decision over the whole recorded table
+    tests/iir_routes/mi355x.txt (tools/record_iir_routes.py: every call's engines as the device noted them before the decision was gathered
+    into that header, with the device's CU count): the same engines in the same order, no lazy fact asked twice in a call; and over
+    hand-written cases for what the engine names do not show (planes, workspaces, group and twin buffers, state slices, row blocks)."""
+    exe = str(tmp_path / "iir_route_emul")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "scikit-dsp-comm_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "host", "iir_route_emul.cpp"), "-o", exe])
+    out = subprocess.run([exe, os.path.join(ROOT, "tests", "iir_routes", "mi355x.txt")], stdout=subprocess.PIPE).stdout.decode()
+    assert out.strip().endswith("OK"), out[-4000:]
+
+
 def _v32_designs():
     """tests/golden/g18_v32_designs.npz (gen_golden_v32.py): name -> (sos, {chunk length: the three detuned tones the host model ranks worst})."""
     z = np.load(os.path.join(GOLDEN, "g18_v32_designs.npz"))
