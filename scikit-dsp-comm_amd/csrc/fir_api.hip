@@ -23,6 +23,13 @@ static FirRouteOptions fir_route_options()
 
 int fir_algo_for(const FirHandle *h, int64_t n) { return pick_fir_algo(fir_shape_of(h), n, fir_route_options()); }
 
+// the handles of tap segments and heads are made below; the device memory of a handle frees itself (dev_mem.hpp)
+FirHandle::~FirHandle()
+{
+    for (FirHandle *p : parts) delete p;
+    for (FirHandle *p : heads) delete p;
+}
+
 // ---- tap partitioning: filters longer than one launch takes ------------------------------------------------------
 // The reference accepts any tap count (lfilter(b,[1],x), multirate_helper.py:108).  One launch takes up to 4097 taps in
 // the overlap-save engine (float32 / complex64) and a few thousand in the float64 direct-form kernels (LDS window); a

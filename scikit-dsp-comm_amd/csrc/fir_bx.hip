@@ -621,49 +621,48 @@ static double bx_f16_val(unsigned short h)
 
 // A-operand table of one (L, M): At[((kb RT + rt) kBxPh + piece) 64 + lane] = 8 fp16 of row 16 rt + (lane & 15),
 // lags u = K - 1 - (32 kb + 8 (lane >> 4) + i); the taps are L b 2^te, te the power of two that puts the largest into [2^13, 2^14)
-static int get_bx_table(FirHandle *h, int L, int M, const FirHandle::BxTab **out)
+struct BxTab : TilePlan, BxGeometry {   // key = (L, M); the geometry is the base bx_geometry fills and bx_columns reads
+    float tap_inv = 0.0f;               // the taps' scale
+    DevTable<unsigned short> At;
+};
+static int get_bx_table(FirHandle *h, int L, int M, BxTab **out)
 {
-    for (auto &t : h->bx)
-        if (t.L == L && t.M == M) { *out = &t; return SKDSP_OK; }
-    FirHandle::BxTab t;
-    SK_CHECK(bx_geometry(fir_shape_of(h), L, M, &t), SKDSP_ERR_UNSUPPORTED, "fir_bx: L=%d M=%d not covered", L, M);
-    const int P = h->ntaps, T = (P + L - 1) / L, K = 32 * t.KB;
-    double tmax = 0.0;
-    for (int k = 0; k < P; ++k) tmax = std::max(tmax, std::fabs((double)L * h->taps_host[k]));
-    int te = 0;
-    if (tmax > 0.0 && std::isfinite(tmax)) {
-        int ex;
-        std::frexp(tmax, &ex);        // tmax = m 2^ex, m in [0.5, 1)
-        te = std::min(std::max(14 - ex, -100), 100);
-    }
-    t.tap_inv = (float)std::ldexp(1.0, -te);
-    std::vector<unsigned short> host((size_t)t.KB * t.RT * kBxPh * 64 * 8, 0);
-    for (int kb = 0; kb < t.KB; ++kb)
-        for (int rt = 0; rt < t.RT; ++rt)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int i = 0; i < 8; ++i) {
-                    const int r = 16 * rt + (lane & 15);
-                    if (r >= t.RS) continue;
-                    const int u = K - 1 - (32 * kb + 8 * (lane >> 4) + i);
-                    const int ds = r / t.Lp, c = r % t.Lp;
-                    const int64_t cm = (int64_t)c * M;
-                    const int phi = (int)(cm % L), ic = (int)(cm / L);
-                    const int tt = u - t.U0 + ic + t.q * ds;
-                    if (tt < 0 || tt >= T) continue;
-                    const int k = phi + L * tt;
-                    if (k >= P) continue;
-                    double v = std::ldexp((double)L * h->taps_host[k], te);
-                    for (int p = 0; p < kBxPh; ++p) {   // (the second piece: the residual lifted by 2^11, see kBxLift)
-                        const unsigned short piece = bx_f16_rne(v);
-                        host[((((size_t)kb * t.RT + rt) * kBxPh + p) * 64 + lane) * 8 + i] = piece;
-                        v = std::ldexp(v - bx_f16_val(piece), kBxLift);
+    return tile_plan(h->bx, plan_key(L, M), out, [&](BxTab &t) -> int {
+        SK_CHECK(bx_geometry(fir_shape_of(h), L, M, &t), SKDSP_ERR_UNSUPPORTED, "fir_bx: L=%d M=%d not covered", L, M);
+        const int P = h->ntaps, T = (P + L - 1) / L, K = 32 * t.KB;
+        double tmax = 0.0;
+        for (int k = 0; k < P; ++k) tmax = std::max(tmax, std::fabs((double)L * h->taps_host[k]));
+        int te = 0;
+        if (tmax > 0.0 && std::isfinite(tmax)) {
+            int ex;
+            std::frexp(tmax, &ex);        // tmax = m 2^ex, m in [0.5, 1)
+            te = std::min(std::max(14 - ex, -100), 100);
+        }
+        t.tap_inv = (float)std::ldexp(1.0, -te);
+        std::vector<unsigned short> host((size_t)t.KB * t.RT * kBxPh * 64 * 8, 0);
+        for (int kb = 0; kb < t.KB; ++kb)
+            for (int rt = 0; rt < t.RT; ++rt)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int i = 0; i < 8; ++i) {
+                        const int r = 16 * rt + (lane & 15);
+                        if (r >= t.RS) continue;
+                        const int u = K - 1 - (32 * kb + 8 * (lane >> 4) + i);
+                        const int ds = r / t.Lp, c = r % t.Lp;
+                        const int64_t cm = (int64_t)c * M;
+                        const int phi = (int)(cm % L), ic = (int)(cm / L);
+                        const int tt = u - t.U0 + ic + t.q * ds;
+                        if (tt < 0 || tt >= T) continue;
+                        const int k = phi + L * tt;
+                        if (k >= P) continue;
+                        double v = std::ldexp((double)L * h->taps_host[k], te);
+                        for (int p = 0; p < kBxPh; ++p) {   // (the second piece: the residual lifted by 2^11, see kBxLift)
+                            const unsigned short piece = bx_f16_rne(v);
+                            host[((((size_t)kb * t.RT + rt) * kBxPh + p) * 64 + lane) * 8 + i] = piece;
+                            v = std::ldexp(v - bx_f16_val(piece), kBxLift);
+                        }
                     }
-                }
-    SK_HIP(hipMalloc(&t.At, host.size() * 2));
-    SK_HIP(hipMemcpy(t.At, host.data(), host.size() * 2, hipMemcpyHostToDevice));
-    h->bx.push_back(t);
-    *out = &h->bx.back();
-    return SKDSP_OK;
+        return t.At.upload(host);
+    });
 }
 
 template <bool CPLX, int KB, int RT, int RSP, int KSP = 1, bool T16 = false>
@@ -731,7 +730,7 @@ int fir_bx_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, int L,
 {
     note_path("fir_bx");
     if (n_out <= 0) return SKDSP_OK;
-    const FirHandle::BxTab *t = nullptr;
+    BxTab *t = nullptr;
     int rc = get_bx_table(h, L, M, &t);
     if (rc) return rc;
     const bool cplx = dtype_complex(h->dtype);
@@ -755,8 +754,8 @@ int fir_bx_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, int L,
     const int64_t ncols = (n_out + a.RS - 1) / a.RS;
     const int64_t nwin = (ncols + a.NS - 1) / a.NS;
     const unsigned grid = (unsigned)std::min<int64_t>(nwin, (int64_t)2 * ctx().num_cus);  // persistent: two per CU
-    const bool ok = cplx ? bx_dispatch<true>(t->KB / t->KSP, t->RT / t->RSP, t->RSP, t->KSP, grid, lds, s, x, t->At, a, y)
-                         : bx_dispatch<false>(t->KB / t->KSP, t->RT / t->RSP, t->RSP, t->KSP, grid, lds, s, x, t->At, a, y);
+    const bool ok = cplx ? bx_dispatch<true>(t->KB / t->KSP, t->RT / t->RSP, t->RSP, t->KSP, grid, lds, s, x, t->At.dev, a, y)
+                         : bx_dispatch<false>(t->KB / t->KSP, t->RT / t->RSP, t->RSP, t->KSP, grid, lds, s, x, t->At.dev, a, y);
     SK_CHECK(ok, SKDSP_ERR_UNSUPPORTED, "fir_bx: no kernel for %d blocks x %d row tiles", t->KB, t->RT);
     SK_HIP(hipGetLastError());
     return SKDSP_OK;

@@ -595,62 +595,55 @@ __global__ __launch_bounds__(256) void fir_sw_kernel(const X *__restrict__ x, co
 }
 
 // ------------------------------------------------------------------ host side
-FirHandle::~FirHandle()
-{
-    for (auto &p : poly) if (p.dev) (void)hipFree(p.dev);
-    for (auto &t : sw) { if (t.taps) (void)hipFree(t.taps); if (t.rho) (void)hipFree(t.rho); }
-    for (auto &t : mm) if (t.At) (void)hipFree(t.At);
-    for (auto &t : bx) if (t.At) (void)hipFree(t.At);
-    if (ols) fir_ols_free(ols);
-    for (auto &u : ols_up) fir_ols_free(u.plan);
-    if (ols64) fir_ols64_free(ols64);
-    for (auto &u : ols64_up) fir_ols64_free(u.plan);
-    for (FirHandle *p : parts) delete p;
-    for (FirHandle *p : heads) delete p;
-    if (taps64_dev) (void)hipFree(taps64_dev);
-}
-
 int fir_careful(FirHandle *h, CarefulFir *out)
 {
-    if (!h->taps64_dev) {
-        const size_t bytes = h->taps_host.size() * sizeof(double);
-        SK_HIP(hipMalloc(&h->taps64_dev, bytes));
-        SK_HIP(hipMemcpy(h->taps64_dev, h->taps_host.data(), bytes, hipMemcpyHostToDevice));
+    if (!h->taps64.dev) {
+        const int rc = h->taps64.upload(h->taps_host);
+        if (rc) return rc;
     }
-    out->taps = (const double *)h->taps64_dev;
+    out->taps = h->taps64.dev;
     out->ntaps = h->ntaps;
     out->taps_complex = h->taps_complex ? 1 : 0;
     return SKDSP_OK;
 }
 
+struct PolyBank : TilePlan {   // key = L
+    int T = 0;
+    DevTable<char> dev;        // taps in the compute precision
+};
+struct SwTab : TilePlan {      // key = (L, M, R)
+    DevTable<char> taps;
+    DevTable<int> rho;
+};
+
 // polyphase bank for interpolation factor L in the compute precision
 static int get_bank(FirHandle *h, int L, void **dev, int *T_out)
 {
-    for (auto &p : h->poly)
-        if (p.L == L) { *dev = p.dev; *T_out = p.T; return SKDSP_OK; }
-    const int P = h->ntaps;
-    const int T = (P + L - 1) / L;
-    const bool dbl = dtype_double(h->dtype);
-    const int comp = h->taps_complex ? 2 : 1;
-    const size_t esz = (dbl ? 8 : 4) * comp;
-    std::vector<char> host((size_t)L * T * esz, 0);
-    for (int phi = 0; phi < L; ++phi)
-        for (int t = 0; t < T; ++t) {
-            const int k = phi + L * t;
-            if (k >= P) continue;
-            for (int cc = 0; cc < comp; ++cc) {
-                const double v = h->taps_host[(size_t)k * comp + cc];
-                const size_t idx = ((size_t)phi * T + t) * comp + cc;
-                if (dbl) reinterpret_cast<double *>(host.data())[idx] = v;
-                else reinterpret_cast<float *>(host.data())[idx] = (float)v;
+    PolyBank *bank = nullptr;
+    const int rc = tile_plan(h->poly, plan_key(L), &bank, [&](PolyBank &p) {
+        const int P = h->ntaps;
+        const int T = (P + L - 1) / L;
+        const bool dbl = dtype_double(h->dtype);
+        const int comp = h->taps_complex ? 2 : 1;
+        const size_t esz = (dbl ? 8 : 4) * comp;
+        std::vector<char> host((size_t)L * T * esz, 0);
+        for (int phi = 0; phi < L; ++phi)
+            for (int t = 0; t < T; ++t) {
+                const int k = phi + L * t;
+                if (k >= P) continue;
+                for (int cc = 0; cc < comp; ++cc) {
+                    const double v = h->taps_host[(size_t)k * comp + cc];
+                    const size_t idx = ((size_t)phi * T + t) * comp + cc;
+                    if (dbl) reinterpret_cast<double *>(host.data())[idx] = v;
+                    else reinterpret_cast<float *>(host.data())[idx] = (float)v;
+                }
             }
-        }
-    void *d = nullptr;
-    SK_HIP(hipMalloc(&d, host.size()));
-    SK_HIP(hipMemcpy(d, host.data(), host.size(), hipMemcpyHostToDevice));
-    h->poly.push_back({L, T, d});
-    *dev = d;
-    *T_out = T;
+        p.T = T;
+        return p.dev.upload(host);
+    });
+    if (rc) return rc;
+    *dev = bank->dev.dev;
+    *T_out = bank->T;
     return SKDSP_OK;
 }
 
@@ -668,48 +661,41 @@ static int launch_typed(const X *x, const B *bank, const PolyArgs &a, int R, int
 
 // zero-padded per-(class, residue) tap tables for the sliding-window kernel:
 //   taps[(c q + j) nB R + m'] = b[phi_c + L (q (m' - delta) + j)]   (0 outside),  rho[c q + j] in [0,q) or -1
-static int get_sw_table(FirHandle *h, int L, int M, int R, int nB, const FirHandle::SwTab **out)
+static int get_sw_table(FirHandle *h, int L, int M, int R, int nB, SwTab **out)
 {
-    for (auto &t : h->sw)
-        if (t.L == L && t.M == M && t.R == R) { *out = &t; return SKDSP_OK; }
-    const int g = std::gcd(L, M), Lp = L / g, q = M / g;
-    const int P = h->ntaps, T = (P + L - 1) / L;
-    const bool dbl = dtype_double(h->dtype);
-    const int comp = h->taps_complex ? 2 : 1;
-    const size_t esz = (dbl ? 8 : 4) * comp;
-    const size_t pitch = (size_t)nB * R;
-    std::vector<char> host((size_t)Lp * q * pitch * esz, 0);
-    std::vector<int> rho((size_t)Lp * q, -1);
-    for (int c = 0; c < Lp; ++c) {
-        const long long cm = (long long)c * M;
-        const int phi = (int)(cm % L), ic = (int)(cm / L);
-        for (int j = 0; j < q; ++j) {
-            if (j >= T) continue;
-            const int delta = ic < j ? 1 : 0;
-            rho[(size_t)c * q + j] = ic - j + q * delta;
-            const int Tj = (T - j + q - 1) / q;
-            for (int m = 0; m < Tj; ++m) {
-                const int t = q * m + j;          // tap index inside the phase
-                const int k = phi + L * t;        // original tap
-                if (k >= P) continue;
-                const size_t idx0 = ((size_t)c * q + j) * pitch + (size_t)(m + delta);
-                for (int cc = 0; cc < comp; ++cc) {
-                    const double v = h->taps_host[(size_t)k * comp + cc];
-                    if (dbl) reinterpret_cast<double *>(host.data())[idx0 * comp + cc] = v;
-                    else reinterpret_cast<float *>(host.data())[idx0 * comp + cc] = (float)v;
+    return tile_plan(h->sw, plan_key(L, M, R), out, [&](SwTab &t) {
+        const int g = std::gcd(L, M), Lp = L / g, q = M / g;
+        const int P = h->ntaps, T = (P + L - 1) / L;
+        const bool dbl = dtype_double(h->dtype);
+        const int comp = h->taps_complex ? 2 : 1;
+        const size_t esz = (dbl ? 8 : 4) * comp;
+        const size_t pitch = (size_t)nB * R;
+        std::vector<char> host((size_t)Lp * q * pitch * esz, 0);
+        std::vector<int> rho((size_t)Lp * q, -1);
+        for (int c = 0; c < Lp; ++c) {
+            const long long cm = (long long)c * M;
+            const int phi = (int)(cm % L), ic = (int)(cm / L);
+            for (int j = 0; j < q; ++j) {
+                if (j >= T) continue;
+                const int delta = ic < j ? 1 : 0;
+                rho[(size_t)c * q + j] = ic - j + q * delta;
+                const int Tj = (T - j + q - 1) / q;
+                for (int m = 0; m < Tj; ++m) {
+                    const int t = q * m + j;          // tap index inside the phase
+                    const int k = phi + L * t;        // original tap
+                    if (k >= P) continue;
+                    const size_t idx0 = ((size_t)c * q + j) * pitch + (size_t)(m + delta);
+                    for (int cc = 0; cc < comp; ++cc) {
+                        const double v = h->taps_host[(size_t)k * comp + cc];
+                        if (dbl) reinterpret_cast<double *>(host.data())[idx0 * comp + cc] = v;
+                        else reinterpret_cast<float *>(host.data())[idx0 * comp + cc] = (float)v;
+                    }
                 }
             }
         }
-    }
-    FirHandle::SwTab t;
-    t.L = L; t.M = M; t.R = R; t.taps = nullptr; t.rho = nullptr;
-    SK_HIP(hipMalloc(&t.taps, host.size()));
-    SK_HIP(hipMalloc(&t.rho, rho.size() * sizeof(int)));
-    SK_HIP(hipMemcpy(t.taps, host.data(), host.size(), hipMemcpyHostToDevice));
-    SK_HIP(hipMemcpy(t.rho, rho.data(), rho.size() * sizeof(int), hipMemcpyHostToDevice));
-    h->sw.push_back(t);
-    *out = &h->sw.back();
-    return SKDSP_OK;
+        const int rc = t.taps.upload(host);
+        return rc ? rc : t.rho.upload(rho);
+    });
 }
 
 int fir_direct_launch(FirHandle *h, int tier, const void *x, int64_t n, int64_t n_hist, int L, int M, int64_t n_out, void *y,
@@ -755,7 +741,7 @@ int fir_direct_launch(FirHandle *h, int tier, const void *x, int64_t n, int64_t 
         const bool want_tile = a.Lp > 4;  // up to 4 classes the per-class row transposition measured faster
         const bool tile_fits = (size_t)phys * esz + 4096 + tile_bytes <= lds_cap;
         if (want_tile && !tile_fits && R > 2) continue;
-        const FirHandle::SwTab *tab = nullptr;
+        SwTab *tab = nullptr;
         int rc2 = get_sw_table(h, L, M, R, nB, &tab);
         if (rc2) return rc2;
         SwArgs w;
@@ -791,7 +777,7 @@ do {                                                                            
         (void)hipFuncSetAttribute((const void *)fir_sw_kernel<XT, BT, RR, QQ>,                                    \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
     hipLaunchKernelGGL((fir_sw_kernel<XT, BT, RR, QQ>), dim3((unsigned)nb), dim3(256), lds, s, (const XT *)x,     \
-                       (const BT *)tab->taps, (const int *)tab->rho, w, (XT *)y);                                 \
+                       (const BT *)tab->taps.dev, tab->rho.dev, w, (XT *)y);                                     \
 } while (0)
 #define SK_SWR(XT, BT, RR)                                   \
 do {                                                     \
@@ -812,7 +798,7 @@ do {                                                                            
         (void)hipFuncSetAttribute((const void *)fir_sw_kernel<float2, float, 8, QQ, LL>,                           \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                          \
     hipLaunchKernelGGL((fir_sw_kernel<float2, float, 8, QQ, LL>), dim3((unsigned)nb), dim3(256), lds, s,           \
-                       (const float2 *)x, (const float *)tab->taps, (const int *)tab->rho, w, (float2 *)y);        \
+                       (const float2 *)x, (const float *)tab->taps.dev, tab->rho.dev, w, (float2 *)y);            \
 } while (0)
 #define SK_SWLQ(LL)                                   \
 do {                                              \

@@ -198,50 +198,48 @@ __global__ __launch_bounds__(256) void fir_mm_kernel(const X *__restrict__ x, co
 }
 
 // A-operand table of one (L, M): At[ks][lane] = A[row = lane & 15][u = 4 ks + (lane >> 4)]
-static int get_mm_table(FirHandle *h, int L, int M, const FirHandle::MmTab **out)
+struct MmTab : TilePlan {   // key = (L, M)
+    int q, DS, RS, U0, K4;
+    DevTable<char> At;      // float32 or float64, the handle's precision
+};
+static int get_mm_table(FirHandle *h, int L, int M, MmTab **out)
 {
-    for (auto &t : h->mm)
-        if (t.L == L && t.M == M) { *out = &t; return SKDSP_OK; }
-    const int g = std::gcd(L, M), Lp = L / g, q = M / g;
-    const int P = h->ntaps, T = (P + L - 1) / L;
-    const int DS = 16 / Lp, RS = Lp * DS;
-    int imax = 0;
-    for (int c = 0; c < Lp; ++c) imax = std::max(imax, (int)(((int64_t)c * M) / L));
-    const int U0 = imax + q * (DS - 1);
-    const int K4 = ((T + U0 + 3) / 4 + 3) / 4 * 4;  // padded to the kernel instantiations (multiples of 4 steps)
-    const bool dbl = dtype_double(h->dtype);
-    std::vector<double> host((size_t)K4 * 64, 0.0);
-    for (int r = 0; r < RS; ++r) {
-        const int ds = r / Lp, c = r % Lp;
-        const int64_t cm = (int64_t)c * M;
-        const int phi = (int)(cm % L), ic = (int)(cm / L);
-        for (int u = 0; u < 4 * K4; ++u) {
-            const int t = u - U0 + ic + q * ds;
-            if (t < 0 || t >= T) continue;
-            const int k = phi + L * t;
-            if (k >= P) continue;
-            // MFMA row that must hold output row r: the f64 instruction returns rows (lane >> 4) + 4 reg
-            const int row = dbl ? (r % 4) * 4 + r / 4 : r;
-            host[(size_t)(u / 4) * 64 + (size_t)(u % 4) * 16 + row] = (double)L * h->taps_host[k];
+    return tile_plan(h->mm, plan_key(L, M), out, [&](MmTab &t) {
+        const int g = std::gcd(L, M), Lp = L / g, q = M / g;
+        const int P = h->ntaps, T = (P + L - 1) / L;
+        const int DS = 16 / Lp, RS = Lp * DS;
+        int imax = 0;
+        for (int c = 0; c < Lp; ++c) imax = std::max(imax, (int)(((int64_t)c * M) / L));
+        const int U0 = imax + q * (DS - 1);
+        const int K4 = ((T + U0 + 3) / 4 + 3) / 4 * 4;  // padded to the kernel instantiations (multiples of 4 steps)
+        const bool dbl = dtype_double(h->dtype);
+        std::vector<double> host((size_t)K4 * 64, 0.0);
+        for (int r = 0; r < RS; ++r) {
+            const int ds = r / Lp, c = r % Lp;
+            const int64_t cm = (int64_t)c * M;
+            const int phi = (int)(cm % L), ic = (int)(cm / L);
+            for (int u = 0; u < 4 * K4; ++u) {
+                const int t = u - U0 + ic + q * ds;
+                if (t < 0 || t >= T) continue;
+                const int k = phi + L * t;
+                if (k >= P) continue;
+                // MFMA row that must hold output row r: the f64 instruction returns rows (lane >> 4) + 4 reg
+                const int row = dbl ? (r % 4) * 4 + r / 4 : r;
+                host[(size_t)(u / 4) * 64 + (size_t)(u % 4) * 16 + row] = (double)L * h->taps_host[k];
+            }
         }
-    }
-    std::vector<float> hostf;
-    if (!dbl) hostf.assign(host.begin(), host.end());
-    FirHandle::MmTab t;
-    t.L = L; t.M = M; t.Lp = Lp; t.q = q; t.DS = DS; t.RS = RS; t.U0 = U0; t.K4 = K4; t.At = nullptr;
-    const size_t tbytes = host.size() * (dbl ? 8 : 4);
-    SK_HIP(hipMalloc(&t.At, tbytes));
-    SK_HIP(hipMemcpy(t.At, dbl ? (const void *)host.data() : (const void *)hostf.data(), tbytes, hipMemcpyHostToDevice));
-    h->mm.push_back(t);
-    *out = &h->mm.back();
-    return SKDSP_OK;
+        std::vector<float> hostf;
+        if (!dbl) hostf.assign(host.begin(), host.end());
+        t.q = q; t.DS = DS; t.RS = RS; t.U0 = U0; t.K4 = K4;
+        return t.At.upload(dbl ? (const char *)host.data() : (const char *)hostf.data(), host.size() * (dbl ? 8 : 4));
+    });
 }
 
 int fir_mm_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, int L, int M, int64_t n_out, void *y, hipStream_t s)
 {
     note_path("fir_mm");
     if (n_out <= 0) return SKDSP_OK;
-    const FirHandle::MmTab *t = nullptr;
+    MmTab *t = nullptr;
     int rc = get_mm_table(h, L, M, &t);
     if (rc) return rc;
     const size_t esz = dtype_size(h->dtype);
@@ -260,7 +258,7 @@ int fir_mm_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, int L,
     const size_t lds = ((((size_t)a.win + (size_t)a.win / 8 + 2) * esz + 15) & ~(size_t)15) + 64;
     const unsigned grid = (unsigned)((ncols + NS - 1) / NS);
 #define SK_MM(XT, KB)                                                                                              \
-    hipLaunchKernelGGL((fir_mm_kernel<XT, KB>), dim3(grid), dim3(256), lds, s, (const XT *)x, (const typename MmIo<XT>::S *)t->At, a, (XT *)y)
+    hipLaunchKernelGGL((fir_mm_kernel<XT, KB>), dim3(grid), dim3(256), lds, s, (const XT *)x, (const typename MmIo<XT>::S *)t->At.dev, a, (XT *)y)
 #define SK_MMK(XT)                                                       \
     switch (a.K4) {                                                      \
     case 4: SK_MM(XT, 4); break;                                      \

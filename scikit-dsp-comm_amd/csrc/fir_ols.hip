@@ -30,11 +30,11 @@ namespace skdsp {
 using namespace ols;
 typedef float v4f_t __attribute__((ext_vector_type(4)));
 
-struct OlsPlan {
+struct OlsPlan : TilePlan {   // key = (kind, L): build_plan
     int ntaps = 0;
     int ov = 0;  // overlap (discarded head) in samples, multiple of 512
     int V = 0;   // valid outputs per tile
-    float4 *T1 = nullptr, *T2 = nullptr, *Hp = nullptr;
+    DevTable<float4> T1, T2, Hp;
 };
 
 struct OlsArgs {
@@ -1026,18 +1026,19 @@ __global__ __launch_bounds__(256, 2) void ols_rep_kernel(OlsArgs A)
 // Tables of one plan: `up` phase filters (phase p: taps gain * b[p + up t], t < T) as `up` consecutive Hp tables; up = 1 is the filter itself.
 // kind 0: all `up` phases; 1: pairs of phases (real taps: table k holds phase 2k + i phase 2k+1, see load_tile_xr; an odd up leaves its last
 // phase out); 2: the last phase alone (what kind 1 leaves out)
-static int build_plan(const FirHandle *h, int up, OlsPlan **out, int kind = 0)
+static int build_plan(const FirHandle *h, int up, OlsPlan *p, int kind)
 {
-    if (kind == 1) {
-        const int T = (h->ntaps + up - 1) / up;
-        OlsPlan *p = new OlsPlan();
-        p->ntaps = T;
-        p->ov = ((T - 1 + 511) / 512) * 512;
-        if (p->ov == 0) p->ov = 512;
-        p->V = kN - p->ov;
-        std::vector<float4> T1, T2, Hp, Hall;
-        make_T1(T1);
-        make_T2(T2);
+    const int comp = h->taps_complex ? 2 : 1;
+    const int T = kind == 3 ? h->ntaps : (h->ntaps + up - 1) / up;   // (kind 3: the WHOLE filter at the high rate, with the gain L: ols_rep_kernel)
+    const int q_first = kind == 2 ? up - 1 : 0;
+    p->ntaps = T;
+    p->ov = ((T - 1 + 511) / 512) * 512;
+    if (p->ov == 0) p->ov = 512;
+    p->V = kN - p->ov;
+    std::vector<float4> T1, T2, Hp, Hall;
+    make_T1(T1);
+    make_T2(T2);
+    if (kind == 1) {   // (real taps: pair k holds phase 2k + i phase 2k+1)
         std::vector<double> ph((size_t)T * 2);
         for (int k = 0; k < up / 2; ++k) {
             std::fill(ph.begin(), ph.end(), 0.0);
@@ -1049,31 +1050,7 @@ static int build_plan(const FirHandle *h, int up, OlsPlan **out, int kind = 0)
             make_Hp(ph.data(), T, 2, Hp);
             Hall.insert(Hall.end(), Hp.begin(), Hp.end());
         }
-        hipError_t e;
-        if ((e = hipMalloc((void **)&p->T1, T1.size() * sizeof(float4))) != hipSuccess ||
-            (e = hipMalloc((void **)&p->T2, T2.size() * sizeof(float4))) != hipSuccess ||
-            (e = hipMalloc((void **)&p->Hp, Hall.size() * sizeof(float4))) != hipSuccess ||
-            (e = hipMemcpy(p->T1, T1.data(), T1.size() * sizeof(float4), hipMemcpyHostToDevice)) != hipSuccess ||
-            (e = hipMemcpy(p->T2, T2.data(), T2.size() * sizeof(float4), hipMemcpyHostToDevice)) != hipSuccess ||
-            (e = hipMemcpy(p->Hp, Hall.data(), Hall.size() * sizeof(float4), hipMemcpyHostToDevice)) != hipSuccess) {
-            fir_ols_free(p);
-            return hip_fail(e, "ols tables (paired phases)", __FILE__, __LINE__);
-        }
-        *out = p;
-        return SKDSP_OK;
-    }
-    const int comp = h->taps_complex ? 2 : 1;
-    const int T = kind == 3 ? h->ntaps : (h->ntaps + up - 1) / up;   // (kind 3: the WHOLE filter at the high rate, with the gain L: ols_rep_kernel)
-    const int q_first = kind == 2 ? up - 1 : 0;
-    OlsPlan *p = new OlsPlan();
-    p->ntaps = T;
-    p->ov = ((T - 1 + 511) / 512) * 512;
-    if (p->ov == 0) p->ov = 512;
-    p->V = kN - p->ov;
-    std::vector<float4> T1, T2, Hp, Hall;
-    make_T1(T1);
-    make_T2(T2);
-    if (up == 1) {
+    } else if (up == 1) {
         make_Hp(h->taps_host.data(), h->ntaps, comp, Hall);
     } else if (kind == 3) {
         std::vector<double> scaled(h->taps_host);
@@ -1092,43 +1069,23 @@ static int build_plan(const FirHandle *h, int up, OlsPlan **out, int kind = 0)
             Hall.insert(Hall.end(), Hp.begin(), Hp.end());
         }
     }
-    hipError_t e;
-    if ((e = hipMalloc((void **)&p->T1, T1.size() * sizeof(float4))) != hipSuccess ||
-        (e = hipMalloc((void **)&p->T2, T2.size() * sizeof(float4))) != hipSuccess ||
-        (e = hipMalloc((void **)&p->Hp, Hall.size() * sizeof(float4))) != hipSuccess) {
-        fir_ols_free(p);
-        return hip_fail(e, "hipMalloc(ols tables)", __FILE__, __LINE__);
-    }
-    if ((e = hipMemcpy(p->T1, T1.data(), T1.size() * sizeof(float4), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(p->T2, T2.data(), T2.size() * sizeof(float4), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(p->Hp, Hall.data(), Hall.size() * sizeof(float4), hipMemcpyHostToDevice)) != hipSuccess) {
-        fir_ols_free(p);
-        return hip_fail(e, "hipMemcpy(ols tables)", __FILE__, __LINE__);
-    }
-    *out = p;
+    int rc;
+    if ((rc = p->T1.upload(T1)) || (rc = p->T2.upload(T2)) || (rc = p->Hp.upload(Hall))) return rc;
     return SKDSP_OK;
 }
 
-static int ensure_plan(FirHandle *h)
+// the plan of (kind, L), made on first use; (0, 1) is the filter itself
+static int ols_plan(FirHandle *h, int L, int kind, OlsPlan **out)
 {
-    if (h->ols) return SKDSP_OK;
-    return build_plan(h, 1, &h->ols);
-}
-
-void fir_ols_free(OlsPlan *p)
-{
-    if (!p) return;
-    if (p->T1) (void)hipFree(p->T1);
-    if (p->T2) (void)hipFree(p->T2);
-    if (p->Hp) (void)hipFree(p->Hp);
-    delete p;
+    return tile_plan(h->ols, plan_key(kind, L), out, [&](OlsPlan &p) { return build_plan(h, L, &p, kind); });
 }
 
 int fir_ols_tile_outputs(FirHandle *h, int *V)
 {
-    int rc = ensure_plan(h);
+    OlsPlan *p = nullptr;
+    int rc = ols_plan(h, 1, 0, &p);
     if (rc) return rc;
-    *V = h->ols->V;
+    *V = p->V;
     return SKDSP_OK;
 }
 
@@ -1155,15 +1112,15 @@ int fir_ols_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, void 
     SK_CHECK(fir_ols_supported(fir_shape_of(h)), SKDSP_ERR_UNSUPPORTED, "fir_ols: needs complex64 (or float32 with real taps) and 2..4097 taps");
     // (the decimating stores divide tile-local indices below M + 16384 by M through a multiply-high by ceil(2^32 / M): exact while (M + 16384) M < 2^32)
     SK_CHECK(dec <= 32768, SKDSP_ERR_UNSUPPORTED, "fir_ols: decimation by %d (the decimating store takes M <= 32768)", dec);
-    int rc = ensure_plan(h);
+    OlsPlan *p = nullptr;
+    int rc = ols_plan(h, 1, 0, &p);
     if (rc) return rc;
-    OlsPlan *p = h->ols;
     OlsArgs A;
     A.x = (const cf *)x;
     A.y = (cf *)y;
     A.n = n;
     A.n_hist = n_hist;
-    A.T1 = p->T1; A.T2 = p->T2; A.Hp = p->Hp;
+    A.T1 = p->T1.dev; A.T2 = p->T2.dev; A.Hp = p->Hp.dev;
     A.ov = p->ov; A.V = p->V; A.a0 = p->ov / 512; A.keep = ols_keep_blocks(A.a0);
     const bool real = h->dtype == SKDSP_F32;
     // element alignment is all the vector accesses need: tile starts are odd multiples of the
@@ -1219,22 +1176,11 @@ int fir_ols_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, void 
 // phase) pairs is cheaper: every pair costs what one tile of .filter costs, whatever the phase length (which calls, and when the phases
 // of a float32 signal run in pairs: fir_ols_up_supported, fir_ols_up_pairs in fir_route.hpp).
 
-static int up_plan(FirHandle *h, int L, int kind, OlsPlan **out)
-{
-    const int key = kind == 1 ? -L : (kind == 2 ? 1000 + L : (kind == 3 ? 100000 + L : L));
-    for (auto &u : h->ols_up)
-        if (u.L == key) { *out = u.plan; return SKDSP_OK; }
-    int rc = build_plan(h, L, out, kind);
-    if (rc) return rc;
-    h->ols_up.push_back(FirHandle::OlsUp{key, *out});
-    return SKDSP_OK;
-}
-
 // one launch of the walk over `cnt` phases (kind as in build_plan)
 static int up_walk(FirHandle *h, int kind, const void *x, int64_t n, int64_t n_hist, int L, void *y, hipStream_t s, int dec, int64_t rows_pitch)
 {
     OlsPlan *p = nullptr;
-    int rc = up_plan(h, L, kind, &p);
+    int rc = ols_plan(h, L, kind, &p);
     if (rc) return rc;
     const bool xr = kind == 1;                              // real signal into the complex tile
     const bool real = h->dtype == SKDSP_F32 && !xr;         // two real tiles per complex tile
@@ -1244,7 +1190,7 @@ static int up_walk(FirHandle *h, int kind, const void *x, int64_t n, int64_t n_h
     A.y = (cf *)y;
     A.n = n;
     A.n_hist = n_hist;
-    A.T1 = p->T1; A.T2 = p->T2; A.Hp = p->Hp;
+    A.T1 = p->T1.dev; A.T2 = p->T2.dev; A.Hp = p->Hp.dev;
     A.ov = p->ov; A.V = p->V; A.a0 = p->ov / 512; A.keep = ols_keep_blocks(A.a0);
     const int esz = h->dtype == SKDSP_F32 ? 4 : 8;
     A.aligned = xr ? (((uintptr_t)x & 3) == 0 && ((uintptr_t)y & (L % 2 ? 3 : 7)) == 0) : ((((uintptr_t)x) | ((uintptr_t)y)) & (real ? 3 : 7)) == 0;
@@ -1291,7 +1237,7 @@ int fir_ols_rep_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, i
     if (n <= 0) return SKDSP_OK;
     SK_CHECK(fir_ols_rep_supported(fir_shape_of(h), L, opt().fir_up_rep), SKDSP_ERR_UNSUPPORTED, "fir_ols_rep: needs complex64 (or float32 with real taps), an even L and 2..4097 taps");
     OlsPlan *p = nullptr;
-    int rc = up_plan(h, L, 3, &p);
+    int rc = ols_plan(h, L, 3, &p);
     if (rc) return rc;
     const bool real = h->dtype == SKDSP_F32;
     const int lf = L % 16 == 0 ? 16 : (L % 8 == 0 ? 8 : (L % 4 == 0 ? 4 : 2));
@@ -1300,7 +1246,7 @@ int fir_ols_rep_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, i
     A.y = (cf *)y;
     A.n = n * L;                  // (the rate the tiles live at)
     A.n_hist = n_hist * L;
-    A.T1 = p->T1; A.T2 = p->T2; A.Hp = p->Hp;
+    A.T1 = p->T1.dev; A.T2 = p->T2.dev; A.Hp = p->Hp.dev;
     A.ov = p->ov; A.V = p->V; A.a0 = p->ov / 512; A.keep = ols_keep_blocks(A.a0);
     A.aligned = ((((uintptr_t)x) | ((uintptr_t)y)) & (real ? 3 : 7)) == 0;
     int64_t ntiles = (A.n + p->V - 1) / p->V;

@@ -549,88 +549,67 @@ __global__ __launch_bounds__(256, 2) void ols64_tile_kernel(Ols64Args A)
 
 }  // namespace
 
-struct Ols64Plan {
+struct Ols64Plan : TilePlan {   // key = (paired, L); L = 1: the filter itself
     int ov = 0, V = 0;
-    cdd *Hp = nullptr, *W1 = nullptr, *W2 = nullptr;
+    DevTable<double> Hp, W1, W2;   // complex128, interleaved
 };
 
-void fir_ols64_free(Ols64Plan *p)
-{
-    if (!p) return;
-    if (p->Hp) (void)hipFree(p->Hp);
-    if (p->W1) (void)hipFree(p->W1);
-    if (p->W2) (void)hipFree(p->W2);
-    delete p;
-}
-
 // Tables of one plan: `up` phase filters (phase q: taps up * b[q + up t]) as `up` consecutive H tables; up = 1: the filter itself.
-static int build_plan64(const FirHandle *h, int up, Ols64Plan **out, bool paired = false)
+static int plan64(FirHandle *h, int up, Ols64Plan **out, bool paired = false)
 {
-    typedef std::complex<long double> cl;
-    const int T = (h->ntaps + up - 1) / up;
-    const int ntab = paired ? up / 2 : up;   // paired (real taps, even up): table k holds phase 2k + i phase 2k+1
-    Ols64Plan *p = new Ols64Plan();
-    p->ov = ((T - 1 + 255) / 256) * 256;
-    if (p->ov == 0) p->ov = 256;
-    p->V = kN64 - p->ov;
-    // H = DFT_4096(b) / N in long double (plain O(N P) sums: once per handle)
-    const int comp = h->taps_complex ? 2 : 1;
-    const long double two_pi = 6.283185307179586476925286766559L;
-    std::vector<cl> wn(kN64);
-    for (int k = 0; k < kN64; ++k) wn[k] = cl(cosl(two_pi * k / kN64), -sinl(two_pi * k / kN64));
-    std::vector<double> Hp((size_t)2 * kN64 * ntab), W1(2 * 256), W2(2 * 16);
-    // each table: the 4096-point DFT of the phase's taps, radix-2 in long double (the O(N T) sums this replaces took seconds for the L tables
-    // of a long interpolator)
-    std::vector<cl> f(kN64);
-    for (int q = 0; q < ntab; ++q) {
-        std::fill(f.begin(), f.end(), cl(0, 0));
-        for (int t = 0; t < T; ++t) {
-            const int j = (paired ? 2 * q : q) + up * t;
-            if (j >= h->ntaps) break;
-            f[t] = paired ? cl(h->taps_host[j], j + 1 < h->ntaps ? h->taps_host[j + 1] : 0.0)
-                          : (comp == 2 ? cl(h->taps_host[2 * j], h->taps_host[2 * j + 1]) : cl(h->taps_host[j], 0));
+    return tile_plan(h->ols64, plan_key(paired ? 1 : 0, up), out, [&](Ols64Plan &plan) -> int {
+        Ols64Plan *p = &plan;
+        typedef std::complex<long double> cl;
+        const int T = (h->ntaps + up - 1) / up;
+        const int ntab = paired ? up / 2 : up;   // paired (real taps, even up): table k holds phase 2k + i phase 2k+1
+        p->ov = ((T - 1 + 255) / 256) * 256;
+        if (p->ov == 0) p->ov = 256;
+        p->V = kN64 - p->ov;
+        // H = DFT_4096(b) / N in long double (plain O(N P) sums: once per handle)
+        const int comp = h->taps_complex ? 2 : 1;
+        const long double two_pi = 6.283185307179586476925286766559L;
+        std::vector<cl> wn(kN64);
+        for (int k = 0; k < kN64; ++k) wn[k] = cl(cosl(two_pi * k / kN64), -sinl(two_pi * k / kN64));
+        std::vector<double> Hp((size_t)2 * kN64 * ntab), W1(2 * 256), W2(2 * 16);
+        // each table: the 4096-point DFT of the phase's taps, radix-2 in long double (the O(N T) sums this replaces took seconds for the L tables
+        // of a long interpolator)
+        std::vector<cl> f(kN64);
+        for (int q = 0; q < ntab; ++q) {
+            std::fill(f.begin(), f.end(), cl(0, 0));
+            for (int t = 0; t < T; ++t) {
+                const int j = (paired ? 2 * q : q) + up * t;
+                if (j >= h->ntaps) break;
+                f[t] = paired ? cl(h->taps_host[j], j + 1 < h->ntaps ? h->taps_host[j + 1] : 0.0)
+                              : (comp == 2 ? cl(h->taps_host[2 * j], h->taps_host[2 * j + 1]) : cl(h->taps_host[j], 0));
+            }
+            for (int i = 1, j = 0; i < kN64; ++i) {   // bit reversal
+                int bit = kN64 >> 1;
+                for (; j & bit; bit >>= 1) j ^= bit;
+                j ^= bit;
+                if (i < j) std::swap(f[i], f[j]);
+            }
+            for (int len = 2; len <= kN64; len <<= 1)
+                for (int i = 0; i < kN64; i += len)
+                    for (int k = 0; k < len / 2; ++k) {
+                        const cl u = f[i + k], w = f[i + k + len / 2] * wn[(size_t)k * (kN64 / len)];
+                        f[i + k] = u + w;
+                        f[i + k + len / 2] = u - w;
+                    }
+            for (int k = 0; k < kN64; ++k) {
+                cl acc = f[k];
+                acc *= (long double)up / (long double)kN64;   // (up = 1: 1 / N; else the gain L of multirate_FIR.up as well)
+                const int k1 = k & 15, k2 = (k >> 4) & 15, k3 = k >> 8;
+                const size_t idx = (size_t)q * kN64 + (size_t)k3 * 256 + 16 * k1 + k2;
+                Hp[2 * idx] = (double)acc.real();
+                Hp[2 * idx + 1] = (double)acc.imag();
+            }
         }
-        for (int i = 1, j = 0; i < kN64; ++i) {   // bit reversal
-            int bit = kN64 >> 1;
-            for (; j & bit; bit >>= 1) j ^= bit;
-            j ^= bit;
-            if (i < j) std::swap(f[i], f[j]);
-        }
-        for (int len = 2; len <= kN64; len <<= 1)
-            for (int i = 0; i < kN64; i += len)
-                for (int k = 0; k < len / 2; ++k) {
-                    const cl u = f[i + k], w = f[i + k + len / 2] * wn[(size_t)k * (kN64 / len)];
-                    f[i + k] = u + w;
-                    f[i + k + len / 2] = u - w;
-                }
-        for (int k = 0; k < kN64; ++k) {
-            cl acc = f[k];
-            acc *= (long double)up / (long double)kN64;   // (up = 1: 1 / N; else the gain L of multirate_FIR.up as well)
-            const int k1 = k & 15, k2 = (k >> 4) & 15, k3 = k >> 8;
-            const size_t idx = (size_t)q * kN64 + (size_t)k3 * 256 + 16 * k1 + k2;
-            Hp[2 * idx] = (double)acc.real();
-            Hp[2 * idx + 1] = (double)acc.imag();
-        }
-    }
-    for (int t = 0; t < 256; ++t) { W1[2 * t] = (double)wn[t].real(); W1[2 * t + 1] = (double)wn[t].imag(); }
-    for (int c = 0; c < 16; ++c) { W2[2 * c] = (double)wn[16 * c].real(); W2[2 * c + 1] = (double)wn[16 * c].imag(); }
-    hipError_t e;
-    if ((e = hipMalloc((void **)&p->Hp, Hp.size() * 8)) != hipSuccess || (e = hipMalloc((void **)&p->W1, W1.size() * 8)) != hipSuccess ||
-        (e = hipMalloc((void **)&p->W2, W2.size() * 8)) != hipSuccess ||
-        (e = hipMemcpy(p->Hp, Hp.data(), Hp.size() * 8, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(p->W1, W1.data(), W1.size() * 8, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(p->W2, W2.data(), W2.size() * 8, hipMemcpyHostToDevice)) != hipSuccess) {
-        fir_ols64_free(p);
-        return hip_fail(e, "ols64 tables", __FILE__, __LINE__);
-    }
-    *out = p;
-    return SKDSP_OK;
-}
-
-static int ensure_plan64(FirHandle *h)
-{
-    if (h->ols64) return SKDSP_OK;
-    return build_plan64(h, 1, &h->ols64);
+        for (int t = 0; t < 256; ++t) { W1[2 * t] = (double)wn[t].real(); W1[2 * t + 1] = (double)wn[t].imag(); }
+        for (int c = 0; c < 16; ++c) { W2[2 * c] = (double)wn[16 * c].real(); W2[2 * c + 1] = (double)wn[16 * c].imag(); }
+        int rc;
+        if ((rc = p->Hp.upload(Hp)) || (rc = p->W1.upload(W1)) || (rc = p->W2.upload(W2))) return rc;
+        return SKDSP_OK;
+    });
 }
 
 int fir_ols64_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, void *y, hipStream_t s, int dec)
@@ -640,12 +619,12 @@ int fir_ols64_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, voi
     if (dec > 1) n = (n / dec) * dec;
     if (n <= 0) return SKDSP_OK;
     SK_CHECK(fir_ols64_supported(fir_shape_of(h)), SKDSP_ERR_UNSUPPORTED, "fir_ols64: needs complex128 (or float64 with real taps) and 2..2049 taps");
-    int rc = ensure_plan64(h);
+    Ols64Plan *p = nullptr;
+    int rc = plan64(h, 1, &p);
     if (rc) return rc;
-    Ols64Plan *p = h->ols64;
     Ols64Args A;
     A.x = (const double *)x; A.y = (double *)y; A.n = n; A.n_hist = n_hist;
-    A.Hp = p->Hp; A.W1 = p->W1; A.W2 = p->W2;
+    A.Hp = (const cdd *)p->Hp.dev; A.W1 = (const cdd *)p->W1.dev; A.W2 = (const cdd *)p->W2.dev;
     A.ov = p->ov; A.V = p->V; A.a0 = p->ov / 256;
     const bool real = h->dtype == SKDSP_F64;
     int64_t ntiles = (n + p->V - 1) / p->V;
@@ -678,18 +657,11 @@ int fir_ols64_up_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, 
     SK_CHECK(fir_ols64_up_supported(fir_shape_of(h), L), SKDSP_ERR_UNSUPPORTED, "fir_ols64_up: needs complex128 (or float64 with real taps), 2 <= L <= 256, 2..2049 taps per phase");
     const bool paired = paired_in != 0;
     SK_CHECK(!paired || fir_ols64_up_pairs(fir_shape_of(h), L, dec, (unsigned)(uintptr_t)y, opt().fir_up_pair), SKDSP_ERR_BADARG, "fir_ols64_up: phases in pairs need float64, real taps, an even L, no decimation and a 16-byte aligned destination");
-    const int key = paired ? -L : L;
     Ols64Plan *p = nullptr;
-    for (auto &u : h->ols64_up)
-        if (u.L == key) p = u.plan;
-    if (!p) {
-        int rc = build_plan64(h, L, &p, paired);
-        if (rc) return rc;
-        h->ols64_up.push_back(FirHandle::Ols64Up{key, p});
-    }
+    if (int rc = plan64(h, L, &p, paired)) return rc;
     Ols64Args A;
     A.x = (const double *)x; A.y = (double *)y; A.n = n; A.n_hist = n_hist;
-    A.Hp = p->Hp; A.W1 = p->W1; A.W2 = p->W2;
+    A.Hp = (const cdd *)p->Hp.dev; A.W1 = (const cdd *)p->W1.dev; A.W2 = (const cdd *)p->W2.dev;
     A.ov = p->ov; A.V = p->V; A.a0 = p->ov / 256;
     const bool real = h->dtype == SKDSP_F64 && !paired;
     const int phases = paired ? L / 2 : L;

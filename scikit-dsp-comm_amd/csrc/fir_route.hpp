@@ -153,7 +153,7 @@ constexpr bool bx_fits(bool cplx, int kb, int rt)
 // RT / KB: row tiles / 32-lag blocks of the table; RSP / KSP: waves they are dealt to
 struct BxGeometry { int L, M, Lp, q, DS, RS, RT, U0, KB, RSP, KSP; };
 
-// geometry of one (L, M): false if the kernel family does not cover it (G: BxGeometry, or the table that begins with its fields -- FirHandle::BxTab)
+// geometry of one (L, M): false if the kernel family does not cover it (G: BxGeometry, or the table that derives from it -- BxTab of fir_bx.hip)
 template <class G> inline bool bx_geometry(const FirShape &h, int L, int M, G *t)
 {
     const int g = std::gcd(L, M), Lp = L / g, q = M / g;

@@ -13,83 +13,47 @@ static_assert(SKDSP_F32 == kIirF32 && SKDSP_C64 == kIirC64 && SKDSP_F64 == kIirF
 
 IirHandle::~IirHandle()
 {
-    if (plan) iir_free(plan);
-    if (par) iir_par_free(par);
     for (IirHandle *g : groups) delete g;
-    if (group_tmp) (void)hipFree(group_tmp);
     delete twin64;
-    if (seq_coef_dev) (void)hipFree(seq_coef_dev);
-    if (twin_in) (void)hipFree(twin_in);
-    if (twin_out) (void)hipFree(twin_out);
-}
-
-void iir_free(IirPlan *p)
-{
-    if (!p) return;
-    for (void *d : {(void *)p->pw_dev, (void *)p->pwa_dev, (void *)p->lb_dev, (void *)p->lbk_dev, (void *)p->gt_dev, (void *)p->state_dev, (void *)p->v_dev,
-                    (void *)p->agg_dev, (void *)p->lbg_dev, (void *)p->ticket_dev})
-        if (d) (void)hipFree(d);
-    delete p;
 }
 
 // ---- the plan of the cascade scans: the numbers are iir_scan_plan.hpp, here their device copies ---------------------------------
 static int ensure_plan(IirHandle *h)
 {
     if (h->plan) return SKDSP_OK;
-    IirPlan *p = new IirPlan();
+    std::unique_ptr<IirPlan> p(new IirPlan());
     p->nsec = h->nsec; p->order = h->order; p->D = h->nsec * h->order;
-    const int D = p->D;
+    const size_t D = p->D;
     p->A_host = scan_A_host(h->coef.data(), h->nsec, h->order);
-    hipError_t e;
-    if ((e = hipMalloc((void **)&p->pw_dev, (size_t)kPowers * D * D * 8)) != hipSuccess ||
-        (e = hipMalloc((void **)&p->pwa_dev, (size_t)8 * 4 * 64 * 8)) != hipSuccess ||
-        (e = hipMalloc((void **)&p->lb_dev, (size_t)8 * D * D * 8)) != hipSuccess ||
-        (e = hipMalloc((void **)&p->lbk_dev, (size_t)32 * D * D * 8)) != hipSuccess ||
-        (e = hipMalloc((void **)&p->state_dev, (size_t)4 * D * 8)) != hipSuccess ||
-        (e = hipMalloc((void **)&p->agg_dev, (size_t)2 * 2 * kMaxW * D * 8)) != hipSuccess) {
-        iir_free(p);
-        return hip_fail(e, "hipMalloc(iir plan)", __FILE__, __LINE__);
-    }
-    h->plan = p;
-    return SKDSP_OK;
-}
-
-// a buffer that only grows; what ran on the stream may still read the old one
-static int grow(void *&p, size_t &have, size_t need, hipStream_t s)
-{
-    if (need <= have) return SKDSP_OK;
-    if (p) {
-        SK_HIP(hipStreamSynchronize(s));
-        SK_HIP(hipFree(p));
-        p = nullptr; have = 0;
-    }
-    SK_HIP(hipMalloc(&p, need));
-    have = need;
+    int rc;
+    if ((rc = p->pw_dev.alloc(kPowers * D * D)) || (rc = p->pwa_dev.alloc(8 * 4 * 64)) || (rc = p->lb_dev.alloc(8 * D * D)) ||
+        (rc = p->lbk_dev.alloc(32 * D * D)) || (rc = p->state_dev.alloc(4 * D)) || (rc = p->agg_dev.alloc(2 * 2 * kMaxW * D)))
+        return rc;
+    h->plan = std::move(p);
     return SKDSP_OK;
 }
 
 // the tables of chunk length T on the device (cached: one chunk length at a time)
 static int ensure_powers(IirHandle *h, int64_t T, hipStream_t s)
 {
-    IirPlan *p = h->plan;
+    IirPlan *p = iir_plan_of(h);
     if (p->cached_T == T) return SKDSP_OK;
     const ScanTables t = scan_tables(h->coef.data(), h->nsec, h->order, p->A_host, T, dtype_double(h->dtype));
-    SK_HIP(hipMemcpyAsync(p->lbk_dev, t.lbk.data(), t.lbk.size() * 8, hipMemcpyHostToDevice, s));
+    p->cached_T = -1;   // from the first overwrite until all tables are those of T, the plan holds the tables of no chunk length
     p->gt_T = -1;
+    SK_HIP(hipMemcpyAsync(p->lbk_dev.dev, t.lbk.data(), t.lbk.size() * 8, hipMemcpyHostToDevice, s));
     if (t.gt_T == T) {
-        void *gt = p->gt_dev;
-        const int rc = grow(gt, p->gt_cap, t.gt.size() * 8, s);
-        p->gt_dev = (double *)gt;
+        const int rc = p->gt_dev.reserve(t.gt.size() * 8, s);
         if (rc) return rc;
-        SK_HIP(hipMemcpyAsync(p->gt_dev, t.gt.data(), t.gt.size() * 8, hipMemcpyHostToDevice, s));
-        p->gt_T = T;
+        SK_HIP(hipMemcpyAsync(p->gt_dev.dev, t.gt.data(), t.gt.size() * 8, hipMemcpyHostToDevice, s));
     }
     p->n_lv = t.n_lv;
     p->n_lb = t.n_lb;
-    SK_HIP(hipMemcpyAsync(p->lb_dev, t.lb.data(), t.lb.size() * 8, hipMemcpyHostToDevice, s));
-    SK_HIP(hipMemcpyAsync(p->pw_dev, t.pw.data(), t.pw.size() * 8, hipMemcpyHostToDevice, s));
-    SK_HIP(hipMemcpyAsync(p->pwa_dev, t.pwa.data(), t.pwa.size() * 8, hipMemcpyHostToDevice, s));
+    SK_HIP(hipMemcpyAsync(p->lb_dev.dev, t.lb.data(), t.lb.size() * 8, hipMemcpyHostToDevice, s));
+    SK_HIP(hipMemcpyAsync(p->pw_dev.dev, t.pw.data(), t.pw.size() * 8, hipMemcpyHostToDevice, s));
+    SK_HIP(hipMemcpyAsync(p->pwa_dev.dev, t.pwa.data(), t.pwa.size() * 8, hipMemcpyHostToDevice, s));
     SK_HIP(hipStreamSynchronize(s));  // t is a local
+    if (t.gt_T == T) p->gt_T = T;
     p->cached_T = T;
     return SKDSP_OK;
 }
@@ -102,19 +66,19 @@ struct IirQueries {
     {
         const int rc = ensure_plan(h);
         if (rc) return rc;
-        fstate = interleaved ? h->plan->fused_state_c : h->plan->fused_state;   // applicability only (cached); the policy is per call
-        fnlv = interleaved ? h->plan->fused_nlv_c : h->plan->fused_nlv;
+        fstate = interleaved ? iir_plan_of(h)->fused_state_c : iir_plan_of(h)->fused_state;   // applicability only (cached); the policy is per call
+        fnlv = interleaved ? iir_plan_of(h)->fused_nlv_c : iir_plan_of(h)->fused_nlv;
         return SKDSP_OK;
     }
     void fused_remember(IirHandle *h, bool interleaved, int fstate, int fnlv)
     {
-        (interleaved ? h->plan->fused_state_c : h->plan->fused_state) = fstate;
-        (interleaved ? h->plan->fused_nlv_c : h->plan->fused_nlv) = fnlv;
+        (interleaved ? iir_plan_of(h)->fused_state_c : iir_plan_of(h)->fused_state) = fstate;
+        (interleaved ? iir_plan_of(h)->fused_nlv_c : iir_plan_of(h)->fused_nlv) = fnlv;
     }
     int scan_facts(IirHandle *h, int64_t T, ScanFacts &f)
     {
         const int rc = ensure_powers(h, T, s);
-        f = ScanFacts{h->plan->n_lv, h->plan->n_lb, h->plan->gt_T};
+        f = ScanFacts{iir_plan_of(h)->n_lv, iir_plan_of(h)->n_lb, iir_plan_of(h)->gt_T};
         return rc;
     }
 };
@@ -130,19 +94,16 @@ static int scan_step(const Step &st, const void *x, void *y, const double *zi_ho
     const int64_t n = st.n;
     int rc = ensure_plan(h);
     if (rc) return rc;
-    IirPlan *p = h->plan;
+    IirPlan *p = iir_plan_of(h);
     const int D = p->D;
     const int64_t T = fused ? fused_chunk(dbl, st.interleaved) : st.geom.T;
     if ((rc = ensure_powers(h, T, s))) return rc;   // (a no-op where the route asked for these tables last)
-    void *v = p->v_dev;
-    rc = grow(v, p->v_cap, fused ? 0 : (size_t)nbatch * D * st.geom.J * 8, s);
-    p->v_dev = (double *)v;
-    if (rc) return rc;
+    if ((rc = p->v_dev.reserve(fused ? 0 : (size_t)nbatch * D * st.geom.J * 8, s))) return rc;
     SK_CHECK(dec <= 1 || (zf_host == nullptr && (st.interleaved || nbatch == 1)), SKDSP_ERR_UNSUPPORTED,
              "iir: decimating store needs a real or interleaved complex signal and no state output");
     SK_CHECK(nbatch >= 1 && nbatch <= 2, SKDSP_ERR_BADARG, "iir: batch must be 1 or 2");
     const double *zi_dev = nullptr;
-    double *zf_dev = zf_host ? p->state_dev + 2 * D : nullptr;
+    double *zf_dev = zf_host ? p->state_dev.dev + 2 * D : nullptr;
     if (zi_host) {
         std::vector<double> zi_int;  // the caller's DF2T states in the internal factorisation (IirHandle::state_scale)
         if (!h->state_scale.empty()) {
@@ -151,9 +112,9 @@ static int scan_step(const Step &st, const void *x, void *y, const double *zi_ho
                 for (int d = 0; d < D; ++d) zi_int[(size_t)b * D + d] = zi_host[(size_t)b * D + d] * h->state_scale[d];
             zi_host = zi_int.data();
         }
-        SK_HIP(hipMemcpyAsync(p->state_dev, zi_host, (size_t)nbatch * D * 8, hipMemcpyHostToDevice, s));
+        SK_HIP(hipMemcpyAsync(p->state_dev.dev, zi_host, (size_t)nbatch * D * 8, hipMemcpyHostToDevice, s));
         if (!zi_int.empty()) SK_HIP(hipStreamSynchronize(s));  // zi_int is a local
-        zi_dev = p->state_dev;
+        zi_dev = p->state_dev.dev;
     }
     if (fused) {
         rc = iir_fused_launch(h, x, n, nbatch, st.x_stride, y, zi_dev, zf_dev, s, dec, st.interleaved);
@@ -161,10 +122,10 @@ static int scan_step(const Step &st, const void *x, void *y, const double *zi_ho
         IirArgs a;
         a.x = x; a.y = y; a.n = n; a.T = T; a.J = st.geom.J; a.batch_stride = st.x_stride;
         a.il = st.interleaved ? 1 : 0;
-        a.pw = p->pw_dev; a.v = p->v_dev;
-        a.agg = p->agg_dev;
-        a.carry = p->agg_dev + (size_t)2 * kMaxW * D;
-        a.lbmat = p->lb_dev;
+        a.pw = p->pw_dev.dev; a.v = p->v_dev.as<double>();
+        a.agg = p->agg_dev.dev;
+        a.carry = p->agg_dev.dev + (size_t)2 * kMaxW * D;
+        a.lbmat = p->lb_dev.dev;
         a.n_lb = st.fast ? 0 : p->n_lb;   // (aggregate-free mode: K3 reads the carries)
         a.n_lv = p->n_lv < 8 ? p->n_lv : 8;
         a.zi = zi_dev; a.zf = zf_dev;
@@ -172,7 +133,7 @@ static int scan_step(const Step &st, const void *x, void *y, const double *zi_ho
         a.n_keep = (n / a.dec) * a.dec;
         a.dec_dq = scan_dec_dq(st.interleaved, dbl, T, a.dec);
         a.dec_dr = scan_dec_dr(st.interleaved, dbl, T, a.dec);
-        const ScanLaunch L{h->coef.data(), h->nsec, h->order, p->gt_dev, p->lbk_dev, p->n_lv, p->gt_T, nbatch, st.geom.W, ctx().num_cus,
+        const ScanLaunch L{h->coef.data(), h->nsec, h->order, p->gt_dev.as<double>(), p->lbk_dev.dev, p->n_lv, p->gt_T, nbatch, st.geom.W, ctx().num_cus,
                            ScanForm{st.fast, h->unit_tail, scan_k1(st.fast, st.interleaved, D, T)}};
         rc = dbl ? iir_scan_launch_f64(L, a, s) : iir_scan_launch_f32(L, a, s);
         if (!rc) note_path("iir_scan");   // (recorded once the two-pass kernels WERE launched: the other engines note themselves)
@@ -194,9 +155,9 @@ static int run_step(const Step &st, const IirCall &c, size_t esz, const void *x_
     hipStream_t s = ctx().stream;
     IirHandle *h = st.h;
     auto at = [&](const IirBuf<IirHandle> &b, void **out) -> int {
-        auto owned = [&](void *&p, size_t &have) {   // a buffer of the handle b.owner
-            const int rc = grow(p, have, (size_t)b.bytes, s);
-            *out = p;
+        auto owned = [&](DevBuffer &buf) {   // a buffer of the handle b.owner
+            const int rc = buf.reserve((size_t)b.bytes, s);
+            *out = buf.dev;
             return rc;
         };
         switch (b.kind) {
@@ -204,9 +165,9 @@ static int run_step(const Step &st, const IirCall &c, size_t esz, const void *x_
         case kBufY: *out = (char *)y_dev + (size_t)row * c.y_stride * esz; return SKDSP_OK;
         case kBufPlanes: return ws_reserve(3, (size_t)b.bytes, out);
         case kBufFull: return ws_reserve(2, (size_t)b.bytes, out);
-        case kBufGroupTmp: return owned(b.owner->group_tmp, b.owner->group_tmp_bytes);
-        case kBufTwinIn: return owned(b.owner->twin_in, b.owner->twin_in_bytes);
-        default: return owned(b.owner->twin_out, b.owner->twin_out_bytes);
+        case kBufGroupTmp: return owned(b.owner->group_tmp);
+        case kBufTwinIn: return owned(b.owner->twin_in);
+        default: return owned(b.owner->twin_out);
         }
     };
     void *src = nullptr, *dst = nullptr;

@@ -9,34 +9,32 @@
 
 namespace skdsp {
 
-struct IirPlan {
+struct IirPlan : TilePlan {   // (owned by its handle through the base: IirHandle::plan)
     int nsec, order, D;
     // per call geometry is recomputed; matrix powers are cached per chunk length T
     int64_t cached_T = -1;
-    double *pw_dev = nullptr;    // kPowers matrices M^(2^l), each D x D row-major
-    double *pwa_dev = nullptr;   // M^(2^l), l = 0..7, zero-padded to 16 x 16, as MFMA A operands [l][k / 4][64] (D <= 16)
-    double *lb_dev = nullptr;    // look-back matrices (M^256)^k, k = 1..7
-    double *lbk_dev = nullptr;   // chunk look-back powers M^k, k = 0..31, lane-contiguous (aggregate-free mode)
-    double *gt_dev = nullptr;    // G = [A^(T-1-k) b]_k in MFMA A-operand order: [T/4][64], grown on demand
-    size_t gt_cap = 0;
+    DevTable<double> pw_dev;     // kPowers matrices M^(2^l), each D x D row-major
+    DevTable<double> pwa_dev;    // M^(2^l), l = 0..7, zero-padded to 16 x 16, as MFMA A operands [l][k / 4][64] (D <= 16)
+    DevTable<double> lb_dev;     // look-back matrices (M^256)^k, k = 1..7
+    DevTable<double> lbk_dev;    // chunk look-back powers M^k, k = 0..31, lane-contiguous (aggregate-free mode)
+    DevBuffer gt_dev;            // G = [A^(T-1-k) b]_k in MFMA A-operand order: [T/4][64] doubles, grown on demand
     int64_t gt_T = -1;           // chunk length the table was built for (-1: none)
     int n_lb = 0;                // terms of the in-kernel carry look-back (0 = use the K2 scan)
     int n_lv = kPowers;          // first l with max|M^(2^l)| < 1e-30 (chunk-level scan depth that matters)
-    double *state_dev = nullptr; // [2][2][D]: zi and zf for up to two planes
-    double *v_dev = nullptr;     // [D][J] chunk end states (SoA), capacity below
-    double *agg_dev = nullptr;   // [2][kMaxW][D] workgroup aggregates / carries (ping-pong) + carry
-    size_t v_cap = 0;
+    DevTable<double> state_dev;  // [2][2][D]: zi and zf for up to two planes
+    DevBuffer v_dev;             // [D][J] doubles: chunk end states (SoA)
+    DevTable<double> agg_dev;    // [2][kMaxW][D] workgroup aggregates / carries (ping-pong) + carry
     std::vector<double> A_host;
     // single-pass scan (iir_fused_kernel)
     int fused_state = 0;                   // 0 untested, 1 applicable, -1 not (the segment transition does not vanish)
     int fused_state_c = 0;                 // the same for interleaved complex signals (chunks half as long)
     int fused_nlv = 0, fused_nlv_c = 0;    // scan levels (n_lv) at the single-pass chunk length, for the path policy
-    unsigned long long *lbg_dev = nullptr;  // look-back granules [batch][nseg][32]
-    size_t lbg_cap = 0;
-    unsigned long long *ticket_dev = nullptr;  // [2] segment dispensers, monotonic
+    DevBuffer lbg_dev;                     // look-back granules [batch][nseg][32] of 8 bytes
+    DevTable<unsigned long long> ticket_dev;   // [2] segment dispensers, monotonic (allocated and zeroed by the first launch)
     unsigned long long ticket_count[2] = {0, 0};  // their values (a launch adds nseg to each dispenser it uses)
     unsigned epoch = 0;
 };
+inline IirPlan *iir_plan_of(const IirHandle *h) { return static_cast<IirPlan *>(h->plan.get()); }
 
 struct IirArgs {
     const void *x;

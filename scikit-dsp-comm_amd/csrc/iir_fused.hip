@@ -841,31 +841,28 @@ template <typename IO>
 static int launch_fused(IirHandle *h, const void *x, int64_t n, int nbatch, int64_t batch_stride, void *y, const double *zi_dev,
                         double *zf_dev, hipStream_t s, int dec, int interleaved)
 {
-    IirPlan *p = h->plan;
+    IirPlan *p = iir_plan_of(h);
     const int T = (interleaved ? 256 : 512) / (int)sizeof(IO);
     const int64_t S = (int64_t)kIirThreads * T;
     const int64_t nseg = (n + S - 1) / S;
     SK_CHECK(nseg < (1 << 30), SKDSP_ERR_BADARG, "iir: too many segments");
-    if (!p->ticket_dev) {
-        SK_HIP(hipMalloc((void **)&p->ticket_dev, 16));
-        SK_HIP(hipMemsetAsync(p->ticket_dev, 0, 16, s));
+    int rc;
+    if (!p->ticket_dev.dev) {
+        if ((rc = p->ticket_dev.alloc(2))) return rc;
+        if (hipError_t e = hipMemsetAsync(p->ticket_dev.dev, 0, 16, s)) {
+            p->ticket_dev.reset();   // (dispensers that were never zeroed must not be found by the next call)
+            return hip_fail(e, "hipMemsetAsync(tickets)", __FILE__, __LINE__);
+        }
         p->ticket_count[0] = p->ticket_count[1] = 0;
     }
     const size_t need = (size_t)(interleaved ? 2 : nbatch) * nseg * 32 * 8;
-    if (need > p->lbg_cap) {
-        if (p->lbg_dev) {
-            SK_HIP(hipStreamSynchronize(s));
-            SK_HIP(hipFree(p->lbg_dev));
-        }
-        p->lbg_dev = nullptr; p->lbg_cap = 0;
-        SK_HIP(hipMalloc((void **)&p->lbg_dev, need));
-        SK_HIP(hipMemsetAsync(p->lbg_dev, 0, need, s));  // epoch 0 is never used as a tag
-        p->lbg_cap = need;
-    }
+    bool fresh;
+    if ((rc = p->lbg_dev.reserve(need, s, &fresh))) return rc;
+    if (fresh) SK_HIP(hipMemsetAsync(p->lbg_dev.dev, 0, need, s));  // epoch 0 is never used as a tag
     FusedArgs a;
     a.x = x; a.y = y; a.n = n; a.batch_stride = batch_stride;
-    a.pw = p->pw_dev; a.gt = p->gt_dev;
-    a.lb = p->lbg_dev; a.ticket = p->ticket_dev;
+    a.pw = p->pw_dev.dev; a.gt = p->gt_dev.as<double>();
+    a.lb = p->lbg_dev.as<unsigned long long>(); a.ticket = p->ticket_dev.dev;
     a.ticket_base[0] = p->ticket_count[0]; a.ticket_base[1] = p->ticket_count[1];
     a.epoch = ++p->epoch;
     if (a.epoch == 0) a.epoch = ++p->epoch;
@@ -909,8 +906,8 @@ static int launch_fused(IirHandle *h, const void *x, int64_t n, int nbatch, int6
     case N: {                                                                                                        \
         Coef<N, 2> cf;                                                                                               \
         std::memcpy(cf.c, h->coef.data(), sizeof(cf.c));                                                             \
-        if (N >= 2 && h->unit_tail) hipLaunchKernelGGL((iir_fused_kernel<N, IO, (N >= 2)>), grid, dim3(kIirThreads), 0, s, a, cf, a.pw, a.gt, (const double *)p->pwa_dev); \
-        else hipLaunchKernelGGL((iir_fused_kernel<N, IO, false>), grid, dim3(kIirThreads), 0, s, a, cf, a.pw, a.gt, (const double *)p->pwa_dev);  \
+        if (N >= 2 && h->unit_tail) hipLaunchKernelGGL((iir_fused_kernel<N, IO, (N >= 2)>), grid, dim3(kIirThreads), 0, s, a, cf, a.pw, a.gt, p->pwa_dev.dev); \
+        else hipLaunchKernelGGL((iir_fused_kernel<N, IO, false>), grid, dim3(kIirThreads), 0, s, a, cf, a.pw, a.gt, p->pwa_dev.dev);  \
         break;                                                                                                       \
     }
     switch (h->nsec) {
@@ -927,7 +924,7 @@ int iir_fused_launch(IirHandle *h, const void *x, int64_t n, int nbatch, int64_t
                      double *zf_dev, hipStream_t s, int dec, int interleaved)
 {
     // the rule of iir_scan_plan.hpp: biquads, at most 8, and the plan's tables are those of the single-pass chunk length and vanish over a segment
-    const IirPlan *p = h->plan;
+    const IirPlan *p = iir_plan_of(h);
     const int64_t Tf = fused_chunk(dtype_double(h->dtype), interleaved != 0);
     SK_CHECK(h->order == 2 && h->nsec <= 8 && p && p->cached_T == Tf && fused_applies(ScanFacts{p->n_lv, p->n_lb, p->gt_T}, Tf), SKDSP_ERR_UNSUPPORTED,
              "iir_fused: the single-pass scan does not take this call");

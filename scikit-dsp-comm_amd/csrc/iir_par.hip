@@ -1088,41 +1088,25 @@ static_assert(par_stage_image_bytes(4) == (int64_t)64 * Stage<float>::pitch * (i
               par_stage_image_bytes(8) == (int64_t)64 * Stage<double>::pitch * (int64_t)sizeof(double), "par_stage_image_bytes is 64 rows of Stage<IO>");
 
 struct ParTables {
-    int T = 0;                   // 0: not made yet
+    int T = 0;                   // 0: not made yet (published, with n_lv and K, once the three tables below are on the device)
     int n_lv = 0, K = 0;         // K = 0: the filter remembers more than par_max_k segments of this length (not served)
-    double *gt_dev = nullptr;    // ParTableValues::gt, lvl, psi on the device
-    double *lvl_dev = nullptr;
-    double *psi_dev = nullptr;
+    DevTable<double> gt, lvl, psi;   // ParTableValues::gt, lvl, psi on the device
     int v32 = 0;                 // V = G x in float32 for chunks of this length (par_v32_probe): 0 not probed, 1 admitted, -1 refused
     double v32_err = 0.0;        // ... the worst probe error it showed (a refusal: the first one above the limit)
 };
 
-struct ParPlan {
+struct ParPlan : TilePlan {      // (owned by its handle through the base: IirHandle::par)
     int state = 0;               // 0 untested, 1 expansion accepted, -1 not applicable
     ParExpansion e;
     ParTables tab[8];            // by slot (iir_par_plan.hpp: par_slot_T and its neighbours)
-    struct UpJump { int up; double *dev; };
-    std::vector<UpJump> upj;     // per L: par_upj_values on the device (UPJ kernels)
-    unsigned long long *lbg_dev = nullptr;
-    size_t lbg_cap = 0;
-    unsigned long long *ticket_dev = nullptr;
+    struct UpJump : TilePlan { DevTable<double> dev; };
+    TilePlans upj;               // per L (the key): par_upj_values on the device (UPJ kernels)
+    DevBuffer lbg_dev;           // look-back granules
+    DevTable<unsigned long long> ticket_dev;   // kParTickets dispensers (allocated and zeroed by the first launch)
     unsigned long long ticket_count = 0;
     unsigned epoch = 0;
 };
-
-void iir_par_free(ParPlan *p)
-{
-    if (!p) return;
-    for (ParTables &t : p->tab) {
-        if (t.gt_dev) (void)hipFree(t.gt_dev);
-        if (t.lvl_dev) (void)hipFree(t.lvl_dev);
-        if (t.psi_dev) (void)hipFree(t.psi_dev);
-    }
-    for (auto &u : p->upj) if (u.dev) (void)hipFree(u.dev);
-    if (p->lbg_dev) (void)hipFree(p->lbg_dev);
-    if (p->ticket_dev) (void)hipFree(p->ticket_dev);
-    delete p;
-}
+static ParPlan *par_plan_of(const IirHandle *h) { return static_cast<ParPlan *>(h->par.get()); }
 
 // host-only: the expansion of a handle's cascade (tests; no GPU needed).  out = [c0, (a1, a2, r0, r1) x nsec, kappa, ir_err, v32_err at 128, at 96]:
 // 5 + 4 nsec doubles
@@ -1148,10 +1132,12 @@ int iir_par_expand_host(const double *coef, int nsec, double *out, int *accepted
     return SKDSP_OK;
 }
 
-static int par_upload(const std::vector<double> &v, double **dev, hipStream_t s)
+// a table's allocation and the copy of its values, enqueued: the caller syncs once behind its group of tables (v outlives that sync)
+static int par_upload(const std::vector<double> &v, DevTable<double> &t, hipStream_t s)
 {
-    SK_HIP(hipMalloc((void **)dev, v.size() * 8));
-    SK_HIP(hipMemcpyAsync(*dev, v.data(), v.size() * 8, hipMemcpyHostToDevice, s));
+    const int rc = t.alloc(v.size());
+    if (rc) return rc;
+    SK_HIP(hipMemcpyAsync(t.dev, v.data(), v.size() * 8, hipMemcpyHostToDevice, s));
     return SKDSP_OK;
 }
 
@@ -1161,31 +1147,35 @@ static int par_slot_K(ParPlan &P, int slot, hipStream_t s)
     ParTables &tb = P.tab[slot];
     if (tb.T != 0) return tb.K;
     const ParTableValues v = par_table_values(P.e, par_slot_T(slot), par_slot_chunks(slot), par_slot_negl(slot), par_max_k(par_slot_dbl(slot)));
-    tb.T = par_slot_T(slot);
+    if (!v.failed) {   // a failed attempt leaves the slot unmade (the next call tries again; a second alloc frees the first)
+        int rc = par_upload(v.gt, tb.gt, s);
+        if (!rc) rc = par_upload(v.lvl, tb.lvl, s);
+        if (!rc) rc = par_upload(v.psi, tb.psi, s);
+        if (rc) {
+            (void)hipStreamSynchronize(s);   // (copies already enqueued read v, a local)
+            return rc;
+        }
+        SK_HIP(hipStreamSynchronize(s));
+    }
     tb.n_lv = v.n_lv;
     tb.K = v.failed ? 0 : v.K;
-    if (v.failed) return 0;
-    int rc = par_upload(v.gt, &tb.gt_dev, s);
-    if (!rc) rc = par_upload(v.lvl, &tb.lvl_dev, s);
-    if (!rc) rc = par_upload(v.psi, &tb.psi_dev, s);
-    if (rc) return rc;
-    SK_HIP(hipStreamSynchronize(s));
+    tb.T = par_slot_T(slot);
     return tb.K;
 }
 
 // UPJ table of a plan for the factor L, made on first use
 static int par_upj_table(ParPlan &P, int L, hipStream_t s, const double **out)
 {
-    for (auto &u : P.upj)
-        if (u.up == L) { *out = u.dev; return SKDSP_OK; }
-    const std::vector<double> tab = par_upj_values(P.e, L);
-    double *dev = nullptr;
-    const int rc = par_upload(tab, &dev, s);
-    if (rc) return rc;
-    SK_HIP(hipStreamSynchronize(s));
-    P.upj.push_back(ParPlan::UpJump{L, dev});
-    *out = dev;
-    return SKDSP_OK;
+    ParPlan::UpJump *u = nullptr;
+    const int rc = tile_plan(P.upj, plan_key(L), &u, [&](ParPlan::UpJump &t) -> int {
+        const std::vector<double> tab = par_upj_values(P.e, L);
+        const int rc2 = par_upload(tab, t.dev, s);
+        if (rc2) return rc2;
+        SK_HIP(hipStreamSynchronize(s));
+        return SKDSP_OK;
+    });
+    if (!rc) *out = u->dev.dev;
+    return rc;
 }
 
 // Which <N, IO, DECM, CPLX, TT, UPJ, UPS, V32> exist: the families <IO, TT, UPJ, UPS> par_choose names, and inside them the variants the kernel was
@@ -1233,7 +1223,7 @@ template <int N, typename IO, int DECM, bool CPLX, int TT, bool UPJ, int UPS, bo
         cf.gamma = L.e->gamma;
         if constexpr (V32) note_path("iir_par_v32");   // (tests assert which arithmetic ran by this record)
         hipLaunchKernelGGL((iir_par_kernel<N, IO, DECM, CPLX, TT, UPJ, UPS, V32>), dim3(L.grid), dim3(kIirThreads), 0, L.s, L.a, cf,
-                           (const double *)L.tb->gt_dev, (const double *)L.tb->lvl_dev, (const double *)L.tb->psi_dev, 0ull, L.upj);
+                           L.tb->gt.dev, L.tb->lvl.dev, L.tb->psi.dev, 0ull, L.upj);
         return SKDSP_OK;
     } else
         return par_no_kernel(N, (int)sizeof(IO), DECM, CPLX, TT, UPJ, UPS, V32);
@@ -1301,27 +1291,24 @@ static int launch_par(IirHandle *h, ParPlan *p, const ParChoice &c, bool dbl, bo
     const int64_t nseg = (n + S - 1) / S;
     SK_CHECK(nseg * nrow < (1 << 30), SKDSP_ERR_BADARG, "iir: too many segments");
     const int total = (int)(nseg * nrow);
-    if (!p->ticket_dev) {
-        SK_HIP(hipMalloc((void **)&p->ticket_dev, 8 * kParTickets));
-        SK_HIP(hipMemsetAsync(p->ticket_dev, 0, 8 * kParTickets, s));
+    int rc;
+    if (!p->ticket_dev.dev) {
+        if ((rc = p->ticket_dev.alloc(kParTickets))) return rc;
+        if (hipError_t e = hipMemsetAsync(p->ticket_dev.dev, 0, 8 * kParTickets, s)) {
+            p->ticket_dev.reset();   // (dispensers that were never zeroed must not be found by the next call)
+            return hip_fail(e, "hipMemsetAsync(tickets)", __FILE__, __LINE__);
+        }
         p->ticket_count = 0;
     }
     const size_t need = (size_t)total * (interleaved ? 64 : 32) * 8;
-    if (need > p->lbg_cap) {
-        if (p->lbg_dev) {
-            SK_HIP(hipStreamSynchronize(s));
-            SK_HIP(hipFree(p->lbg_dev));
-        }
-        p->lbg_dev = nullptr; p->lbg_cap = 0;
-        SK_HIP(hipMalloc((void **)&p->lbg_dev, need));
-        SK_HIP(hipMemsetAsync(p->lbg_dev, 0, need, s));  // epoch 0 is never used as a tag
-        p->lbg_cap = need;
-    }
+    bool fresh;
+    if ((rc = p->lbg_dev.reserve(need, s, &fresh))) return rc;
+    if (fresh) SK_HIP(hipMemsetAsync(p->lbg_dev.dev, 0, need, s));  // epoch 0 is never used as a tag
     ParLaunch L;
     ParArgs &a = L.a;
     a.x = x; a.y = y; a.n = n; a.x_stride = x_stride; a.y_stride = y_stride;
     a.nseg = (int)nseg; a.total = total;
-    a.lb = p->lbg_dev; a.ticket = p->ticket_dev; a.ticket_base = p->ticket_count;
+    a.lb = p->lbg_dev.as<unsigned long long>(); a.ticket = p->ticket_dev.dev; a.ticket_base = p->ticket_count;
     a.epoch = ++p->epoch;
     if (a.epoch == 0) a.epoch = ++p->epoch;
     a.n_lv = tb.n_lv; a.K = tb.K;
@@ -1338,8 +1325,7 @@ static int launch_par(IirHandle *h, ParPlan *p, const ParChoice &c, bool dbl, bo
     a.n_keep = (n / a.dec) * a.dec;
     L.upj = nullptr;
     if (c.UPJ) {
-        const int rc = par_upj_table(*p, a.up, s, &L.upj);
-        if (rc) return rc;
+        if ((rc = par_upj_table(*p, a.up, s, &L.upj))) return rc;
     }
     {
         const int64_t step = (int64_t)(64 / (dbl ? Stage<double>::segs : Stage<float>::segs)) * T;   // samples between a lane's staged segments
@@ -1350,7 +1336,6 @@ static int launch_par(IirHandle *h, ParPlan *p, const ParChoice &c, bool dbl, bo
     // draw segments beyond the last and leave)
     L.grid = (unsigned)(((total + 3) / 4 + kParTickets - 1) / kParTickets * kParTickets);
     L.e = &p->e; L.tb = &tb; L.s = s;
-    int rc;
     if (c.UPJ) rc = par_launch_dtype<96, true, 0>(dbl, interleaved, h->nsec, c.DECM, v32, L);
     else if (c.TT == 96) rc = c.UPS == 3 ? par_launch_dtype<96, false, 3>(dbl, interleaved, h->nsec, c.DECM, v32, L)
                                          : par_launch_dtype<96, false, 0>(dbl, interleaved, h->nsec, c.DECM, v32, L);
@@ -1373,10 +1358,11 @@ ParChoice iir_par_takes(IirHandle *h, int64_t n, int nrow, int dec, int interlea
     if (dbl || interleaved) return no;
 #endif
     if (!h->par) {
-        h->par = new ParPlan();
-        h->par->state = par_expand(h->coef.data(), h->nsec, h->par->e) ? 1 : -1;
+        std::unique_ptr<ParPlan> made(new ParPlan());
+        made->state = par_expand(h->coef.data(), h->nsec, made->e) ? 1 : -1;
+        h->par = std::move(made);
     }
-    ParPlan *p = h->par;
+    ParPlan *p = par_plan_of(h);
     if (p->state != 1) return no;   // (poles shared between sections, slow decay, ...)
     const ParOptions o{opt().iir_dn_t96, opt().iir_up_jump, opt().iir_up_lean, opt().iir_dn_compact, opt().iir_par_v32};
     return par_choose(h->nsec, dbl, interleaved != 0, nrow, dec, up, n, o, [&](int slot) { return par_slot_K(*p, slot, s); });
@@ -1386,11 +1372,12 @@ ParChoice iir_par_takes(IirHandle *h, int64_t n, int nrow, int dec, int interlea
 int iir_par_launch(IirHandle *h, const ParChoice &c, const void *x, int64_t n, int nrow, int64_t x_stride, int64_t y_stride, void *y, hipStream_t s, int dec,
                    int interleaved, int up)
 {
-    SK_CHECK(c.status == 0 && h->par && h->par->state == 1 && h->par->tab[c.slot].T != 0, SKDSP_ERR_UNSUPPORTED,
+    ParPlan *p = par_plan_of(h);
+    SK_CHECK(c.status == 0 && p && p->state == 1 && p->tab[c.slot].T != 0, SKDSP_ERR_UNSUPPORTED,
              "iir_par: the parallel form does not take this call");
     const bool dbl = dtype_double(h->dtype);
-    if (interleaved) return launch_par(h, h->par, c, dbl, true, x, n, 1, 0, 0, y, s, dec, up);
-    return launch_par(h, h->par, c, dbl, false, x, n, nrow, x_stride, y_stride, y, s, dec, up);
+    if (interleaved) return launch_par(h, p, c, dbl, true, x, n, 1, 0, 0, y, s, dec, up);
+    return launch_par(h, p, c, dbl, false, x, n, nrow, x_stride, y_stride, y, s, dec, up);
 }
 
 }  // namespace skdsp

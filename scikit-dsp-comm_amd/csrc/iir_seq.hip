@@ -158,10 +158,8 @@ int iir_seq_launch(IirHandle *h, const void *x, int64_t n, int nrow, int64_t x_s
     SK_CHECK(dec <= 1 || nrow == 1, SKDSP_ERR_UNSUPPORTED, "iir_seq: the decimating store takes one row");
     note_path("iir_seq");
     const int nsec = h->nsec;
-    if (!h->seq_coef_dev) {
-        SK_HIP(hipMalloc(&h->seq_coef_dev, h->seq_coef.size() * 8));
-        SK_HIP(hipMemcpy(h->seq_coef_dev, h->seq_coef.data(), h->seq_coef.size() * 8, hipMemcpyHostToDevice));
-    }
+    int rc;
+    if (!h->seq_coef_dev.dev && (rc = h->seq_coef_dev.upload(h->seq_coef))) return rc;
     const bool dbl = dtype_double(h->dtype);
     const bool with_state = zi_host || zf_host;
     const int npass = (nsec + 63) / 64;
@@ -170,19 +168,11 @@ int iir_seq_launch(IirHandle *h, const void *x, int64_t n, int nrow, int64_t x_s
     double *mid = nullptr;
     if (npass > 1) {
         const size_t need = (size_t)nrow * (size_t)n * 8 + 256;
-        if (need > h->group_tmp_bytes) {
-            if (h->group_tmp) {
-                SK_HIP(hipStreamSynchronize(s));
-                SK_HIP(hipFree(h->group_tmp));
-                h->group_tmp = nullptr; h->group_tmp_bytes = 0;
-            }
-            SK_HIP(hipMalloc(&h->group_tmp, need));
-            h->group_tmp_bytes = need;
-        }
-        mid = static_cast<double *>(h->group_tmp);
+        if ((rc = h->group_tmp.reserve(need, s))) return rc;
+        mid = h->group_tmp.as<double>();
     }
     std::vector<double> st;   // per pass [rows][2 ns], packed pass after pass
-    double *st_dev = nullptr;
+    DevTable<double> st_dev;  // this call's: freed on every path out
     if (with_state) {
         st.assign((size_t)nrow * 2 * nsec, 0.0);
         size_t at = 0;
@@ -192,8 +182,8 @@ int iir_seq_launch(IirHandle *h, const void *x, int64_t n, int nrow, int64_t x_s
                 for (int d = 0; d < 2 * ns; ++d) st[at + (size_t)r * 2 * ns + d] = zi_host ? zi_host[(size_t)r * 2 * nsec + 2 * s0 + d] : 0.0;
             at += (size_t)nrow * 2 * ns;
         }
-        SK_HIP(hipMalloc((void **)&st_dev, st.size() * 8));
-        SK_HIP(hipMemcpyAsync(st_dev, st.data(), st.size() * 8, hipMemcpyHostToDevice, s));
+        if ((rc = st_dev.alloc(st.size()))) return rc;
+        SK_HIP(hipMemcpyAsync(st_dev.dev, st.data(), st.size() * 8, hipMemcpyHostToDevice, s));
     }
     size_t at = 0;
     for (int p = 0; p < npass; ++p) {
@@ -205,9 +195,9 @@ int iir_seq_launch(IirHandle *h, const void *x, int64_t n, int nrow, int64_t x_s
         a.n = n;
         a.x_stride = first ? x_stride : n;
         a.y_stride = lastp ? y_stride : n;
-        a.coef = (const double *)h->seq_coef_dev + 5 * s0;
+        a.coef = h->seq_coef_dev.dev + 5 * s0;
         a.ns = ns;
-        a.state = with_state ? st_dev + at : nullptr;
+        a.state = with_state ? st_dev.dev + at : nullptr;
         a.dec = lastp && dec > 1 ? dec : 1;
         const bool in_d = dbl || !first, out_d = dbl || !lastp;   // (the buffer between passes is float64 whatever the handle)
         if (in_d && out_d) seq_launch_one<double, double>(nrow, s, a);
@@ -218,9 +208,8 @@ int iir_seq_launch(IirHandle *h, const void *x, int64_t n, int nrow, int64_t x_s
     }
     SK_HIP(hipGetLastError());
     if (with_state) {
-        SK_HIP(hipMemcpyAsync(st.data(), st_dev, st.size() * 8, hipMemcpyDeviceToHost, s));
+        SK_HIP(hipMemcpyAsync(st.data(), st_dev.dev, st.size() * 8, hipMemcpyDeviceToHost, s));
         SK_HIP(hipStreamSynchronize(s));
-        (void)hipFree(st_dev);
         if (zf_host) {
             size_t a2 = 0;
             for (int p = 0; p < npass; ++p) {

@@ -162,10 +162,12 @@ __global__ __launch_bounds__(256) void psd_reduce_kernel(const double *__restric
 struct PsdTab {
     int device, log2n;
     std::vector<double> win;
-    void *win_dev = nullptr, *tw_dev = nullptr;
+    DevTable<double> win_dev, tw_dev;   // tw: complex128, interleaved
 };
 std::mutex g_tab_mu;
-std::vector<PsdTab> g_tabs;   // most recently used first
+// Most recently used first.  Never destroyed: the tables own device memory, and a free during static destruction -- after the runtime
+// has torn down -- hangs or aborts the exit of the process; nothing device-side runs then.
+std::vector<PsdTab> &g_tabs = *new std::vector<PsdTab>();
 constexpr size_t kMaxTabs = 16;
 constexpr int kMaxDevices = 64;
 
@@ -186,21 +188,17 @@ static int lds_limit(int dev, int *out)
     return SKDSP_OK;
 }
 
-static int upload_tables(PsdTab &tb, hipStream_t s)
+static int upload_tables(PsdTab &tb)
 {
-    const int N = 1 << tb.log2n, ns = (int)tb.win.size();
+    const int N = 1 << tb.log2n;
     std::vector<cx<double>> tw(N);
     const double kTwoPi = 6.283185307179586476925286766559;
     for (int i = 0; i < N; ++i) tw[i] = cx<double>{cos(kTwoPi * i / N), -sin(kTwoPi * i / N)};
-    SK_HIP(hipMalloc(&tb.win_dev, sizeof(double) * ns));
-    SK_HIP(hipMalloc(&tb.tw_dev, sizeof(cx<double>) * N));
-    SK_HIP(hipMemcpyAsync(tb.win_dev, tb.win.data(), sizeof(double) * ns, hipMemcpyHostToDevice, s));
-    SK_HIP(hipMemcpyAsync(tb.tw_dev, tw.data(), sizeof(cx<double>) * N, hipMemcpyHostToDevice, s));
-    SK_HIP(hipStreamSynchronize(s));   // (tw dies with this frame)
-    return SKDSP_OK;
+    const int rc = tb.win_dev.upload(tb.win);
+    return rc ? rc : tb.tw_dev.upload(&tw[0].x, (size_t)2 * N);
 }
 
-static int tables_for(int log2n, const double *window, int ns, hipStream_t s, void **win_dev, void **tw_dev)
+static int tables_for(int log2n, const double *window, int ns, void **win_dev, void **tw_dev)
 {
     std::lock_guard<std::mutex> lk(g_tab_mu);
     const int dev = ctx().device;
@@ -209,29 +207,21 @@ static int tables_for(int log2n, const double *window, int ns, hipStream_t s, vo
     for (size_t i = 0; i < g_tabs.size(); ++i) {
         PsdTab &tb = g_tabs[i];
         if (tb.device == dev && tb.log2n == log2n && (int)tb.win.size() == ns && memcmp(tb.win.data(), window, sizeof(double) * ns) == 0) {
-            *win_dev = tb.win_dev;
-            *tw_dev = tb.tw_dev;
+            *win_dev = tb.win_dev.dev;
+            *tw_dev = tb.tw_dev.dev;
             if (i) std::rotate(g_tabs.begin(), g_tabs.begin() + i, g_tabs.begin() + i + 1);
             return SKDSP_OK;
         }
     }
-    if (g_tabs.size() >= kMaxTabs) {   // least recently used out (hipFree waits for the device)
-        (void)hipFree(g_tabs.back().win_dev);
-        (void)hipFree(g_tabs.back().tw_dev);
-        g_tabs.pop_back();
-    }
+    if (g_tabs.size() >= kMaxTabs) g_tabs.pop_back();   // least recently used out (the free waits for the device)
     PsdTab tb;
     tb.device = dev;
     tb.log2n = log2n;
     tb.win.assign(window, window + ns);
-    int rc = upload_tables(tb, s);
-    if (rc) {
-        (void)hipFree(tb.win_dev);
-        (void)hipFree(tb.tw_dev);
-        return rc;
-    }
-    *win_dev = tb.win_dev;
-    *tw_dev = tb.tw_dev;
+    int rc = upload_tables(tb);
+    if (rc) return rc;
+    *win_dev = tb.win_dev.dev;
+    *tw_dev = tb.tw_dev.dev;
     g_tabs.insert(g_tabs.begin(), std::move(tb));
     return SKDSP_OK;
 }
@@ -324,7 +314,7 @@ int psd_launch(const void *x, int64_t n, int dtype, const double *window, int ns
     const int rows = (int)((nseg + spw - 1) / spw);
 
     void *win_dev = nullptr, *tw_dev = nullptr, *partial = nullptr;
-    if ((rc = tables_for(log2n, window, ns, s, &win_dev, &tw_dev))) return rc;
+    if ((rc = tables_for(log2n, window, ns, &win_dev, &tw_dev))) return rc;
     if ((rc = ws_reserve(3, (size_t)rows * n_fft * sizeof(double) + 256, &partial))) return rc;
 
     PsdArgs a{n, nseg, step, ns, (int)spw, (int)cs, cap};

@@ -28,6 +28,24 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line)
     return SKDSP_ERR_HIP;
 }
 
+// the device behind dev_mem.hpp
+int dev_alloc(void **out, size_t bytes)
+{
+    SK_HIP(hipMalloc(out, bytes));
+    return SKDSP_OK;
+}
+void dev_free(void *p) { (void)hipFree(p); }
+int dev_copy_in(void *dst, const void *src, size_t bytes)
+{
+    SK_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+    return SKDSP_OK;
+}
+int dev_sync(void *stream)
+{
+    SK_HIP(hipStreamSynchronize((hipStream_t)stream));
+    return SKDSP_OK;
+}
+
 static Context g_slots[kMaxSlots];
 static int g_nslots = 0;            // bound slots; slot 0 is bound by the first call that needs a device
 static std::mutex g_slots_mu;

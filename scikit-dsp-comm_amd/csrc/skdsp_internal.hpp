@@ -9,6 +9,7 @@
 #include <mutex>
 #include "../../include/skdsp.h"
 #include "careful.hpp"
+#include "dev_mem.hpp"
 
 namespace skdsp {
 
@@ -155,45 +156,12 @@ struct HandleBase {
     }
 };
 
-// ---- device tables and per-key plans of the tile engines (fir_up4k.hip, fir_up2k.hip, fir_dn4k.hip, fir_bank.hip) -------
-// One device allocation, freed with its owner.
-template <class T> struct DevTable {
-    T *dev = nullptr;
-    DevTable() = default;
-    DevTable(const DevTable &) = delete;
-    DevTable &operator=(const DevTable &) = delete;
-    ~DevTable()
-    {
-        if (dev) (void)hipFree(dev);
-    }
-    int upload(const T *src, size_t count)
-    {
-        SK_HIP(hipMalloc((void **)&dev, count * sizeof(T)));
-        SK_HIP(hipMemcpy(dev, src, count * sizeof(T), hipMemcpyHostToDevice));
-        return SKDSP_OK;
-    }
-    int upload(const std::vector<T> &v) { return upload(v.data(), v.size()); }
-};
-// What a FIR handle keeps per rate-change factor (key = L or M): the engine's file derives its plan from this.
-struct TilePlan {
-    int key = 0;
-    virtual ~TilePlan() {}
-};
-typedef std::vector<std::unique_ptr<TilePlan>> TilePlans;
-// The plan of `key`, built by fill(P &) on first use (under the handle's lock, like every other table); a plan whose fill fails is
-// released with everything it had uploaded.
-template <class P, class Fill> int tile_plan(TilePlans &plans, int key, P **out, Fill fill)
-{
-    for (auto &q : plans)
-        if (q->key == key) { *out = static_cast<P *>(q.get()); return SKDSP_OK; }
-    std::unique_ptr<P> p(new P());
-    p->key = key;
-    const int rc = fill(*p);
-    if (rc) return rc;
-    *out = p.get();
-    plans.push_back(std::move(p));
-    return SKDSP_OK;
-}
+// The one rule of the handles below: DEVICE MEMORY A HANDLE OWNS IS A DevTable OR A DevBuffer (dev_mem.hpp), alone or inside a plan of a TilePlans
+// cache.  No handle declares a raw device pointer, no destructor enumerates allocations, a table is non-empty only once its upload succeeded,
+// and a lookup hands out the plan's address, which holds for the life of the handle.  (Context-owned memory -- workspaces, the host pipeline,
+// the sharding state -- has an explicit shutdown order instead: runtime.hip.)
+
+// ---- the launch arithmetic of the tile engines (fir_up4k.hip, fir_up2k.hip, fir_dn4k.hip, fir_bank.hip) -------
 // The launch arithmetic of a persistent walk over tiles (their overlap: tile_overlap in ols_tables.hpp).
 // 2 workgroups per CU, less the slots option ols_reserve leaves free (where the grid is at least 4 x that), at most one per tile
 inline int64_t persistent_grid(int64_t ntiles)
@@ -206,35 +174,22 @@ inline int64_t persistent_grid(int64_t ntiles)
 inline bool elem_aligned(const void *x, const void *y, int esz) { return ((((uintptr_t)x) | ((uintptr_t)y)) & (uintptr_t)(esz - 1)) == 0; }
 
 // ---- FIR -----------------------------------------------------------------
-struct OlsPlan;    // fir_ols.hip
-struct Ols64Plan;  // fir_ols64.hip
 struct FirHandle : HandleBase {
     int ntaps = 0;
     bool taps_complex = false;
     int algo = SKDSP_FIR_AUTO;
     std::vector<double> taps_host;  // ntaps (real) or 2*ntaps (complex, interleaved)
-    void *taps64_dev = nullptr;     // the same on the device, natural order (careful.hpp: the rare exact path of a poisoned tile); lazy
-    // polyphase tap banks, keyed by L (lazy): bank[phase][t] = b[phase + L*t], T = ceil(P/L)
-    struct Poly { int L; int T; void *dev; };
-    std::vector<Poly> poly;
-    // sliding-window tap tables, keyed by (L, M, R)
-    struct SwTab { int L, M, R; void *taps; void *rho; };
-    std::vector<SwTab> sw;
-    // Toeplitz-product (matrix pipe) A-operand tables, keyed by (L, M)  -- fir_mm.hip
-    struct MmTab { int L, M, Lp, q, DS, RS, U0, K4; void *At; };
-    std::vector<MmTab> mm;
-    // bf16x3 Toeplitz-product A-operand tables, keyed by (L, M)  -- fir_bx.hip
-    struct BxTab { int L, M, Lp, q, DS, RS, RT, U0, KB, RSP, KSP; float tap_inv = 0.0f; void *At = nullptr; };   // the fields of BxGeometry (fir_route.hpp: bx_geometry fills them), the taps' scale and the table
-    std::vector<BxTab> bx;
-    OlsPlan *ols = nullptr;
-    struct OlsUp { int L; OlsPlan *plan; };   // overlap-save plans of multirate_FIR.up, keyed by L (fir_ols_up_launch)
-    std::vector<OlsUp> ols_up;
-    TilePlans up4k;   // plans of the frequency-domain interpolator, keyed by L (fir_up4k.hip)
-    TilePlans up2k;   // ... of its many-phase form (fir_up2k.hip)
-    TilePlans dn4k;   // plans of the frequency-domain decimator, keyed by M (fir_dn4k.hip)
-    Ols64Plan *ols64 = nullptr;
-    struct Ols64Up { int L; Ols64Plan *plan; };
-    std::vector<Ols64Up> ols64_up;
+    DevTable<double> taps64;        // the same on the device, natural order (careful.hpp: the rare exact path of a poisoned tile); lazy
+    // Per-shape tables and plans, made on first use; each engine's file derives its plan type and packs the key (plan_key):
+    TilePlans poly;      // polyphase tap banks, keyed by L: bank[phase][t] = b[phase + L*t], T = ceil(P/L) (fir_direct.hip)
+    TilePlans sw;        // sliding-window tap tables, keyed by (L, M, R) (fir_direct.hip)
+    TilePlans mm;        // Toeplitz-product (matrix pipe) A-operand tables, keyed by (L, M) (fir_mm.hip)
+    TilePlans bx;        // bf16x3 Toeplitz-product A-operand tables, keyed by (L, M) (fir_bx.hip)
+    TilePlans ols;       // overlap-save plans, keyed by (kind, L): the plain filter and the walks of multirate_FIR.up (fir_ols.hip)
+    TilePlans up4k;      // plans of the frequency-domain interpolator, keyed by L (fir_up4k.hip)
+    TilePlans up2k;      // ... of its many-phase form (fir_up2k.hip)
+    TilePlans dn4k;      // plans of the frequency-domain decimator, keyed by M (fir_dn4k.hip)
+    TilePlans ols64;     // float64 overlap-save plans, keyed by (paired, L) (fir_ols64.hip)
     // Filters longer than one kernel launch takes (fir_part_len in fir_route.hpp) run as partial FIRs over consecutive tap segments,
     // each applied to the correspondingly delayed input and summed (fir_api.hip): parts[s] holds taps [s seg, (s+1) seg).
     std::vector<FirHandle *> parts;
@@ -270,7 +225,6 @@ int fir_ols_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, v
                    const unsigned *halo_flag = nullptr, unsigned halo_seq = 0, unsigned *halo_err = nullptr,
                    int halo_spins = 0);   // polls of ~1 us before that wait gives up (0: the steady-state bound, seconds)
 int fir_ols_publish_halo(unsigned *flag, unsigned seq, hipStream_t s);  // one-thread kernel: *flag = seq (agent-scope release)
-void fir_ols_free(OlsPlan *p);
 // multirate_FIR.up as an overlap-save walk over (tile, phase) pairs: complex64, float32 with real taps; 2..4097 taps per phase
 int fir_ols_up_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, int L, void *y_dev, hipStream_t s, int dec = 1,
                       int64_t rows_pitch = 0, int paired = 0);  // dec = M: L / M, floor(n L / M) outputs; rows_pitch > 0: y[phase * rows_pitch + i] instead of
@@ -286,7 +240,6 @@ int fir_up2k_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, 
 int fir_dn4k_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, int M, void *y_dev, hipStream_t s);
 // FFT overlap-save in float64 (fir_ols64.hip): complex128, and float64 with real taps; 2..2049 taps
 int fir_ols64_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, void *y_dev, hipStream_t s, int dec = 1);
-void fir_ols64_free(Ols64Plan *p);
 int fir_ols64_up_launch(FirHandle *h, const void *x_dev, int64_t n, int64_t n_hist, int L, void *y_dev, hipStream_t s, int dec = 1, int64_t rows_pitch = 0, int paired = 0);
 
 // ---- FIR bank (fir_bank.hip): B frequency-shifted copies of one FIR over ONE input, sigsys.fft_caf (sigsys.py:2696-2781) --------------
@@ -308,8 +261,9 @@ struct IirHandle : HandleBase {
     // one (z_int = scale * z); empty = identity.
     bool unit_tail = false;
     std::vector<double> state_scale;
-    IirPlan *plan = nullptr;
-    struct ParPlan *par = nullptr;   // partial-fraction form of the same transfer function (iir_par.hip), made on first use
+    // made on first use, owned through the base like the plans of a cache (the types are their units'): iir_plan_of() / par_plan_of() read them
+    std::unique_ptr<TilePlan> plan;   // IirPlan (iir_common.hpp): the tables and buffers of the cascade scans
+    std::unique_ptr<TilePlan> par;    // ParPlan (iir_par.hip): the partial-fraction form of the same transfer function
     // Cascades of more than 8 biquads run as consecutive groups of at most 8 (the kernels' register budgets; 8 is what the parallel form
     // takes): group g filters the output of group g - 1 in place, each with its own plans; the caller's per-section states are sliced.
     // scipy.signal.sosfilt takes any number of sections, and so does this.
@@ -318,24 +272,21 @@ struct IirHandle : HandleBase {
     // of the cascade, would break the float32 contract: iir_api.hip) and are too many for one launch sequence: the same cascade as a float64
     // handle; the signal is widened, filtered and narrowed on the device
     IirHandle *twin64 = nullptr;
-    void *twin_in = nullptr, *twin_out = nullptr;
-    size_t twin_in_bytes = 0, twin_out_bytes = 0;
+    DevBuffer twin_in, twin_out;
     // Cascades whose float64 result is itself uncertain beyond what the scans may add to it (iir_api.hip: the probe at creation) run the reference's
     // own recursion (iir_seq.hip): the caller's sections [nsec][5], the relative float64 spread the probe measured
     bool seq = false;
     double seq_spread = 0.0;
     std::vector<double> seq_coef;
-    void *seq_coef_dev = nullptr;
+    DevTable<double> seq_coef_dev;
     int group_first = 0;             // (a group: its first section in the parent's numbering)
-    void *group_tmp = nullptr;       // full-rate intermediate of a decimating call
-    size_t group_tmp_bytes = 0;
+    DevBuffer group_tmp;             // full-rate intermediate of a decimating call
     ~IirHandle();
 };
 // Which engines a call runs is ONE decision (iir_route.hpp, standard headers only), made before the call's first kernel and executed by
 // iir_api.hip (iir_run), which also owns the plans, the workspaces and the state transfer.  The units below only launch: an engine that is
 // asked for a call it does not take returns SKDSP_ERR_UNSUPPORTED.  x / y: real rows or planes in the handle's precision (complex through
 // two planes: nrow = 2), or interleaved complex where an engine says so.  In-place (y == x) is allowed.
-void iir_free(IirPlan *p);
 // the reference's recursion, one wave per row (iir_seq.hip): handles with h->seq set
 int iir_seq_launch(IirHandle *h, const void *x_dev, int64_t n, int nrow, int64_t x_stride, int64_t y_stride, void *y_dev, hipStream_t s,
                    const double *zi_host = nullptr, double *zf_host = nullptr, int dec = 1);
@@ -348,7 +299,6 @@ int iir_par_launch(IirHandle *h, const ParChoice &c, const void *x_dev, int64_t 
                    int dec = 1, int interleaved = 0,    // interleaved = 1: x / y interleaved complex, n complex samples, one row
                    int up = 1);                         // up > 1: x holds n / up samples, the launch filters up * upsample(x, up) (n outputs)
 int iir_par_expand_host(const double *coef, int nsec, double *out, int *accepted);   // host-only (tests): [c0, (a1,a2,r0,r1) x nsec, kappa, ir_err, v32_err at 128, at 96]: 5 + 4 nsec doubles
-void iir_par_free(ParPlan *p);
 
 // ---- resamplers (resample.hip) ---------------------------------------------
 int upsample_launch(const void *x_dev, int64_t n, int L, int dtype, double scale, void *y_dev, hipStream_t s);

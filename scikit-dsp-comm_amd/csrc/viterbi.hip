@@ -212,12 +212,8 @@ __global__ __launch_bounds__(vit::kWave) void viterbi_kernel(VitArgs a)
 
 struct VitHandle : HandleBase {
     vit::Plan plan;
-    void *state = nullptr;   // vit::state_bytes(plan), zero = at rest
+    DevTable<char> state;    // vit::state_bytes(plan), zero = at rest
     int family = 0;          // whose metrics the state holds: 0 at rest, 1 hard / soft (int32), 2 unquant (float64)
-    ~VitHandle()
-    {
-        if (state) (void)hipFree(state);
-    }
 };
 
 template <int METRIC, int K> static void launch_w(int words, unsigned grid, hipStream_t s, const VitArgs &a)
@@ -256,8 +252,8 @@ int viterbi_create(const char *const *polys, int npoly, int depth, HandleBase **
     h->kind = H_VITERBI;
     h->dtype = 0;
     h->plan = plan;
-    SK_HIP(hipMalloc(&h->state, vit::state_bytes(plan)));
-    SK_HIP(hipMemsetAsync(h->state, 0, vit::state_bytes(plan), ctx().stream));
+    if (int rc = h->state.alloc(vit::state_bytes(plan))) return rc;
+    SK_HIP(hipMemsetAsync(h->state.dev, 0, vit::state_bytes(plan), ctx().stream));
     SK_HIP(hipStreamSynchronize(ctx().stream));
     *out = h.release();
     return SKDSP_OK;
@@ -274,7 +270,7 @@ int viterbi_out_len(HandleBase *hb, int64_t nval, int64_t *n_out)
 int viterbi_reset(HandleBase *hb, hipStream_t s)
 {
     VitHandle *h = static_cast<VitHandle *>(hb);
-    SK_HIP(hipMemsetAsync(h->state, 0, vit::state_bytes(h->plan), s));
+    SK_HIP(hipMemsetAsync(h->state.dev, 0, vit::state_bytes(h->plan), s));
     h->family = 0;
     return SKDSP_OK;
 }
@@ -309,7 +305,7 @@ int viterbi_launch(HandleBase *hb, const void *x_dev, int64_t n, int64_t nrow, i
     VitArgs a;
     a.x = x_dev;
     a.y = y_dev;
-    a.state = stateful ? h->state : nullptr;
+    a.state = stateful ? h->state.dev : nullptr;
     a.nval = n;
     a.nsym = vit::symbols_of(p, n);
     a.nout = vit::out_len(p, n);

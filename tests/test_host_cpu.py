@@ -144,6 +144,18 @@ def test_ols_tile_index_algebra_host_emulation(tmp_path):
     assert out.strip().endswith("OK"), out
 
 
+def test_device_ownership_types_host_emulation(tmp_path):
+    """Compiles csrc/dev_mem.hpp for the HOST against a fake device (tests/host/dev_mem_emul.cpp defines the four dev_* functions: it counts
+    live blocks, records the call order and fails the k-th call), under the address and undefined-behaviour sanitizers: DevTable, DevBuffer
+    and tile_plan leave no block behind on any failure path, a failed upload leaves an empty table, and plan addresses and keys hold."""
+    exe = str(tmp_path / "dev_mem_emul")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I", os.path.join(ROOT, "scikit-dsp-comm_amd", "csrc"), os.path.join(ROOT, "tests", "host", "dev_mem_emul.cpp"), "-o", exe])
+    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    out = run.stdout.decode()
+    assert run.returncode == 0 and out.strip().endswith("OK"), out[-4000:]
+
+
 @pytest.mark.parametrize("name", ["ols4k_emul", "ols2k_emul"])
 def test_interpolator_decimator_tiles_host_emulation(tmp_path, name):
     """Compiles csrc/ols4k_core.hpp (4096 points, 16 per thread) / csrc/ols2k_core.hpp (2048 points, 8 per thread) for the HOST and
