@@ -17,7 +17,7 @@
 // 68 KiB (row pitch 17: every 16-lane access pattern used here lands on 16 distinct 16-byte bank groups) -> two
 // persistent workgroups per CU.  V = 4096 - OV valid outputs per tile, OV = Ntaps-1 rounded up to 256 (<= 2048: longer
 // filters are partitioned by fir_api.hip).  Algorithmic bytes: 32 B per complex128 sample, 16 B per float64 sample.
-// Precision: float64 butterflies, twiddle powers by repeated multiplication (<= 15 products): 1e-14 of the peak.
+// Precision: float64 butterflies, twiddle powers w^(4a + b) = w^b (w^4)^a from two table entries (twiddle_powers: at most five products).
 #include "skdsp_internal.hpp"
 #include "fir_route.hpp"
 #include <complex>
@@ -38,6 +38,24 @@ __device__ __forceinline__ cdd cadd(cdd a, cdd b) { return make_double2(a.x + b.
 __device__ __forceinline__ cdd csub(cdd a, cdd b) { return make_double2(a.x - b.x, a.y - b.y); }
 __device__ __forceinline__ cdd cmul(cdd a, cdd w) { return make_double2(fma(a.x, w.x, -a.y * w.y), fma(a.x, w.y, a.y * w.x)); }
 __device__ __forceinline__ cdd cmulc(cdd a, cdd w) { return make_double2(fma(a.x, w.x, a.y * w.y), fma(a.y, w.x, -a.x * w.y)); }
+// f(k, w^k) for k = 1 .. 15, from w and q = w^4 (two table entries): w^(4a + b) = w^b q^a, at most five products deep.  A running power
+// w^k = w^(k-1) w carries k times the rounding of w besides that of its products: over the 256 entries of W_4096^t 3.0 units of 2^-53
+// rms and 10 at worst, where a rounded entry has 0.3 -- which made the error of this tile 2 - 3 x that of a host FFT, larger on the outputs of
+// some t than of others (tests/test_gpu_errspec.py).  This form: 1.06 rms, 3.8 at worst, in one product less.
+template <class F> __device__ __forceinline__ void twiddle_powers(cdd w, cdd q, F f)
+{
+    cdd wb = w;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        if (b >= 2) wb = cmul(wb, w);
+        cdd tw = wb;   // w^b (b = 0: unused, a = 1 starts from q)
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            if (a > 0) tw = (b == 0 && a == 1) ? q : cmul(tw, q);
+            if (a + b > 0) f(4 * a + b, tw);
+        }
+    }
+}
 // a * (-i) (forward) / a * (+i) (inverse)
 template <bool INV> __device__ __forceinline__ cdd mul_mi(cdd a) { return INV ? make_double2(-a.y, a.x) : make_double2(a.y, -a.x); }
 
@@ -133,8 +151,8 @@ struct Ols64Args {
     double *y;
     int64_t n, n_hist;
     const cdd *Hp;    // [16][256]: Hp[k3 * 256 + 16 k1 + k2] = H[k1 + 16 k2 + 256 k3] / N
-    const cdd *W1;    // [256]: W_4096^t
-    const cdd *W2;    // [16]:  W_256^c
+    const cdd *W1;    // [512]: W_4096^t, then W_4096^(4 t)
+    const cdd *W2;    // [32]:  W_256^c, then W_256^(4 c)
     int ov, V, a0;    // a0 = ov / 256: first stored 256-block
     int64_t ntiles;
     int dec;
@@ -160,8 +178,8 @@ __global__ __launch_bounds__(256, 2) void ols64_tile_kernel(Ols64Args A)
     const int t = threadIdx.x;
     if (t == 0) ols_noted = 0;
     const int hi4 = t >> 4, lo4 = t & 15;
-    const cdd w1 = A.W1[t];        // W_4096^t            (pass 1: t = 16 b + c)
-    const cdd w2 = A.W2[lo4];      // W_256^c             (pass 2: thread (k1, c))
+    const cdd w1 = A.W1[t], w1q = A.W1[256 + t];       // W_4096^t and its fourth power   (pass 1: t = 16 b + c)
+    const cdd w2 = A.W2[lo4], w2q = A.W2[16 + lo4];    // W_256^c and its fourth power    (pass 2: thread (k1, c))
     // This thread's 16 bins of H: in registers for the whole launch in the complex kernel (0.691 vs 0.738 ms at 2^26), streamed
     // from L2 per tile in the two-real-tiles kernel (registers there: 0.487 vs 0.401 ms -- its loads and stores need more of them)
     constexpr bool HREG = !UP && !REAL;
@@ -252,17 +270,13 @@ __global__ __launch_bounds__(256, 2) void ols64_tile_kernel(Ols64Args A)
         int tl = t, th = t, ts = t;
         asm volatile("" : "+v"(tl));
         if (!PREF || !have) load_tile(tin, tl, v);
-        // ---- pass 1: DFT16 over a, twiddle W_4096^(t k1) (running power), write [k1][b][c] ----
+        // ---- pass 1: DFT16 over a, twiddle W_4096^(t k1) (twiddle_powers), write [k1][b][c] ----
         dft16_f(v);   // X[k1] at v[P16(k1)]
         {
-            cdd w = w1;
-            asm volatile("" : "+v"(w.x), "+v"(w.y));   // (the running powers are recomputed per tile: hoisted out of the tile loop they are 60 spilled registers)
+            cdd w = w1, q = w1q;
+            asm volatile("" : "+v"(w.x), "+v"(w.y), "+v"(q.x), "+v"(q.y));   // (the powers are recomputed per tile: hoisted out of the tile loop they are 60 spilled registers)
             img[0 * kPitch64 + hi4 * 17 + lo4] = v[0];
-#pragma unroll
-            for (int k1 = 1; k1 < 16; ++k1) {
-                img[k1 * kPitch64 + hi4 * 17 + lo4] = cmul(v[P16(k1)], w);
-                w = cmul(w, w1);
-            }
+            twiddle_powers(w, q, [&](int k1, cdd tw) __attribute__((always_inline)) { img[k1 * kPitch64 + hi4 * 17 + lo4] = cmul(v[P16(k1)], tw); });
         }
         __syncthreads();
         // ---- pass 2: thread (k1 = hi4, c = lo4): DFT16 over b, twiddle W_256^(c k2), write [k1][k2][c] (same 16-lane group) ----
@@ -270,14 +284,10 @@ __global__ __launch_bounds__(256, 2) void ols64_tile_kernel(Ols64Args A)
         for (int b = 0; b < 16; ++b) v[b] = img[hi4 * kPitch64 + b * 17 + lo4];
         dft16_f(v);
         {
-            cdd w = w2;
-            asm volatile("" : "+v"(w.x), "+v"(w.y));
+            cdd w = w2, q = w2q;
+            asm volatile("" : "+v"(w.x), "+v"(w.y), "+v"(q.x), "+v"(q.y));
             img[hi4 * kPitch64 + 0 * 17 + lo4] = v[0];
-#pragma unroll
-            for (int k2 = 1; k2 < 16; ++k2) {
-                img[hi4 * kPitch64 + k2 * 17 + lo4] = cmul(v[P16(k2)], w);
-                w = cmul(w, w2);
-            }
+            twiddle_powers(w, q, [&](int k2, cdd tw) __attribute__((always_inline)) { img[hi4 * kPitch64 + k2 * 17 + lo4] = cmul(v[P16(k2)], tw); });
         }
         // ---- pass 3: thread (k1 = hi4, k2 = lo4): DFT16 over c; multiply by H ----
         // (H streamed from L2 -- the two-real-tiles kernel -- is requested HERE, a whole DFT16 ahead of its use: requested at
@@ -319,14 +329,10 @@ __global__ __launch_bounds__(256, 2) void ols64_tile_kernel(Ols64Args A)
         for (int c = 0; c < 16; ++c) img[hi4 * kPitch64 + lo4 * 17 + c] = v[c];
         // thread (k1, c = lo4) reads over k2, applies conj W_256^(c k2), inverse DFT16 over k2 -> b
         {
-            cdd w = w2;
-            asm volatile("" : "+v"(w.x), "+v"(w.y));
+            cdd w = w2, q = w2q;
+            asm volatile("" : "+v"(w.x), "+v"(w.y), "+v"(q.x), "+v"(q.y));
             v[0] = img[hi4 * kPitch64 + 0 * 17 + lo4];
-#pragma unroll
-            for (int k2 = 1; k2 < 16; ++k2) {
-                v[P16(k2)] = cmulc(img[hi4 * kPitch64 + k2 * 17 + lo4], w);
-                w = cmul(w, w2);
-            }
+            twiddle_powers(w, q, [&](int k2, cdd tw) __attribute__((always_inline)) { v[P16(k2)] = cmulc(img[hi4 * kPitch64 + k2 * 17 + lo4], tw); });
         }
         dft16_g(v);   // v[b] for thread (k1, c)   (rows 4 wave .. 4 wave + 3 belong to this wave alone until here)
 #pragma unroll
@@ -334,14 +340,10 @@ __global__ __launch_bounds__(256, 2) void ols64_tile_kernel(Ols64Args A)
         __syncthreads();
         // thread t = (b = hi4, c = lo4) reads over k1, conj W_4096^(t k1), inverse DFT16 over k1 -> a
         {
-            cdd w = w1;
-            asm volatile("" : "+v"(w.x), "+v"(w.y));   // (the running powers are recomputed per tile: hoisted out of the tile loop they are 60 spilled registers)
+            cdd w = w1, q = w1q;
+            asm volatile("" : "+v"(w.x), "+v"(w.y), "+v"(q.x), "+v"(q.y));   // (the powers are recomputed per tile: hoisted out of the tile loop they are 60 spilled registers)
             v[0] = img[0 * kPitch64 + hi4 * 17 + lo4];
-#pragma unroll
-            for (int k1 = 1; k1 < 16; ++k1) {
-                v[P16(k1)] = cmulc(img[k1 * kPitch64 + hi4 * 17 + lo4], w);
-                w = cmul(w, w1);
-            }
+            twiddle_powers(w, q, [&](int k1, cdd tw) __attribute__((always_inline)) { v[P16(k1)] = cmulc(img[k1 * kPitch64 + hi4 * 17 + lo4], tw); });
         }
         dft16_g(v);   // v[a] = y[256 a + t]
         // "these are the results, in these registers, now" (LABNOTES R4.3): without it hipcc carries the finished transform in a form of its own
@@ -570,7 +572,7 @@ static int plan64(FirHandle *h, int up, Ols64Plan **out, bool paired = false)
         const long double two_pi = 6.283185307179586476925286766559L;
         std::vector<cl> wn(kN64);
         for (int k = 0; k < kN64; ++k) wn[k] = cl(cosl(two_pi * k / kN64), -sinl(two_pi * k / kN64));
-        std::vector<double> Hp((size_t)2 * kN64 * ntab), W1(2 * 256), W2(2 * 16);
+        std::vector<double> Hp((size_t)2 * kN64 * ntab), W1(2 * 512), W2(2 * 32);
         // each table: the 4096-point DFT of the phase's taps, radix-2 in long double (the O(N T) sums this replaces took seconds for the L tables
         // of a long interpolator)
         std::vector<cl> f(kN64);
@@ -604,8 +606,9 @@ static int plan64(FirHandle *h, int up, Ols64Plan **out, bool paired = false)
                 Hp[2 * idx + 1] = (double)acc.imag();
             }
         }
-        for (int t = 0; t < 256; ++t) { W1[2 * t] = (double)wn[t].real(); W1[2 * t + 1] = (double)wn[t].imag(); }
-        for (int c = 0; c < 16; ++c) { W2[2 * c] = (double)wn[16 * c].real(); W2[2 * c + 1] = (double)wn[16 * c].imag(); }
+        // W_4096^t and W_256^c, each followed by its fourth powers (twiddle_powers), every entry rounded once from long double
+        for (int t = 0; t < 512; ++t) { const cl w = wn[t < 256 ? t : 4 * (t - 256)]; W1[2 * t] = (double)w.real(); W1[2 * t + 1] = (double)w.imag(); }
+        for (int c = 0; c < 32; ++c) { const cl w = wn[c < 16 ? 16 * c : 64 * (c - 16)]; W2[2 * c] = (double)w.real(); W2[2 * c + 1] = (double)w.imag(); }
         int rc;
         if ((rc = p->Hp.upload(Hp)) || (rc = p->W1.upload(W1)) || (rc = p->W2.upload(W2))) return rc;
         return SKDSP_OK;

@@ -2,7 +2,8 @@
 (tests/fir_routes/mi355x.txt, written by tools/record_fir_routes.py; its header names that commit): every call of the table is made
 again -- same taps, same input, same options -- and must return the same code, run the same engines (skdsp_debug_path) and write
 the same bytes (zlib.crc32; the FIR engines have no data-dependent summation order).  tests/host/fir_route_emul.cpp checks the
-same table against csrc/fir_route.hpp on the host.
+same table against csrc/fir_route.hpp on the host.  The CRCs of the rows that run fir_ols64 / fir_ols64_up were recorded again, by the same
+run_row, when those kernels' twiddle powers changed (csrc/fir_ols64.hip: twiddle_powers); their return codes and engines are the first record's.
 
 Every row up to 2^17 + 3 samples is replayed; of the rows with 2^25 outputs (the cost model's rounds term needs them), the two
 smallest per signal class and engine list, so that a class takes seconds."""
