@@ -292,6 +292,31 @@ int skdsp_bit_count_rows(const uint8_t *tx, int64_t tx_stride, const uint8_t *rx
 int skdsp_bit_count_rows_dev(const uint8_t *tx_dev, int64_t tx_stride, const uint8_t *rx_dev, int64_t rx_stride, int64_t n, int64_t nrow, int invert,
                              int64_t *counts_dev);
 
+/* Gray symbol mapping (csrc/symmap.hip, csrc/symmap_core.hpp): the symbol sequences of digitalcom.qam_gray_encode_bb / mpsk_gray_encode_bb
+ * (digitalcom.py:1584-1681, 1742-1826) and digitalcom.qam_gray_decode / mpsk_gray_decode (digitalcom.py:1684-1739, 1829-1883) over the rows of a
+ * frame set.  kind: 0 QAM (mod 2, 4, 16, 64, 256), 1 MPSK (mod 2, 4, 8, 16, 32); dtype: SKDSP_C64 or SKDSP_C128, pointers aligned to the element.
+ * Bits are bytes 0 / 1 (bit 0 significant), MSB first within a symbol, at any byte alignment.  Symbol k of an input row is element
+ * start + k step of that row (rows x_stride elements apart): nothing else of x is read.  bits_stride: bytes from row to row.
+ *   gray_map_rows:   n symbols per row from bps n bytes.  tab_re / tab_im: HOST pointers, the constellation as the caller computed it, already
+ *                    rounded to float32 for complex64 output -- QAM of 4 points and more: the ntab = sqrt(mod) levels (tab_im unused), otherwise
+ *                    the ntab = mod points.  The kernel only looks up.
+ *   qam_scale_rows:  r[row] = 1 / (std(row) c), float64, std = sqrt(sum |x - mean|^2 / n): a deterministic merge of partial moments.
+ *   qam_demap_rows:  int16(clip(rint((x r[row] + x_m (1 + 1j)) / 2), 0, x_m)) per component, Gray decoded; r: what qam_scale_rows wrote (or any
+ *                    scale of the caller's) -- a DEVICE pointer in the _dev form, not checked.
+ *   mpsk_demap_rows: mod(rint(angle(x rot) mod / 2 / pi), mod), Gray decoded; (rot_re, rot_im): the caller's exp(-1j pi / 4), read for mod 4 only. */
+int skdsp_gray_map_rows(const uint8_t *bits, int64_t n, int64_t nrow, int kind, int mod, const double *tab_re, const double *tab_im, int ntab, int dtype, void *y);
+int skdsp_gray_map_rows_dev(const uint8_t *bits_dev, int64_t bits_stride, int64_t n, int64_t nrow, int kind, int mod, const double *tab_re, const double *tab_im, int ntab,
+                            int dtype, void *y_dev, int64_t y_stride);
+int skdsp_qam_scale_rows(const void *x, int64_t x_stride, int64_t start, int64_t step, int64_t n, int64_t nrow, int dtype, int mod, double c, double *r);
+int skdsp_qam_scale_rows_dev(const void *x_dev, int64_t x_stride, int64_t start, int64_t step, int64_t n, int64_t nrow, int dtype, int mod, double c, double *r_dev);
+int skdsp_qam_demap_rows(const void *x, int64_t x_stride, int64_t start, int64_t step, int64_t n, int64_t nrow, int dtype, int mod, const double *r, uint8_t *bits);
+int skdsp_qam_demap_rows_dev(const void *x_dev, int64_t x_stride, int64_t start, int64_t step, int64_t n, int64_t nrow, int dtype, int mod, const double *r_dev,
+                             uint8_t *bits_dev, int64_t bits_stride);
+int skdsp_mpsk_demap_rows(const void *x, int64_t x_stride, int64_t start, int64_t step, int64_t n, int64_t nrow, int dtype, int mod, double rot_re, double rot_im,
+                          uint8_t *bits);
+int skdsp_mpsk_demap_rows_dev(const void *x_dev, int64_t x_stride, int64_t start, int64_t step, int64_t n, int64_t nrow, int dtype, int mod, double rot_re, double rot_im,
+                              uint8_t *bits_dev, int64_t bits_stride);
+
 /* Host-pointer entry points of a float32/complex64 handle deliver y as float64/complex128 (the
  * reference's result dtype, multirate_helper.py:108 etc.): widened on the device before the copy
  * back, so y must hold twice the bytes.  Device-pointer (_dev) entry points are not affected. */

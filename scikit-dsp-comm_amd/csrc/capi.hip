@@ -1,5 +1,5 @@
 // capi.hip -- the one-call wrappers of the extern "C" boundary of libskdsp_hip.so (see include/skdsp.h): FIR bank,
-// resamplers, Farrow resampler, Welch primitive, Viterbi decoder, block codes, the FEC chain around the decoder.  The runtime is runtime.hip, the host-pointer chunk pipeline
+// resamplers, Farrow resampler, Welch primitive, Viterbi decoder, block codes, the FEC chain around the decoder, Gray symbol mapping.  The runtime is runtime.hip, the host-pointer chunk pipeline
 // host_pipe.hip, FIR / IIR dispatch fir_api.hip / iir_api.hip.
 #include "api_internal.hpp"
 
@@ -398,6 +398,117 @@ int skdsp_bit_count_rows(const uint8_t *tx, int64_t tx_stride, const uint8_t *rx
     int64_t *counts_dev = reinterpret_cast<int64_t *>((char *)rx_dev + cnt_off);
     if ((rc = bitcount_launch((const uint8_t *)tx_dev, tx_stride, (const uint8_t *)rx_dev, rx_stride, n, nrow, invert, counts_dev, ctx().stream))) return rc;
     return stage_out(counts, counts_dev, (size_t)nrow * sizeof(int64_t));
+}
+
+// ---------------------------------------------------------------- Gray symbol mapping (symmap.hip): qam_gray_encode_bb / mpsk_gray_encode_bb's symbols, qam_gray_decode / mpsk_gray_decode
+int skdsp_gray_map_rows_dev(const uint8_t *bits_dev, int64_t bits_stride, int64_t n, int64_t nrow, int kind, int mod, const double *tab_re, const double *tab_im, int ntab,
+                            int dtype, void *y_dev, int64_t y_stride)
+{
+    int rc = symmap_check(kind, mod, n, nrow, dtype, bits_stride, y_stride);   // (argument errors need no device)
+    if (rc) return rc;
+    SK_CHECK(tab_re, SKDSP_ERR_BADARG, "gray_map: null table");
+    if (nrow == 0 || n == 0) return SKDSP_OK;
+    SK_CHECK(bits_dev && y_dev, SKDSP_ERR_BADARG, "gray_map: null pointer");
+    API_BEGIN;
+    return symmap_launch(bits_dev, bits_stride, n, nrow, kind, mod, tab_re, tab_im, ntab, dtype, y_dev, y_stride, ctx().stream);
+}
+
+// host form: contiguous rows -- nrow x (bps n) bytes in, nrow x n points out
+int skdsp_gray_map_rows(const uint8_t *bits, int64_t n, int64_t nrow, int kind, int mod, const double *tab_re, const double *tab_im, int ntab, int dtype, void *y)
+{
+    const int bps = sym_bits_per_symbol(kind, mod);
+    int rc = symmap_check(kind, mod, n, nrow, dtype, bps * n, n);
+    if (rc) return rc;
+    SK_CHECK(tab_re, SKDSP_ERR_BADARG, "gray_map: null table");
+    if (nrow == 0 || n == 0) return SKDSP_OK;
+    SK_CHECK(bits && y, SKDSP_ERR_BADARG, "gray_map: null pointer");
+    API_BEGIN;
+    const size_t bytes_in = (size_t)bps * (size_t)n * (size_t)nrow, bytes_out = (size_t)n * (size_t)nrow * dtype_size(dtype);
+    void *bits_dev = nullptr, *y_dev = nullptr;
+    if ((rc = stage_in(bits, bytes_in, &bits_dev))) return rc;
+    if ((rc = ws_reserve(1, bytes_out + 256, &y_dev))) return rc;
+    if ((rc = symmap_launch((const uint8_t *)bits_dev, bps * n, n, nrow, kind, mod, tab_re, tab_im, ntab, dtype, y_dev, n, ctx().stream))) return rc;
+    return stage_out(y, y_dev, bytes_out);
+}
+
+// the partial moments of a launch live in workspace 3 of the calling slot
+int skdsp_qam_scale_rows_dev(const void *x_dev, int64_t x_stride, int64_t start, int64_t step, int64_t n, int64_t nrow, int dtype, int mod, double c, double *r_dev)
+{
+    int rc = symscale_check(mod, n, nrow, dtype, x_stride, start, step);   // (argument errors need no device)
+    if (rc || nrow == 0) return rc;
+    SK_CHECK(n >= 1, SKDSP_ERR_BADARG, "qam_scale: a row has no symbols");
+    SK_CHECK(x_dev && r_dev, SKDSP_ERR_BADARG, "qam_scale: null pointer");
+    API_BEGIN;
+    void *scratch = nullptr;
+    if ((rc = ws_reserve(3, symscale_scratch_bytes(n, nrow) + 256, &scratch))) return rc;
+    return symscale_launch(x_dev, x_stride, start, step, n, nrow, dtype, mod, c, scratch, r_dev, ctx().stream);
+}
+
+// host forms of the strided calls: the rows are copied whole -- (nrow - 1) x_stride + start + (n - 1) step + 1 elements
+static size_t sym_span(int64_t x_stride, int64_t start, int64_t step, int64_t n, int64_t nrow) { return (size_t)((nrow - 1) * x_stride + start + (n - 1) * step + 1); }
+
+int skdsp_qam_scale_rows(const void *x, int64_t x_stride, int64_t start, int64_t step, int64_t n, int64_t nrow, int dtype, int mod, double c, double *r)
+{
+    int rc = symscale_check(mod, n, nrow, dtype, x_stride, start, step);
+    if (rc || nrow == 0) return rc;
+    SK_CHECK(n >= 1, SKDSP_ERR_BADARG, "qam_scale: a row has no symbols");
+    SK_CHECK(x && r, SKDSP_ERR_BADARG, "qam_scale: null pointer");
+    API_BEGIN;
+    void *x_dev = nullptr, *r_dev = nullptr, *scratch = nullptr;
+    if ((rc = stage_in(x, sym_span(x_stride, start, step, n, nrow) * dtype_size(dtype), &x_dev))) return rc;
+    if ((rc = ws_reserve(1, (size_t)nrow * sizeof(double) + 256, &r_dev))) return rc;
+    if ((rc = ws_reserve(3, symscale_scratch_bytes(n, nrow) + 256, &scratch))) return rc;
+    if ((rc = symscale_launch(x_dev, x_stride, start, step, n, nrow, dtype, mod, c, scratch, (double *)r_dev, ctx().stream))) return rc;
+    return stage_out(r, r_dev, (size_t)nrow * sizeof(double));
+}
+
+int skdsp_qam_demap_rows_dev(const void *x_dev, int64_t x_stride, int64_t start, int64_t step, int64_t n, int64_t nrow, int dtype, int mod, const double *r_dev,
+                             uint8_t *bits_dev, int64_t bits_stride)
+{
+    int rc = symdemap_check(0, mod, n, nrow, dtype, x_stride, start, step, bits_stride);   // (argument errors need no device)
+    if (rc || nrow == 0 || n == 0) return rc;
+    SK_CHECK(x_dev && r_dev && bits_dev, SKDSP_ERR_BADARG, "qam_demap: null pointer");
+    API_BEGIN;
+    return symdemap_launch(x_dev, x_stride, start, step, n, nrow, dtype, 0, mod, r_dev, 1.0, 0.0, bits_dev, bits_stride, ctx().stream);
+}
+
+int skdsp_mpsk_demap_rows_dev(const void *x_dev, int64_t x_stride, int64_t start, int64_t step, int64_t n, int64_t nrow, int dtype, int mod, double rot_re, double rot_im,
+                              uint8_t *bits_dev, int64_t bits_stride)
+{
+    int rc = symdemap_check(1, mod, n, nrow, dtype, x_stride, start, step, bits_stride);   // (argument errors need no device)
+    if (rc || nrow == 0 || n == 0) return rc;
+    SK_CHECK(x_dev && bits_dev, SKDSP_ERR_BADARG, "mpsk_demap: null pointer");
+    API_BEGIN;
+    return symdemap_launch(x_dev, x_stride, start, step, n, nrow, dtype, 1, mod, nullptr, rot_re, rot_im, bits_dev, bits_stride, ctx().stream);
+}
+
+// host form of both demappers: r: the rows' scales (QAM; HOST pointer), bits: nrow contiguous rows of bps n bytes
+static int demap_host(int kind, const void *x, int64_t x_stride, int64_t start, int64_t step, int64_t n, int64_t nrow, int dtype, int mod, const double *r, double rot_re,
+                      double rot_im, uint8_t *bits)
+{
+    const int bps = sym_bits_per_symbol(kind, mod);
+    int rc = symdemap_check(kind, mod, n, nrow, dtype, x_stride, start, step, bps * n);
+    if (rc || nrow == 0 || n == 0) return rc;
+    SK_CHECK(x && bits && (kind || r), SKDSP_ERR_BADARG, "%s: null pointer", kind ? "mpsk_demap" : "qam_demap");
+    API_BEGIN;
+    const size_t bytes_out = (size_t)bps * (size_t)n * (size_t)nrow, r_off = round_up(bytes_out, 256);
+    void *x_dev = nullptr, *out_dev = nullptr;
+    if ((rc = stage_in(x, sym_span(x_stride, start, step, n, nrow) * dtype_size(dtype), &x_dev))) return rc;
+    if ((rc = ws_reserve(1, r_off + (size_t)nrow * sizeof(double) + 256, &out_dev))) return rc;
+    double *r_dev = reinterpret_cast<double *>((char *)out_dev + r_off);
+    if (!kind) SK_HIP(hipMemcpyAsync(r_dev, r, (size_t)nrow * sizeof(double), hipMemcpyHostToDevice, ctx().stream));
+    if ((rc = symdemap_launch(x_dev, x_stride, start, step, n, nrow, dtype, kind, mod, kind ? nullptr : r_dev, rot_re, rot_im, (uint8_t *)out_dev, bps * n, ctx().stream))) return rc;
+    return stage_out(bits, out_dev, bytes_out);
+}
+
+int skdsp_qam_demap_rows(const void *x, int64_t x_stride, int64_t start, int64_t step, int64_t n, int64_t nrow, int dtype, int mod, const double *r, uint8_t *bits)
+{
+    return demap_host(0, x, x_stride, start, step, n, nrow, dtype, mod, r, 1.0, 0.0, bits);
+}
+int skdsp_mpsk_demap_rows(const void *x, int64_t x_stride, int64_t start, int64_t step, int64_t n, int64_t nrow, int dtype, int mod, double rot_re, double rot_im,
+                          uint8_t *bits)
+{
+    return demap_host(1, x, x_stride, start, step, n, nrow, dtype, mod, nullptr, rot_re, rot_im, bits);
 }
 
 }  // extern "C"

@@ -354,4 +354,18 @@ int bitcount_check(int64_t tx_stride, int64_t rx_stride, int64_t n, int64_t nrow
 int bitcount_launch(const uint8_t *tx_dev, int64_t tx_stride, const uint8_t *rx_dev, int64_t rx_stride, int64_t n, int64_t nrow, int invert, int64_t *counts_dev,
                     hipStream_t s);
 
+// ---- Gray symbol mapping (symmap.hip): the symbol sequences of qam_gray_encode_bb / mpsk_gray_encode_bb and qam_gray_decode / mpsk_gray_decode over rows; the plans are symmap_core.hpp ----
+// kind 0 QAM, 1 MPSK; symbols are complex64 / complex128, symbol k of a row is element start + k step; bits are bytes 0 / 1 at any alignment.  No handle: the tables travel as arguments.
+int sym_bits_per_symbol(int kind, int mod);   // host-only: 0 for an order the family does not have
+int symmap_check(int kind, int mod, int64_t n, int64_t nrow, int dtype, int64_t bits_stride, int64_t y_stride);   // host-only
+int symmap_launch(const uint8_t *bits_dev, int64_t bits_stride, int64_t n, int64_t nrow, int kind, int mod, const double *tab_re_host, const double *tab_im_host, int ntab,
+                  int dtype, void *y_dev, int64_t y_stride, hipStream_t s);
+int symscale_check(int mod, int64_t n, int64_t nrow, int dtype, int64_t x_stride, int64_t start, int64_t step);   // host-only
+size_t symscale_scratch_bytes(int64_t n, int64_t nrow);                                                            // host-only: the partial moments of a launch
+int symscale_launch(const void *x_dev, int64_t x_stride, int64_t start, int64_t step, int64_t n, int64_t nrow, int dtype, int mod, double c, void *scratch_dev,
+                    double *r_dev, hipStream_t s);
+int symdemap_check(int kind, int mod, int64_t n, int64_t nrow, int dtype, int64_t x_stride, int64_t start, int64_t step, int64_t bits_stride);   // host-only
+int symdemap_launch(const void *x_dev, int64_t x_stride, int64_t start, int64_t step, int64_t n, int64_t nrow, int dtype, int kind, int mod, const double *r_dev,
+                    double rot_re, double rot_im, uint8_t *bits_dev, int64_t bits_stride, hipStream_t s);
+
 }  // namespace skdsp

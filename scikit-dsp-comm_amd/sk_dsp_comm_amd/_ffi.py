@@ -40,6 +40,8 @@ SYMBOLS = [
     "skdsp_blockcode_create", "skdsp_blockcode_encode", "skdsp_blockcode_encode_dev", "skdsp_blockcode_decode", "skdsp_blockcode_decode_dev",
     "skdsp_convcode_create", "skdsp_convcode_encode_rows", "skdsp_convcode_encode_rows_dev", "skdsp_puncture_out_len", "skdsp_depuncture_out_len",
     "skdsp_puncture_rows", "skdsp_puncture_rows_dev", "skdsp_depuncture_rows", "skdsp_depuncture_rows_dev", "skdsp_bit_count_rows", "skdsp_bit_count_rows_dev",
+    "skdsp_gray_map_rows", "skdsp_gray_map_rows_dev", "skdsp_qam_scale_rows", "skdsp_qam_scale_rows_dev", "skdsp_qam_demap_rows", "skdsp_qam_demap_rows_dev",
+    "skdsp_mpsk_demap_rows", "skdsp_mpsk_demap_rows_dev",
     "skdsp_dist_unique_id", "skdsp_dist_init", "skdsp_dist_shutdown", "skdsp_dist_comm_count", "skdsp_dist_barrier",
     "skdsp_dist_allreduce_max", "skdsp_dist_allreduce_sum", "skdsp_dist_sendrecv", "skdsp_dist_allgather", "skdsp_dist_halo_exchange", "skdsp_fir_filter_shard_dev",
 ]
@@ -162,6 +164,15 @@ def load():
             L.skdsp_puncture_rows.argtypes = L.skdsp_puncture_rows_dev.argtypes = [vp, i64, i64, ci, u64, u64, ci, vp]
             L.skdsp_depuncture_rows.argtypes = L.skdsp_depuncture_rows_dev.argtypes = [vp, i64, i64, ci, u64, u64, ci, vp, vp]
             L.skdsp_bit_count_rows.argtypes = L.skdsp_bit_count_rows_dev.argtypes = [vp, i64, vp, i64, i64, i64, ci, vp]
+        if hasattr(L, "skdsp_gray_map_rows"):
+            dbl = ctypes.c_double
+            L.skdsp_gray_map_rows.argtypes = [vp, i64, i64, ci, ci, vp, vp, ci, ci, vp]
+            L.skdsp_gray_map_rows_dev.argtypes = [vp, i64, i64, i64, ci, ci, vp, vp, ci, ci, vp, i64]
+            L.skdsp_qam_scale_rows.argtypes = L.skdsp_qam_scale_rows_dev.argtypes = [vp, i64, i64, i64, i64, i64, ci, ci, dbl, vp]
+            L.skdsp_qam_demap_rows.argtypes = [vp, i64, i64, i64, i64, i64, ci, ci, vp, vp]
+            L.skdsp_qam_demap_rows_dev.argtypes = [vp, i64, i64, i64, i64, i64, ci, ci, vp, vp, i64]
+            L.skdsp_mpsk_demap_rows.argtypes = [vp, i64, i64, i64, i64, i64, ci, ci, dbl, dbl, vp]
+            L.skdsp_mpsk_demap_rows_dev.argtypes = [vp, i64, i64, i64, i64, i64, ci, ci, dbl, dbl, vp, i64]
         L.skdsp_dist_unique_id.argtypes = [vp]
         L.skdsp_dist_init.argtypes = [ci, ci, vp]
         L.skdsp_dist_comm_count.argtypes = [ctypes.POINTER(ci)]
@@ -860,6 +871,161 @@ class ConvCodeKernel:
     puncture_rows_dev = staticmethod(puncture_rows_dev)
     depuncture_rows = staticmethod(depuncture_rows)
     depuncture_rows_dev = staticmethod(depuncture_rows_dev)
+
+
+# --------------------------------------------------------------------------
+# Gray symbol mapping (csrc/symmap.hip): the two ends of an M-QAM / M-PSK BER loop
+# --------------------------------------------------------------------------
+QAM, MPSK = 0, 1
+_SYM_ORDERS = {QAM: (2, 4, 16, 64, 256), MPSK: (2, 4, 8, 16, 32)}
+_SYM_ERR = {QAM: 'M must be 2, 4, 16, 64, 256', MPSK: 'M must be 2, 4, 8, 16, or 32'}
+
+
+def sym_bits(kind, mod):
+    """Bits per symbol of the order; ValueError with the reference's text for an order the family does not have."""
+    if kind not in _SYM_ORDERS or mod not in _SYM_ORDERS[kind]:
+        raise ValueError(_SYM_ERR.get(kind, "kind must be QAM (0) or MPSK (1)"))
+    return int(mod).bit_length() - 1
+
+
+def gray_table(kind, mod, dtype=np.complex128):
+    """(tab_re, tab_im) float64: the constellation by MSB-first word, computed with the reference's own NumPy operations
+    (digitalcom.py:1626-1681, 1784-1826); for complex64 output rounded to float32 here.  QAM of 4 points and more: the sqrt(mod) levels."""
+    bps = sym_bits(kind, mod)
+    if mod == 2:
+        pts = (2 * np.arange(2) - 1).astype(np.complex128)
+    elif kind == QAM:
+        x_m = np.sqrt(mod) - 1
+        lut = _bin2gray(bps // 2)
+        pts = ((2 * lut - x_m) + 1j * (2 * lut - x_m)) / x_m      # complex / real scalar, as x_IQ / x_m
+    else:
+        lut = _bin2gray(bps)
+        pts = np.exp(1j * (2 * np.pi * lut / mod + (np.pi / mod if mod == 4 else 0.0)))
+    if np.dtype(dtype) == np.complex64:
+        pts = pts.astype(np.complex64).astype(np.complex128)
+    elif np.dtype(dtype) != np.complex128:
+        raise TypeError("gray_map: complex64 or complex128 symbols (got %s)" % np.dtype(dtype))
+    return np.ascontiguousarray(pts.real), np.ascontiguousarray(pts.imag)
+
+
+def _bin2gray(width):
+    """the reference's bin2gray tables: entry k is the running XOR of k's bits from the MSB down"""
+    v = np.arange(2 ** width)
+    shift = 1
+    while shift < width:
+        v = v ^ (v >> shift)
+        shift *= 2
+    return v
+
+
+def qam_scale_const(mod):
+    """c of s = np.std(x_hat) * c (digitalcom.py:1703)"""
+    return float(np.sqrt(3 / (2 * (mod - 1))))
+
+
+def _mpsk_rot():
+    r = np.exp(-1j * np.pi / 4)
+    return float(r.real), float(r.imag)
+
+
+def _sym_rows(x, what):
+    x = np.asarray(x)
+    if x.ndim != 2:
+        raise ValueError("%s: a 2-D array, one frame per row" % what)
+    if x.dtype not in (np.complex64, np.complex128):
+        raise TypeError("%s: complex64 or complex128 symbols (got %s)" % (what, x.dtype))
+    return np.ascontiguousarray(x)
+
+
+def sym_count(width, start, step):
+    """Symbols of a row of `width` elements read as row[start::step]"""
+    if start < 0 or step < 1:
+        raise ValueError("need start >= 0 and step >= 1")
+    return max(0, (width - start + step - 1) // step)
+
+
+def gray_map_rows(bits, kind, mod, dtype=np.complex128):
+    """(nrow, nbits) bytes 0 / 1 -> (nrow, nbits // bps) points of `dtype` (csrc/symmap.hip: symmap_kernel); trailing bits that do not fill a
+    symbol are dropped."""
+    bps = sym_bits(kind, mod)
+    bits = np.asarray(bits)
+    if bits.ndim != 2:
+        raise ValueError("gray_map_rows: a 2-D array, one frame per row")
+    n = bits.shape[1] // bps
+    bits = np.ascontiguousarray(bits[:, :n * bps], dtype=np.uint8)
+    tre, tim = gray_table(kind, mod, dtype)
+    y = np.empty((bits.shape[0], n), dtype=dtype)
+    check(load().skdsp_gray_map_rows(_ptr(bits), n, bits.shape[0], kind, mod, _ptr(tre), _ptr(tim), tre.size, code_of(dtype), _ptr(y)))
+    return y
+
+
+def gray_map_rows_host(bits, kind, mod, dtype=np.complex128):
+    """gray_map_rows in NumPy (no GPU): the same table, looked up by the MSB-first words -- the yardstick of the kernel."""
+    bps = sym_bits(kind, mod)
+    bits = np.asarray(bits)
+    n = bits.shape[1] // bps
+    words = (bits[:, :n * bps].reshape(bits.shape[0], n, bps).astype(np.int64) & 1) @ (2 ** np.arange(bps - 1, -1, -1))
+    tre, tim = gray_table(kind, mod, dtype)
+    y = np.empty(words.shape, dtype=np.complex128)
+    if kind == QAM and mod > 2:
+        half = bps // 2
+        y.real, y.imag = tre[words >> half], tre[words & (2 ** half - 1)]
+    else:
+        y.real, y.imag = tre[words], tim[words]
+    return y.astype(dtype)
+
+
+def gray_map_rows_dev(bits_ptr, bits_stride, n, nrow, kind, mod, dtype, y_ptr, y_stride=None):
+    """Device pointers: n symbols per row from bps n bytes; bits_stride in bytes, y_stride in elements (default n)."""
+    tre, tim = gray_table(kind, mod, dtype)
+    check(load().skdsp_gray_map_rows_dev(ctypes.c_void_p(bits_ptr), int(bits_stride), int(n), int(nrow), kind, mod, _ptr(tre), _ptr(tim), tre.size, code_of(dtype),
+                                         ctypes.c_void_p(y_ptr), int(n if y_stride is None else y_stride)))
+
+
+def qam_scale_rows(x, mod, start=0, step=1):
+    """(nrow, width) complex -> float64[nrow]: r = 1 / (np.std(row[start::step]) * sqrt(3 / (2 (mod - 1)))) (csrc/symmap.hip: symscale_kernel)"""
+    sym_bits(QAM, mod)
+    x = _sym_rows(x, "qam_scale_rows")
+    n = sym_count(x.shape[1], start, step)
+    r = np.empty(x.shape[0], dtype=np.float64)
+    check(load().skdsp_qam_scale_rows(_ptr(x), x.shape[1], int(start), int(step), n, x.shape[0], code_of(x.dtype), mod, qam_scale_const(mod), _ptr(r)))
+    return r
+
+
+def qam_scale_rows_dev(x_ptr, x_stride, start, step, n, nrow, dtype, mod, r_ptr):
+    """Device pointers; x_stride, start, step in elements; r: nrow float64, left on the device (and not checked)."""
+    check(load().skdsp_qam_scale_rows_dev(ctypes.c_void_p(x_ptr), int(x_stride), int(start), int(step), int(n), int(nrow), code_of(dtype), mod, qam_scale_const(mod),
+                                          ctypes.c_void_p(r_ptr)))
+
+
+def gray_demap_rows(x, kind, mod, start=0, step=1, r=None):
+    """(nrow, width) complex -> (nrow, bps n) bytes 0 / 1, n = len(row[start::step]) (csrc/symmap.hip: symdemap_kernel).  QAM: r is the rows'
+    scale, float64[nrow] (qam_scale_rows, or the caller's own)."""
+    bps = sym_bits(kind, mod)
+    x = _sym_rows(x, "gray_demap_rows")
+    n = sym_count(x.shape[1], start, step)
+    bits = np.empty((x.shape[0], bps * n), dtype=np.uint8)
+    L = load()
+    if kind == QAM:
+        r = np.ascontiguousarray(r, dtype=np.float64).reshape(-1)
+        if r.size != x.shape[0]:
+            raise ValueError("gray_demap_rows: one scale per row")
+        check(L.skdsp_qam_demap_rows(_ptr(x), x.shape[1], int(start), int(step), n, x.shape[0], code_of(x.dtype), mod, _ptr(r), _ptr(bits)))
+    else:
+        check(L.skdsp_mpsk_demap_rows(_ptr(x), x.shape[1], int(start), int(step), n, x.shape[0], code_of(x.dtype), mod, *_mpsk_rot(), _ptr(bits)))
+    return bits
+
+
+def gray_demap_rows_dev(x_ptr, x_stride, start, step, n, nrow, dtype, kind, mod, bits_ptr, bits_stride=None, r_ptr=None):
+    """Device pointers; bits_stride in bytes (default bps n); QAM: r_ptr is the device pointer of the rows' scales."""
+    bps = sym_bits(kind, mod)
+    bs = int(bps * n if bits_stride is None else bits_stride)
+    if kind == QAM:
+        check(load().skdsp_qam_demap_rows_dev(ctypes.c_void_p(x_ptr), int(x_stride), int(start), int(step), int(n), int(nrow), code_of(dtype), mod,
+                                              ctypes.c_void_p(r_ptr or None), ctypes.c_void_p(bits_ptr), bs))
+    else:
+        check(load().skdsp_mpsk_demap_rows_dev(ctypes.c_void_p(x_ptr), int(x_stride), int(start), int(step), int(n), int(nrow), code_of(dtype), mod, *_mpsk_rot(),
+                                               ctypes.c_void_p(bits_ptr), bs))
 
 
 class IirKernel(_HostCalls):

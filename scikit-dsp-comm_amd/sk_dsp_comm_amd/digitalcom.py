@@ -9,6 +9,8 @@ the GPU (sigsys.pulse_shape -> multirate_FIR.up -> fir_direct.hip / fir_ols.hip)
   farrow_resample(x, fs_old, fs_new, i_ord, alpha)                       digitalcom.py:53-235
   my_psd(x, NFFT, Fs)                                                    digitalcom.py:1051-1086  (sigsys.my_psd: csrc/psd.hip)
   bit_errors(tx_data, rx_data, n_corr, n_transient)                      digitalcom.py:353-415    (the count: csrc/convcode.hip)
+  qam_gray_decode(x_hat, mod), mpsk_gray_decode(x_hat, mod)              digitalcom.py:1684-1739, 1829-1883  (csrc/symmap.hip)
+  qam_gray_map_rows, mpsk_gray_map_rows, qam_gray_decode_rows, mpsk_gray_decode_rows: frame sets, one launch (csrc/symmap.hip)
 
 farrow_resample, the arbitrary-ratio resampler, is its own engine (csrc/farrow.hip): each output is a 4-tap FIR whose taps
 are polynomials in a fractional delay, evaluated on the GPU for all outputs at once (the reference loops over them in Python).
@@ -144,6 +146,173 @@ def mpsk_gray_encode_bb(n_symb, ns, mod=4, pulse='rect', alpha=0.35, m_span=6, e
         x, b = _shape(x_iq, ns, pulse, alpha, m_span)
         return x, b, data
     return x_iq, 1, data
+
+
+# ---- Gray demapping and the symbol mapping over frame sets (csrc/symmap.hip) -----------------------------------------
+def _sym_input(x_hat, name):
+    """x_hat as the kernels take it: one-dimensional complex64 / complex128.  Real input is widened to complex, integers run as float64,
+    float32 / complex64 stay and are widened exactly on the device."""
+    x = np.asarray(x_hat)
+    if x.ndim != 1:
+        raise ValueError("%s: x_hat must be one-dimensional (got shape %r)" % (name, x.shape))
+    if x.dtype.kind in "biu":
+        x = x.astype(np.float64)
+    if x.dtype.kind not in "fc":
+        raise TypeError("%s: x_hat must be numeric (got %s)" % (name, x.dtype))
+    if x.dtype == np.complex64 or x.dtype == np.float32 or x.dtype == np.float16:
+        return np.ascontiguousarray(x, dtype=np.complex64)
+    return np.ascontiguousarray(x, dtype=np.complex128)
+
+
+def _qam_words_host(x, mod, r):
+    """the reference's decision for complex128 symbols x and r = 1.0 / s: (kI, kQ) int16"""
+    x_m = 1 if mod == 2 else np.sqrt(mod) - 1
+    x = np.asarray(x, dtype=np.complex128)
+    with np.errstate(over="ignore"):
+        kr, ki = (x.real * r + x_m) / 2, (x.imag * r + x_m) / 2           # (x / s is x * (1.0 / s) in NumPy: complex array by real scalar)
+    return np.int16(np.clip(np.rint(kr), 0, x_m)), np.int16(np.clip(np.rint(ki), 0, x_m))
+
+
+def _bits_of_words(words, width):
+    """MSB-first bits of each word: (n, width) uint8"""
+    return ((np.asarray(words, dtype=np.int64)[:, None] >> np.arange(width - 1, -1, -1)) & 1).astype(np.uint8)
+
+
+def _qam_bits_host(x, mod, r):
+    bps = _ffi.sym_bits(_ffi.QAM, mod)
+    kI, kQ = _qam_words_host(x, mod, r)
+    if mod == 2:
+        return kI.astype(np.uint8)
+    half = bps // 2
+    return np.hstack((_bits_of_words(kI ^ (kI >> 1), half), _bits_of_words(kQ ^ (kQ >> 1), half))).reshape(-1)
+
+
+def _qam_scale_host(x, mod):
+    """r = 1.0 / (np.std(x) * sqrt(3 / (2 (mod - 1)))) of complex128 symbols; ValueError where it is zero or not finite"""
+    with np.errstate(all="ignore"):
+        s = np.std(np.asarray(x, dtype=np.complex128)) * np.sqrt(3 / (2 * (mod - 1)))
+        r = 1.0 / s if s != 0 else np.inf
+    return _check_scale(np.array([r]))[0]
+
+
+def _check_scale(r):
+    if not np.all(np.isfinite(r)) or np.any(r == 0):
+        raise ValueError("qam_gray_decode: the scale np.std(x_hat) is zero or not finite (an all-equal frame or a non-finite sample)")
+    return r
+
+
+def _mpsk_bits_host(x, mod):
+    bps = _ffi.sym_bits(_ffi.MPSK, mod)
+    x = np.asarray(x, dtype=np.complex128)
+    if mod == 4:
+        x = x * np.exp(-1j * np.pi / 4)
+    idx = np.mod(np.rint(np.angle(x) * mod / 2 / np.pi).astype(np.int64), mod)
+    return _bits_of_words(idx ^ (idx >> 1), bps).reshape(-1)
+
+
+def qam_gray_decode_host(x_hat, mod=4):
+    """qam_gray_decode in vectorised NumPy (no GPU): the yardstick of qam_gray_decode.  The symbols are widened to complex128 first, then the
+    reference's four steps."""
+    _ffi.sym_bits(_ffi.QAM, mod)
+    x = _sym_input(x_hat, "qam_gray_decode").astype(np.complex128)
+    if x.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    bits = _qam_bits_host(x, mod, _qam_scale_host(x, mod))
+    return bits.astype(np.int16 if mod == 2 else np.int64)
+
+
+def mpsk_gray_decode_host(x_hat, mod=4):
+    """mpsk_gray_decode in vectorised NumPy (no GPU): the yardstick of mpsk_gray_decode."""
+    _ffi.sym_bits(_ffi.MPSK, mod)
+    x = _sym_input(x_hat, "mpsk_gray_decode").astype(np.complex128)
+    if x.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    return _mpsk_bits_host(x, mod).astype(np.int64)
+
+
+def _sym_rows_input(x2d, name):
+    x = np.asarray(x2d)
+    if x.ndim != 2:
+        raise ValueError("%s: a 2-D array, one frame per row" % name)
+    return _sym_input(x.reshape(-1), name).reshape(x.shape)
+
+
+def qam_gray_decode_rows(x2d, mod=4, start=0, step=1):
+    """Beyond the reference: every row of x2d is its own frame with its own np.std; symbol k of a row is x2d[row, start + k * step] (the
+    idiom z[start::ns] behind the matched filter, without a compacting pass).  Returns uint8 (rows, n_symb * bps).  Two launches for the
+    rows' scales, one for the decisions (csrc/symmap.hip).  A row whose scale is zero or not finite raises ValueError."""
+    _ffi.sym_bits(_ffi.QAM, mod)
+    x = _sym_rows_input(x2d, "qam_gray_decode_rows")
+    n = _ffi.sym_count(x.shape[1], start, step)
+    if x.shape[0] == 0 or n == 0:
+        return np.zeros((x.shape[0], 0), dtype=np.uint8)
+    r = _check_scale(_ffi.qam_scale_rows(x, mod, start, step))
+    return _ffi.gray_demap_rows(x, _ffi.QAM, mod, start, step, r)
+
+
+def mpsk_gray_decode_rows(x2d, mod=4, start=0, step=1):
+    """Beyond the reference: mpsk_gray_decode of every row's x2d[row, start::step] in one launch; uint8 (rows, n_symb * bps)."""
+    _ffi.sym_bits(_ffi.MPSK, mod)
+    x = _sym_rows_input(x2d, "mpsk_gray_decode_rows")
+    n = _ffi.sym_count(x.shape[1], start, step)
+    if x.shape[0] == 0 or n == 0:
+        return np.zeros((x.shape[0], 0), dtype=np.uint8)
+    return _ffi.gray_demap_rows(x, _ffi.MPSK, mod, start, step)
+
+
+def qam_gray_decode(x_hat, mod=4):
+    """data_hat = qam_gray_decode(x_hat, mod=4), digitalcom.py:1684-1739: x_hat / (np.std(x_hat) * sqrt(3 / (2 (mod - 1)))), each component
+    decided to the nearest of sqrt(mod) levels, Gray decoded to [I bits, Q bits] per symbol, MSB first.  The reference loops over the symbols
+    in Python; here np.std is a deterministic float64 merge of partial moments on the GPU and every decision is the reference's own float64
+    operations in its order (csrc/symmap.hip).  Returns int64 (mod 2: the int16 level array, like the reference).
+
+    Deliberate differences (tests/golden/g22_conventions.json): a bad order raises the reference's ValueError for an empty x_hat too;
+    an empty x_hat returns an empty int64 array without the reference's warnings; a scale that is zero or not finite (an all-equal frame, a
+    non-finite sample) raises ValueError where the reference casts NaN to an integer; real input is widened to complex (the reference then
+    divides instead of multiplying by the reciprocal: one ulp, on a threshold only); integer input runs as float64; float32 / complex64
+    input is widened exactly and decided in float64 (the reference takes np.std in float32)."""
+    _ffi.sym_bits(_ffi.QAM, mod)
+    x = _sym_input(x_hat, "qam_gray_decode")
+    if x.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    bits = qam_gray_decode_rows(x.reshape(1, -1), mod)[0]
+    return bits.astype(np.int16 if mod == 2 else np.int64)
+
+
+def mpsk_gray_decode(x_hat, mod=4):
+    """data_hat = mpsk_gray_decode(x_hat, mod=4), digitalcom.py:1829-1883: np.mod(rint(angle(x_hat) * mod / 2 / pi), mod) (mod 4: of x_hat
+    rotated by exp(-1j pi / 4)), Gray decoded, MSB first, int64.  The reference's quirks are kept: mod 2 decodes -1 to bit 1, 0 decodes as
+    angle 0, -1 - 0j as angle -pi.  One launch (csrc/symmap.hip).  Deliberate differences: as qam_gray_decode (bad order, empty input,
+    real / integer / single-precision input: the angle is always taken in float64)."""
+    _ffi.sym_bits(_ffi.MPSK, mod)
+    x = _sym_input(x_hat, "mpsk_gray_decode")
+    if x.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    return mpsk_gray_decode_rows(x.reshape(1, -1), mod)[0].astype(np.int64)
+
+
+def _map_rows(kind, bits2d, mod, dtype, name):
+    _ffi.sym_bits(kind, mod)
+    bits = np.asarray(bits2d)
+    if bits.ndim != 2:
+        raise ValueError("%s: a 2-D array of bits, one frame per row" % name)
+    if bits.size and np.any((bits != 0) & (bits != 1)):
+        raise ValueError("%s: bits 0 / 1 only" % name)
+    if np.dtype(dtype) not in (np.dtype(np.complex64), np.dtype(np.complex128)):
+        raise TypeError("%s: dtype must be complex64 or complex128" % name)
+    return _ffi.gray_map_rows(bits.astype(np.uint8), kind, mod, np.dtype(dtype))
+
+
+def qam_gray_map_rows(bits2d, mod=4, dtype=np.complex128):
+    """Beyond the reference: the symbol sequence qam_gray_encode_bb builds before shaping (x_IQ / x_m), for every row of bits at once on the
+    GPU; always complex (mod 2: imaginary part 0).  Trailing bits that do not fill a symbol are dropped, as the reference truncates ext_data.
+    complex128 values are bit-identical to the reference's, complex64 ones their float32 roundings (a table lookup of host-computed points)."""
+    return _map_rows(_ffi.QAM, bits2d, mod, dtype, "qam_gray_map_rows")
+
+
+def mpsk_gray_map_rows(bits2d, mod=4, dtype=np.complex128):
+    """Beyond the reference: the symbol sequence mpsk_gray_encode_bb builds before shaping (x_IQ), as qam_gray_map_rows."""
+    return _map_rows(_ffi.MPSK, bits2d, mod, dtype, "mpsk_gray_map_rows")
 
 
 # ---- the remaining lfilter(b, 1, .) callers of digitalcom.py (488, 608, 666, 1047, 1130) ------------------------------
