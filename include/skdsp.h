@@ -317,6 +317,30 @@ int skdsp_mpsk_demap_rows(const void *x, int64_t x_stride, int64_t start, int64_
 int skdsp_mpsk_demap_rows_dev(const void *x_dev, int64_t x_stride, int64_t start, int64_t step, int64_t n, int64_t nrow, int dtype, int mod, double rot_re, double rot_im,
                               uint8_t *bits_dev, int64_t bits_stride);
 
+/* The AWGN channel and the bit sources of the device-resident BER loops (csrc/channel.hip, csrc/channel_core.hpp): sigsys.cpx_awgn / cpx_awgn2
+ * (sigsys.py:2335-2454), digitalcom.awgn_channel (digitalcom.py:1259-1281), sigsys.pn_gen (sigsys.py:1947-1980) and random data bits, over the
+ * rows of a frame set.  Device pointers only.  The draw is counter based (Philox4x32-10, key = seed, counter = (block, row, tag)): element i of
+ * row r depends on (seed, first_row + r, first_index + i) alone, so a window of a row can be generated by itself and two runs are identical.
+ * One block is one complex normal (float64, radius up to 8.57 sigma); a real stream's element i is component i & 1 of block i >> 1.
+ *   awgn_rows:        y[r, i] = g[r] x[r, i] + sigma[r] z.  y_dtype float32 / float64 (real z) or complex64 / complex128 (complex z); x_dtype
+ *                     = y_dtype, or the real dtype of the same precision.  Strides in elements, pointers aligned to the element, y == x allowed.
+ *                     g_dev / sigma_dev: nrow float64 on the device (awgn_sigma_rows wrote them), or null to use the scalars g / sigma.
+ *   awgn_bits_rows:   bytes 0 / 1 -> the hard decision of 2 b - 1 + sigma z (real z) as bytes: 1, 0, 2 for an exact zero, 3 for not-a-number.
+ *   awgn_sigma_rows:  var = np.var(row) by the deterministic merge of partial moments behind qam_scale_rows; mode 0 (cpx_awgn): sigma =
+ *                     sqrt(ns var p / 2), g = 1 with p = 10^(-es_n0 / 10); mode 1 (cpx_awgn2): sigma = sqrt(var_w / 2), g = sqrt(1 / ns var_w / var p)
+ *                     with p = 10^(es_n0 / 10) and var_w linear.  The powers of ten are the caller's.
+ *   random_bits_rows: bit i of row r of the tag-1 stream, one byte each: bit k & 31 of word k >> 5 of block i >> 7, k = i & 127.
+ *   pn_rows:          y[r, i] = period[(phases[r] + first_index + i) mod q]; period_dev: q <= 65535 bytes, phases_dev: nrow int64 >= 0 or null.
+ * Bits have any byte alignment; strides of bits are bytes.  n = 0 and nrow = 0 are valid and launch nothing. */
+int skdsp_awgn_rows_dev(const void *x_dev, int64_t x_stride, int x_dtype, void *y_dev, int64_t y_stride, int y_dtype, int64_t n, int64_t nrow, const double *g_dev,
+                        const double *sigma_dev, double g, double sigma, uint64_t seed, int64_t first_index, int64_t first_row);
+int skdsp_awgn_bits_rows_dev(const uint8_t *x_dev, int64_t x_stride, uint8_t *y_dev, int64_t y_stride, int64_t n, int64_t nrow, const double *sigma_dev, double sigma,
+                             uint64_t seed, int64_t first_index, int64_t first_row);
+int skdsp_awgn_sigma_rows_dev(const void *x_dev, int64_t x_stride, int64_t n, int64_t nrow, int dtype, int mode, double ns, double p, double var_w, double *g_dev,
+                              double *sigma_dev);
+int skdsp_random_bits_rows_dev(uint8_t *y_dev, int64_t y_stride, int64_t n, int64_t nrow, uint64_t seed, int64_t first_index, int64_t first_row);
+int skdsp_pn_rows_dev(const uint8_t *period_dev, int q, const int64_t *phases_dev, uint8_t *y_dev, int64_t y_stride, int64_t n, int64_t nrow, int64_t first_index);
+
 /* Host-pointer entry points of a float32/complex64 handle deliver y as float64/complex128 (the
  * reference's result dtype, multirate_helper.py:108 etc.): widened on the device before the copy
  * back, so y must hold twice the bytes.  Device-pointer (_dev) entry points are not affected. */

@@ -511,4 +511,60 @@ int skdsp_mpsk_demap_rows(const void *x, int64_t x_stride, int64_t start, int64_
     return demap_host(1, x, x_stride, start, step, n, nrow, dtype, mod, nullptr, rot_re, rot_im, bits);
 }
 
+// ---------------------------------------------------------------- the AWGN channel and the bit sources (channel.hip): cpx_awgn / cpx_awgn2 / awgn_channel, random bits, pn_gen
+int skdsp_awgn_rows_dev(const void *x_dev, int64_t x_stride, int x_dtype, void *y_dev, int64_t y_stride, int y_dtype, int64_t n, int64_t nrow, const double *g_dev,
+                        const double *sigma_dev, double g, double sigma, uint64_t seed, int64_t first_index, int64_t first_row)
+{
+    int rc = awgn_check(x_dtype, y_dtype, n, nrow, x_stride, y_stride, first_index, first_row);   // (argument errors need no device)
+    if (rc || nrow == 0 || n == 0) return rc;
+    SK_CHECK(x_dev && y_dev, SKDSP_ERR_BADARG, "awgn: null pointer");
+    API_BEGIN;
+    return awgn_launch(x_dev, x_stride, x_dtype, y_dev, y_stride, y_dtype, n, nrow, g_dev, sigma_dev, g, sigma, seed, first_index, first_row, ctx().stream);
+}
+
+int skdsp_awgn_bits_rows_dev(const uint8_t *x_dev, int64_t x_stride, uint8_t *y_dev, int64_t y_stride, int64_t n, int64_t nrow, const double *sigma_dev, double sigma,
+                             uint64_t seed, int64_t first_index, int64_t first_row)
+{
+    int rc = chanbits_check("awgn_bits", n, nrow, x_stride, y_stride, first_index, first_row);
+    if (rc || nrow == 0 || n == 0) return rc;
+    SK_CHECK(x_dev && y_dev, SKDSP_ERR_BADARG, "awgn_bits: null pointer");
+    API_BEGIN;
+    return chanbits_launch(x_dev, x_stride, y_dev, y_stride, n, nrow, sigma_dev, sigma, seed, first_index, first_row, 0, ctx().stream);
+}
+
+int skdsp_random_bits_rows_dev(uint8_t *y_dev, int64_t y_stride, int64_t n, int64_t nrow, uint64_t seed, int64_t first_index, int64_t first_row)
+{
+    int rc = chanbits_check("random_bits", n, nrow, 0, y_stride, first_index, first_row);
+    if (rc || nrow == 0 || n == 0) return rc;
+    SK_CHECK(y_dev, SKDSP_ERR_BADARG, "random_bits: null pointer");
+    API_BEGIN;
+    return chanbits_launch(nullptr, 0, y_dev, y_stride, n, nrow, nullptr, 0.0, seed, first_index, first_row, 1, ctx().stream);
+}
+
+int skdsp_pn_rows_dev(const uint8_t *period_dev, int q, const int64_t *phases_dev, uint8_t *y_dev, int64_t y_stride, int64_t n, int64_t nrow, int64_t first_index)
+{
+    int rc = pn_check(q, n, nrow, y_stride, first_index);
+    if (rc || nrow == 0 || n == 0) return rc;
+    SK_CHECK(period_dev && y_dev, SKDSP_ERR_BADARG, "pn: null pointer");
+    API_BEGIN;
+    return pn_launch(period_dev, q, phases_dev, y_dev, y_stride, n, nrow, first_index, ctx().stream);
+}
+
+// the partial moments of a launch live in workspace 3 of the calling slot, as for skdsp_qam_scale_rows_dev
+int skdsp_awgn_sigma_rows_dev(const void *x_dev, int64_t x_stride, int64_t n, int64_t nrow, int dtype, int mode, double ns, double p, double var_w, double *g_dev,
+                              double *sigma_dev)
+{
+    SK_CHECK(mode == 0 || mode == 1, SKDSP_ERR_BADARG, "awgn_sigma: mode 0 (cpx_awgn) or 1 (cpx_awgn2)");
+    SK_CHECK(dtype >= SKDSP_F32 && dtype <= SKDSP_C128, SKDSP_ERR_BADARG, "awgn_sigma: float32, complex64, float64 or complex128 rows (dtype code %d)", dtype);
+    SK_CHECK(n >= 1 && nrow >= 0 && x_stride >= 0, SKDSP_ERR_BADARG, "awgn_sigma: rows of at least one element (n = %lld, nrow = %lld)", (long long)n, (long long)nrow);
+    if (nrow == 0) return SKDSP_OK;
+    SK_CHECK(x_dev && g_dev && sigma_dev, SKDSP_ERR_BADARG, "awgn_sigma: null pointer");
+    API_BEGIN;
+    void *scratch = nullptr;
+    int rc = ws_reserve(3, symscale_scratch_bytes(n, nrow) + 256, &scratch);
+    if (rc) return rc;
+    if ((rc = symvar_launch(x_dev, x_stride, n, nrow, dtype, scratch, sigma_dev, ctx().stream))) return rc;
+    return awgn_sigma_launch(mode, ns, p, var_w, nrow, g_dev, sigma_dev, ctx().stream);
+}
+
 }  // extern "C"

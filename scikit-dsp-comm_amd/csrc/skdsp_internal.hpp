@@ -367,5 +367,19 @@ int symscale_launch(const void *x_dev, int64_t x_stride, int64_t start, int64_t 
 int symdemap_check(int kind, int mod, int64_t n, int64_t nrow, int dtype, int64_t x_stride, int64_t start, int64_t step, int64_t bits_stride);   // host-only
 int symdemap_launch(const void *x_dev, int64_t x_stride, int64_t start, int64_t step, int64_t n, int64_t nrow, int dtype, int kind, int mod, const double *r_dev,
                     double rot_re, double rot_im, uint8_t *bits_dev, int64_t bits_stride, hipStream_t s);
+// var_dev[row] = np.var of the row (M2 / n of the same merge of partial moments), rows of any of the four dtypes; scratch_dev as for symscale_launch
+int symvar_launch(const void *x_dev, int64_t x_stride, int64_t n, int64_t nrow, int dtype, void *scratch_dev, double *var_dev, hipStream_t s);
+
+// ---- the AWGN channel and the bit sources (channel.hip): cpx_awgn / cpx_awgn2 / awgn_channel, random data bits, pn_gen over rows; the draw and the plans are channel_core.hpp ----
+// The value of element i of row r depends on (seed, first_row + r, first + i) only.  Strides in elements (bytes for bits); no handle: the plans travel as arguments.
+int awgn_check(int x_dtype, int y_dtype, int64_t n, int64_t nrow, int64_t x_stride, int64_t y_stride, int64_t first, int64_t first_row);   // host-only
+int awgn_launch(const void *x_dev, int64_t x_stride, int x_dtype, void *y_dev, int64_t y_stride, int y_dtype, int64_t n, int64_t nrow, const double *g_dev,
+                const double *sigma_dev, double g, double sigma, uint64_t seed, int64_t first, int64_t first_row, hipStream_t s);
+int chanbits_check(const char *name, int64_t n, int64_t nrow, int64_t x_stride, int64_t y_stride, int64_t first, int64_t first_row);          // host-only
+int chanbits_launch(const uint8_t *x_dev, int64_t x_stride, uint8_t *y_dev, int64_t y_stride, int64_t n, int64_t nrow, const double *sigma_dev, double sigma, uint64_t seed,
+                    int64_t first, int64_t first_row, int random, hipStream_t s);
+int pn_check(int Q, int64_t n, int64_t nrow, int64_t y_stride, int64_t first);                                                                // host-only
+int pn_launch(const uint8_t *period_dev, int Q, const int64_t *phases_dev, uint8_t *y_dev, int64_t y_stride, int64_t n, int64_t nrow, int64_t first, hipStream_t s);
+int awgn_sigma_launch(int mode, double ns, double p, double var_w, int64_t nrow, double *g_dev, double *sigma_dev, hipStream_t s);
 
 }  // namespace skdsp

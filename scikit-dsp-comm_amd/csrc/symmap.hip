@@ -10,6 +10,8 @@
 //                          symbols, the lanes merged by a fixed tree in LDS, one partial per item into scratch.
 //   symscale_merge_kernel  one workgroup per row: the row's partials dealt in contiguous shares, merged in order, then the same tree;
 //                          r = 1 / (sqrt(M2 / n) c) as one float64.  No atomics anywhere: the same input gives the same bits.
+//                          (symvar_launch: the same two kernels over rows of any dtype, real ones included, storing np.var = M2 / n -- the
+//                          variance behind the channel's sigma and gain, channel.hip.)
 //   symdemap_kernel        the same items: each symbol decided (qam_decide with the row's r read from device memory, or mpsk_index), its bits
 //                          put into an LDS image laid out by the output run's alignment, which leaves in aligned 16-byte chunks.
 // Nothing outside a row's bits, its symbols start + k step (k < n) and its output run is read or written.
@@ -33,6 +35,8 @@ struct DevMem {
         *re = (double)v.x;
         *im = (double)v.y;
     }
+    __device__ __forceinline__ double ld_f32(const float *g) const { return (double)*g; }
+    __device__ __forceinline__ double ld_f64(const double *g) const { return *g; }
     __device__ __forceinline__ void ld_c128(const double *g, double *re, double *im) const
     {
         const double2 v = *reinterpret_cast<const double2 *>(g);
@@ -82,6 +86,8 @@ struct ScaleArgs {
     int64_t x_stride, start, step, n;
     uint32_t items;
     int c64;
+    int real = 0;         // 0: complex symbols (c64: complex64); 1: float32, 2: float64 values
+    int var = 0;          // what r takes: 0 1 / (std c), 1 the variance M2 / n
     double c;
     sym::Moments *part;   // [nrow][items]
     double *r;            // [nrow]
@@ -101,8 +107,13 @@ __global__ __launch_bounds__(sym::kThreads) void symscale_kernel(ScaleArgs a)
     const int t = threadIdx.x;
     const int64_t row = blockIdx.x / a.items, it = blockIdx.x - row * a.items;
     const int len = sym::item_len(a.n, it);
-    const void *xrow = a.c64 ? (const void *)(static_cast<const float *>(a.x) + 2 * row * a.x_stride) : (const void *)(static_cast<const double *>(a.x) + 2 * row * a.x_stride);
-    slot[t] = sym::scale_lane(DevMem(), xrow, a.start + sym::item_first(it) * a.step, a.step, a.c64, len, t);
+    if (a.real) {
+        const void *xrow = a.real == 1 ? (const void *)(static_cast<const float *>(a.x) + row * a.x_stride) : (const void *)(static_cast<const double *>(a.x) + row * a.x_stride);
+        slot[t] = sym::scale_lane_real(DevMem(), xrow, a.start + sym::item_first(it) * a.step, a.step, a.real == 1, len, t);
+    } else {
+        const void *xrow = a.c64 ? (const void *)(static_cast<const float *>(a.x) + 2 * row * a.x_stride) : (const void *)(static_cast<const double *>(a.x) + 2 * row * a.x_stride);
+        slot[t] = sym::scale_lane(DevMem(), xrow, a.start + sym::item_first(it) * a.step, a.step, a.c64, len, t);
+    }
     tree_merge(slot, t);
     if (t == 0) a.part[blockIdx.x] = slot[0];
 }
@@ -118,7 +129,7 @@ __global__ __launch_bounds__(sym::kThreads) void symscale_merge_kernel(ScaleArgs
     for (int64_t j = lo; j < hi; ++j) m = sym::moments_merge(m, part[j]);
     slot[t] = m;
     tree_merge(slot, t);
-    if (t == 0) a.r[blockIdx.x] = sym::scale_of(slot[0], a.c);
+    if (t == 0) a.r[blockIdx.x] = a.var ? sym::var_of(slot[0]) : sym::scale_of(slot[0], a.c);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ demap
@@ -235,6 +246,37 @@ int symscale_launch(const void *x_dev, int64_t x_stride, int64_t start, int64_t 
     hipLaunchKernelGGL(symscale_merge_kernel, dim3((unsigned)nrow), dim3(sym::kThreads), 0, s, a);
     SK_HIP(hipGetLastError());
     note_path("symscale");
+    return SKDSP_OK;
+}
+
+// var_dev[row] = np.var(x[row, k], k < n) = M2 / n of the same merge, for rows of any of the four dtypes (the channel's sigma and gain);
+// scratch_dev as for symscale_launch
+int symvar_launch(const void *x_dev, int64_t x_stride, int64_t n, int64_t nrow, int dtype, void *scratch_dev, double *var_dev, hipStream_t s)
+{
+    SK_CHECK(dtype >= SKDSP_F32 && dtype <= SKDSP_C128, SKDSP_ERR_BADARG, "row_var: float32, complex64, float64 or complex128 rows (dtype code %d)", dtype);
+    SK_CHECK(n >= 1 && nrow >= 0 && n < ((int64_t)1 << 40) && x_stride >= 0, SKDSP_ERR_BADARG, "row_var: rows of 1 ... 2^40 - 1 elements (n = %lld, nrow = %lld)", (long long)n, (long long)nrow);
+    SK_CHECK(grid_fits(sym::items_per_row(n), nrow), SKDSP_ERR_BADARG, "row_var: %lld rows of %lld elements in one launch", (long long)nrow, (long long)n);
+    if (nrow == 0) return SKDSP_OK;
+    SK_CHECK(x_dev && var_dev && scratch_dev, SKDSP_ERR_BADARG, "row_var: null pointer");
+    SK_CHECK(((uintptr_t)x_dev & (dtype_size(dtype) - 1)) == 0 && ((uintptr_t)var_dev & 7) == 0, SKDSP_ERR_BADARG, "row_var: the pointers must be aligned to their elements");
+    ScaleArgs a;
+    a.x = x_dev;
+    a.x_stride = x_stride;
+    a.start = 0;
+    a.step = 1;
+    a.n = n;
+    a.items = (uint32_t)sym::items_per_row(n);
+    a.c64 = dtype == SKDSP_C64;
+    a.real = dtype == SKDSP_F32 ? 1 : dtype == SKDSP_F64 ? 2 : 0;
+    a.var = 1;
+    a.c = 1.0;
+    a.part = static_cast<sym::Moments *>(scratch_dev);
+    a.r = var_dev;
+    hipLaunchKernelGGL(symscale_kernel, dim3((unsigned)(a.items * nrow)), dim3(sym::kThreads), 0, s, a);
+    SK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(symscale_merge_kernel, dim3((unsigned)nrow), dim3(sym::kThreads), 0, s, a);
+    SK_HIP(hipGetLastError());
+    note_path("symvar");
     return SKDSP_OK;
 }
 

@@ -360,6 +360,25 @@ template <class Mem> SK_HD Moments scale_lane(const Mem &m, const void *row, int
     }
     return moments_lane(re, im, cnt);
 }
+// the same over a row of REAL values, float32 (f32) or float64, each a symbol on the real axis (the channel's np.var of a real signal):
+// element sym0 + i step.  Mem: ld_f32(const float *), ld_f64(const double *), the value widened exactly
+template <class Mem> SK_HD Moments scale_lane_real(const Mem &m, const void *row, int64_t sym0, int64_t step, int f32, int len, int t)
+{
+    double re[kSymRun], im[kSymRun];
+    int cnt = 0;
+    for (int u = 0; u < kSymRun; ++u) {
+        const int i = lane_sym(t, u);
+        if (i < len) {
+            const int64_t e = sym0 + i * step;
+            re[cnt] = f32 ? m.ld_f32(static_cast<const float *>(row) + e) : m.ld_f64(static_cast<const double *>(row) + e);
+            im[cnt] = 0.0;
+            ++cnt;
+        }
+    }
+    return moments_lane(re, im, cnt);
+}
+// np.var of the merged row: M2 / n
+SK_HD double var_of(const Moments &a) { return a.m2 / a.n; }
 // lane t's symbols of the item decided into the output image (the item's bits at image bytes [lead, lead + bps len))
 template <class Mem> SK_HD void demap_lane(const Mem &m, const DemapPlan &p, const void *row, int64_t sym0, int64_t step, int c64, int len, double r, uint8_t *img, int lead, int t)
 {

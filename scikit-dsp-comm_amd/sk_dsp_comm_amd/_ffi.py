@@ -42,6 +42,7 @@ SYMBOLS = [
     "skdsp_puncture_rows", "skdsp_puncture_rows_dev", "skdsp_depuncture_rows", "skdsp_depuncture_rows_dev", "skdsp_bit_count_rows", "skdsp_bit_count_rows_dev",
     "skdsp_gray_map_rows", "skdsp_gray_map_rows_dev", "skdsp_qam_scale_rows", "skdsp_qam_scale_rows_dev", "skdsp_qam_demap_rows", "skdsp_qam_demap_rows_dev",
     "skdsp_mpsk_demap_rows", "skdsp_mpsk_demap_rows_dev",
+    "skdsp_awgn_rows_dev", "skdsp_awgn_bits_rows_dev", "skdsp_awgn_sigma_rows_dev", "skdsp_random_bits_rows_dev", "skdsp_pn_rows_dev",
     "skdsp_dist_unique_id", "skdsp_dist_init", "skdsp_dist_shutdown", "skdsp_dist_comm_count", "skdsp_dist_barrier",
     "skdsp_dist_allreduce_max", "skdsp_dist_allreduce_sum", "skdsp_dist_sendrecv", "skdsp_dist_allgather", "skdsp_dist_halo_exchange", "skdsp_fir_filter_shard_dev",
 ]
@@ -173,6 +174,13 @@ def load():
             L.skdsp_qam_demap_rows_dev.argtypes = [vp, i64, i64, i64, i64, i64, ci, ci, vp, vp, i64]
             L.skdsp_mpsk_demap_rows.argtypes = [vp, i64, i64, i64, i64, i64, ci, ci, dbl, dbl, vp]
             L.skdsp_mpsk_demap_rows_dev.argtypes = [vp, i64, i64, i64, i64, i64, ci, ci, dbl, dbl, vp, i64]
+        if hasattr(L, "skdsp_awgn_rows_dev"):
+            dbl, u64 = ctypes.c_double, ctypes.c_uint64
+            L.skdsp_awgn_rows_dev.argtypes = [vp, i64, ci, vp, i64, ci, i64, i64, vp, vp, dbl, dbl, u64, i64, i64]
+            L.skdsp_awgn_bits_rows_dev.argtypes = [vp, i64, vp, i64, i64, i64, vp, dbl, u64, i64, i64]
+            L.skdsp_awgn_sigma_rows_dev.argtypes = [vp, i64, i64, i64, ci, ci, dbl, dbl, dbl, vp, vp]
+            L.skdsp_random_bits_rows_dev.argtypes = [vp, i64, i64, i64, u64, i64, i64]
+            L.skdsp_pn_rows_dev.argtypes = [vp, ci, vp, vp, i64, i64, i64, i64]
         L.skdsp_dist_unique_id.argtypes = [vp]
         L.skdsp_dist_init.argtypes = [ci, ci, vp]
         L.skdsp_dist_comm_count.argtypes = [ctypes.POINTER(ci)]
@@ -1026,6 +1034,211 @@ def gray_demap_rows_dev(x_ptr, x_stride, start, step, n, nrow, dtype, kind, mod,
     else:
         check(load().skdsp_mpsk_demap_rows_dev(ctypes.c_void_p(x_ptr), int(x_stride), int(start), int(step), int(n), int(nrow), code_of(dtype), mod, *_mpsk_rot(),
                                                ctypes.c_void_p(bits_ptr), bs))
+
+
+# --------------------------------------------------------------------------
+# The AWGN channel and the bit sources (csrc/channel.hip): the middle and the start of a device-resident BER loop
+# --------------------------------------------------------------------------
+TAG_NORMAL, TAG_BITS = 0, 1
+SIGMA_AWGN, SIGMA_AWGN2 = 0, 1
+_U32 = np.uint64(0xffffffff)
+_LN2_HI, _LN2_LO = float.fromhex("0x1.62e42feep-1"), float.fromhex("0x1.a39ef35793c76p-33")
+_SQRT2, _TWO_PI = float.fromhex("0x1.6a09e667f3bcdp+0"), float.fromhex("0x1.921fb54442d18p+2")
+
+
+def new_seed():
+    """seed=None of the public functions: 64 bits of NumPy's global generator, so a script that calls np.random.seed stays reproducible"""
+    return int.from_bytes(np.random.bytes(8), "little")
+
+
+def philox_host(seed, row, blocks, tag):
+    """Philox4x32-10 (csrc/channel_core.hpp: philox) in NumPy: key = the 64-bit seed, counter = (block lo, block hi, row, tag).
+    blocks: integers < 2^64 -> four uint64 arrays holding the block's 32-bit words."""
+    blocks = np.asarray(blocks, dtype=np.uint64)
+    c0, c1 = blocks & _U32, blocks >> np.uint64(32)
+    c2 = np.full(blocks.shape, int(row) & 0xffffffff, dtype=np.uint64)
+    c3 = np.full(blocks.shape, int(tag) & 0xffffffff, dtype=np.uint64)
+    k0, k1 = int(seed) & 0xffffffff, (int(seed) >> 32) & 0xffffffff
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2     # 32 x 32 bits: no overflow
+        n0, n2 = (p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0), (p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1)
+        c1, c3, c0, c2 = p1 & _U32, p0 & _U32, n0, n2
+        k0, k1 = (k0 + 0x9E3779B9) & 0xffffffff, (k1 + 0xBB67AE85) & 0xffffffff
+    return c0, c1, c2, c3
+
+
+def neg_ln_u_host(k):
+    """-ln(k 2^-53) for integers 1 ... 2^53: channel_core.hpp's neg_ln_u, operation by operation"""
+    m, e = np.frexp(np.asarray(k, dtype=np.uint64).astype(np.float64))      # m in [1/2, 1): exact
+    m, e = m * 2.0, e.astype(np.int64) - 1 - 53
+    big = m >= _SQRT2
+    m, e = np.where(big, m * 0.5, m), e + big
+    s = (m - 1.0) / (m + 1.0)
+    z = s * s
+    p = np.full(z.shape, 1.0 / 25.0)
+    for d in (23.0, 21.0, 19.0, 17.0, 15.0, 13.0, 11.0, 9.0, 7.0, 5.0, 3.0):
+        p = p * z + 1.0 / d
+    lnm = 2.0 * s + 2.0 * s * (z * p)
+    ne = (-e).astype(np.float64)
+    return ne * _LN2_HI + (ne * _LN2_LO - lnm)
+
+
+def sincos_2pi_host(k):
+    """(cos, sin) of 2 pi k 2^-53 for integers 0 ... 2^53 - 1: channel_core.hpp's sincos_2pi, operation by operation"""
+    k = np.asarray(k, dtype=np.uint64)
+    octant = (k >> np.uint64(50)).astype(np.int64)
+    f = k & np.uint64((1 << 50) - 1)
+    f = np.where(octant & 1, np.uint64(1 << 50) - f, f)
+    x = (f.astype(np.float64) * 2.0 ** -53) * _TWO_PI
+    z = x * x
+    ps = np.full(z.shape, 1.0 / 355687428096000.0)
+    for c in (-1.0 / 1307674368000.0, 1.0 / 6227020800.0, -1.0 / 39916800.0, 1.0 / 362880.0, -1.0 / 5040.0, 1.0 / 120.0, -1.0 / 6.0):
+        ps = c + z * ps
+    sx = x + x * (z * ps)
+    pc = np.full(z.shape, -1.0 / 6402373705728000.0)
+    for c in (1.0 / 20922789888000.0, -1.0 / 87178291200.0, 1.0 / 479001600.0, -1.0 / 3628800.0, 1.0 / 40320.0, -1.0 / 720.0, 1.0 / 24.0):
+        pc = c + z * pc
+    cx = 1.0 - (0.5 * z - (z * z) * pc)
+    sw = ((octant + 1) & 2) != 0
+    ca, sa = np.where(sw, sx, cx), np.where(sw, cx, sx)
+    return np.where((octant + 2) & 4, -ca, ca), np.where(octant & 4, -sa, sa)
+
+
+def uniforms_host(seed, row, blocks):
+    """(k1 + 1, k2) of the tag-0 blocks: u1 = (k1 + 1) 2^-53 in (0, 1], u2 = k2 2^-53 in [0, 1)"""
+    w0, w1, w2, w3 = philox_host(seed, row, blocks, TAG_NORMAL)
+    return ((w0 << np.uint64(21)) | (w1 >> np.uint64(11))) + np.uint64(1), (w2 << np.uint64(21)) | (w3 >> np.uint64(11))
+
+
+def normals_of_uniforms_host(k1p, k2):
+    r = np.sqrt(2.0 * neg_ln_u_host(k1p))
+    c, s = sincos_2pi_host(k2)
+    return r * c, r * s
+
+
+def normals_host(seed, row, first, n, complex=True):
+    """Elements first ... first + n - 1 of row `row` of the normal stream: complex128 (one block each) or float64 (element i is component
+    i & 1 of block i >> 1), the same bits as the device kernels and the C++ emulation draw."""
+    first, n = int(first), int(n)
+    if n <= 0:
+        return np.zeros(0, dtype=np.complex128 if complex else np.float64)
+    if complex:
+        re, im = normals_of_uniforms_host(*uniforms_host(seed, row, np.uint64(first) + np.arange(n, dtype=np.uint64)))
+        z = np.empty(n, dtype=np.complex128)
+        z.real, z.imag = re, im
+        return z
+    b0, b1 = first >> 1, (first + n - 1) >> 1
+    re, im = normals_of_uniforms_host(*uniforms_host(seed, row, np.uint64(b0) + np.arange(b1 - b0 + 1, dtype=np.uint64)))
+    return np.stack([re, im], axis=1).reshape(-1)[first - 2 * b0:first - 2 * b0 + n]
+
+
+def random_bits_host(seed, row, first, n):
+    """Bits first ... first + n - 1 of row `row` of the bit stream, uint8 0 / 1: bit k & 31 of word k >> 5 of block i >> 7, k = i & 127"""
+    first, n = int(first), int(n)
+    if n <= 0:
+        return np.zeros(0, dtype=np.uint8)
+    b0, b1 = first >> 7, (first + n - 1) >> 7
+    w = np.stack(philox_host(seed, row, np.uint64(b0) + np.arange(b1 - b0 + 1, dtype=np.uint64), TAG_BITS), axis=1)   # (blocks, 4)
+    bits = (w[:, :, None] >> np.arange(32, dtype=np.uint64)[None, None, :]) & np.uint64(1)
+    return bits.reshape(-1).astype(np.uint8)[first - 128 * b0:first - 128 * b0 + n]
+
+
+def _per_row(v, nrow):
+    v = np.asarray(v, dtype=np.float64).reshape(-1)
+    return np.broadcast_to(v, (nrow,)) if v.size == 1 else v
+
+
+def awgn_rows_host(x2d, g, sigma, seed, dtype=None, first_index=0, first_row=0):
+    """awgn_kernel in NumPy: y[r, i] = g[r] x[r, i] + sigma[r] z(seed, first_row + r, first_index + i), the sum in float64 rounded once
+    to `dtype` (default: x's); a real x with a complex dtype gets the complex stream."""
+    x2d = np.asarray(x2d)
+    dtype = np.dtype(x2d.dtype if dtype is None else dtype)
+    nrow, n = x2d.shape
+    g, sigma = _per_row(g, nrow), _per_row(sigma, nrow)
+    cpx = dtype.kind == "c"
+    y = np.empty((nrow, n), dtype=np.complex128 if cpx else np.float64)
+    for r in range(nrow):
+        z = normals_host(seed, first_row + r, first_index, n, cpx)
+        xr = x2d[r].astype(np.complex128 if x2d.dtype.kind == "c" else np.float64)
+        if not cpx:
+            y[r] = g[r] * xr + sigma[r] * z
+        elif x2d.dtype.kind == "c":
+            y[r].real, y[r].imag = g[r] * xr.real + sigma[r] * z.real, g[r] * xr.imag + sigma[r] * z.imag
+        else:
+            y[r].real, y[r].imag = g[r] * xr + sigma[r] * z.real, 0.0 + sigma[r] * z.imag
+    return y.astype(dtype)
+
+
+def awgn_bits_rows_host(bits2d, sigma, seed, first_index=0, first_row=0):
+    """awgn_bits_kernel in NumPy: the hard decision of 2 b - 1 + sigma z as bytes -- 1, 0, 2 for an exact zero, 3 for not-a-number"""
+    bits2d = np.asarray(bits2d, dtype=np.uint8)
+    nrow, n = bits2d.shape
+    sigma = _per_row(sigma, nrow)
+    out = np.empty((nrow, n), dtype=np.uint8)
+    for r in range(nrow):
+        v = (2.0 * (bits2d[r] & 1) - 1.0) + sigma[r] * normals_host(seed, first_row + r, first_index, n, False)
+        out[r] = np.where(v > 0, 1, np.where(v < 0, 0, np.where(v == 0, 2, 3)))
+    return out
+
+
+def awgn_sigma_host(var, mode, ns, es_n0, var_w_dB=0.0):
+    """(g, sigma) of a row of variance var: cpx_awgn's (mode SIGMA_AWGN) or cpx_awgn2's (SIGMA_AWGN2) expressions in the reference's order"""
+    var = np.asarray(var, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        if mode == SIGMA_AWGN:
+            return np.ones_like(var), np.sqrt(ns * var * 10 ** (-es_n0 / 10.) / 2.)
+        var_w = 10 ** (var_w_dB / 10)
+        return np.sqrt(1 / ns * var_w / var * 10 ** (es_n0 / 10.)), np.full(var.shape, np.sqrt(var_w / 2))
+
+
+def _dp(d):
+    """the device address of a DeviceArray / DeviceBytes, or the integer itself"""
+    return ctypes.c_void_p((d.ptr if hasattr(d, "ptr") else int(d)) if d is not None else None)
+
+
+def awgn_rows_dev(xd, yd, n, nrow, seed, g=1.0, sigma=1.0, gd=None, sd=None, x_stride=None, y_stride=None, first_index=0, first_row=0,
+                  x_dtype=None, y_dtype=None):
+    """yd[r, i] = g xd[r, i] + sigma z (csrc/channel.hip: awgn_kernel).  xd, yd: DeviceArrays (or addresses with x_dtype / y_dtype), yd may be
+    xd; strides in elements (default n); gd / sd: DeviceArrays of nrow float64 (awgn_sigma_rows_dev), else the scalars g / sigma."""
+    xt, yt = code_of(xd.dtype if x_dtype is None else x_dtype), code_of(yd.dtype if y_dtype is None else y_dtype)
+    check(load().skdsp_awgn_rows_dev(_dp(xd), int(n if x_stride is None else x_stride), xt, _dp(yd), int(n if y_stride is None else y_stride), yt, int(n), int(nrow),
+                                     _dp(gd), _dp(sd), float(g), float(sigma), int(seed) & (2 ** 64 - 1), int(first_index), int(first_row)))
+
+
+def awgn_bits_rows_dev(xd, yd, n, nrow, seed, sigma=1.0, sd=None, x_stride=None, y_stride=None, first_index=0, first_row=0):
+    """bytes 0 / 1 -> hard decisions as bytes (awgn_bits_kernel); xd, yd: DeviceBytes or addresses at any alignment, strides in bytes"""
+    check(load().skdsp_awgn_bits_rows_dev(_dp(xd), int(n if x_stride is None else x_stride), _dp(yd), int(n if y_stride is None else y_stride), int(n), int(nrow),
+                                          _dp(sd), float(sigma), int(seed) & (2 ** 64 - 1), int(first_index), int(first_row)))
+
+
+def awgn_sigma_rows_dev(xd, n, nrow, mode, ns, es_n0, gd, sd, var_w_dB=0.0, x_stride=None, dtype=None):
+    """gd[r], sd[r] = cpx_awgn's (SIGMA_AWGN) or cpx_awgn2's (SIGMA_AWGN2) gain and sigma from np.var of row r, left on the device; the
+    powers of ten are computed here as the reference writes them."""
+    if mode == SIGMA_AWGN:
+        p, var_w = 10 ** (-es_n0 / 10.), 0.0
+    else:
+        p, var_w = 10 ** (es_n0 / 10.), 10 ** (var_w_dB / 10)
+    check(load().skdsp_awgn_sigma_rows_dev(_dp(xd), int(n if x_stride is None else x_stride), int(n), int(nrow), code_of(xd.dtype if dtype is None else dtype), int(mode),
+                                           float(ns), float(p), float(var_w), _dp(gd), _dp(sd)))
+
+
+def random_bits_rows_dev(yd, n, nrow, seed, y_stride=None, first_index=0, first_row=0):
+    """yd[r, i] = bit first_index + i of row first_row + r of the bit stream, one byte each (randbits_kernel)"""
+    check(load().skdsp_random_bits_rows_dev(_dp(yd), int(n if y_stride is None else y_stride), int(n), int(nrow), int(seed) & (2 ** 64 - 1), int(first_index), int(first_row)))
+
+
+def pn_rows_dev(period_d, q, yd, n, nrow, phases_d=None, y_stride=None, first_index=0):
+    """yd[r, i] = period[(phases[r] + first_index + i) mod q] (pn_kernel); period_d: q bytes, phases_d: nrow int64 or None, on the device"""
+    check(load().skdsp_pn_rows_dev(_dp(period_d), int(q), _dp(phases_d), _dp(yd), int(n if y_stride is None else y_stride), int(n), int(nrow), int(first_index)))
+
+
+def device_bytes_of(a):
+    """A DeviceBytes holding the bytes of a host array of any dtype"""
+    a = np.ascontiguousarray(a)
+    d = DeviceBytes(max(a.nbytes, 1))
+    if a.nbytes:
+        d.write(a.reshape(-1).view(np.uint8))
+    return d
 
 
 class IirKernel(_HostCalls):

@@ -543,3 +543,58 @@ def bit_errors_rows(tx2d, rx2d):
             raise ValueError("bit_errors_rows: bits 0 / 1 only")
     n = min(tx.shape[1], rx.shape[1])
     return n, _ffi.bit_count_rows(tx.astype(np.uint8), rx.astype(np.uint8), False, n)
+
+
+# ------------------------------------------------------------------------------------------------ awgn_channel (digitalcom.py:1259-1281)
+def _channel_bits(x, name, ndim):
+    x = np.asarray(x)
+    if x.ndim != ndim:
+        raise ValueError("%s: a %d-D array of bits" % (name, ndim))
+    if x.size and np.any((x != 0) & (x != 1)):
+        raise ValueError("%s: bits 0 / 1 only" % name)
+    return np.ascontiguousarray(x, dtype=np.uint8)
+
+
+def _channel_sigma(eb_n0_dB):
+    var_noise = 10 ** (-eb_n0_dB / 10) / 2
+    return float(np.sqrt(var_noise))
+
+
+def _decisions_as_float(d):
+    """the kernel's bytes as the reference's values: (sign + 1) / 2 is 1., 0., 0.5 for an exact zero and nan for what is not a number"""
+    return np.array([0.0, 1.0, 0.5, np.nan])[d]
+
+
+def awgn_channel_rows(bits2d, eb_n0_dB, seed=None):
+    """Beyond the reference: (nrow, n) bits -> (nrow, n) uint8 hard decisions, row r through the stream of row r, no float stream in between
+    (csrc/channel.hip: awgn_bits_kernel).  A byte is 1 or 0 (2: the sum was exactly zero, 3: it was not a number)."""
+    bits = _channel_bits(bits2d, "awgn_channel_rows", 2)
+    nrow, n = bits.shape
+    if nrow == 0 or n == 0:
+        return np.zeros((nrow, n), dtype=np.uint8)
+    seed = _ffi.new_seed() if seed is None else seed
+    xd = _ffi.device_bytes_of(bits)
+    try:
+        _ffi.awgn_bits_rows_dev(xd, xd, n, nrow, seed, sigma=_channel_sigma(eb_n0_dB))     # in place
+        return xd.read().reshape(nrow, n)
+    finally:
+        xd.free()
+
+
+def awgn_channel(x_bits, eb_n0_dB, seed=None):
+    """y_bits = awgn_channel(x_bits, eb_n0_dB), digitalcom.py:1259-1281: 0 / 1 -> -1 / +1, noise of variance 10^(-eb_n0_dB / 10) / 2, hard
+    decisions back to 0. / 1. (float64, 0.5 for a sum of exactly zero), on the GPU.
+
+    Deliberate differences (tests/golden/g23_conventions.json): the normals are this library's counter-based stream of `seed` (None: 64 bits
+    of NumPy's global generator); x_bits is one-dimensional and holds 0 / 1 only (ValueError otherwise); an empty input gives an empty array."""
+    bits = _channel_bits(x_bits, "awgn_channel", 1)
+    return _decisions_as_float(awgn_channel_rows(bits[None, :], eb_n0_dB, seed)[0])
+
+
+def awgn_channel_host(x_bits, eb_n0_dB, seed=None):
+    """awgn_channel in NumPy (no GPU): the yardstick of awgn_channel."""
+    bits = _channel_bits(x_bits, "awgn_channel", 1)
+    if bits.size == 0:
+        return np.zeros(0)
+    seed = _ffi.new_seed() if seed is None else seed
+    return _decisions_as_float(_ffi.awgn_bits_rows_host(bits[None, :], _channel_sigma(eb_n0_dB), seed)[0])

@@ -678,3 +678,157 @@ def simple_sa(x, NS, NFFT, fs, NAVG=1, window='boxcar'):
         f = fs * np.hstack((np.arange(-NFFTby2, 0), np.arange(NFFTby2))) / float(NFFT)
         Sx = np.hstack((Sx[NFFTby2:], Sx[0:NFFTby2]))
     return f, Sx
+
+
+# ------------------------------------------------------------------------------------------------ the AWGN channel (sigsys.py:2335-2454)
+def _awgn_input(x, name, ndim):
+    x = _gpu_dtype(np.asarray(x))
+    if x.ndim != ndim:
+        raise ValueError("%s: a %d-D signal array" % (name, ndim))
+    out = np.complex64 if x.dtype in (np.float32, np.complex64) else np.complex128
+    return np.ascontiguousarray(x), np.dtype(out)
+
+
+def _awgn_rows(x2d, out, mode, es_n0, ns, var_w, seed):
+    """rows on the device: variance -> (g, sigma) -> y, each row with its own variance and its own stream"""
+    nrow, n = x2d.shape
+    if nrow == 0 or n == 0:
+        return np.zeros((nrow, n), dtype=out)
+    seed = _ffi.new_seed() if seed is None else seed
+    xd = _ffi.DeviceArray.from_host(x2d.reshape(-1))
+    yd = _ffi.DeviceArray(nrow * n, out)
+    gd, sd = _ffi.DeviceArray(nrow, np.float64), _ffi.DeviceArray(nrow, np.float64)
+    try:
+        _ffi.awgn_sigma_rows_dev(xd, n, nrow, mode, ns, es_n0, gd, sd, var_w_dB=var_w)
+        _ffi.awgn_rows_dev(xd, yd, n, nrow, seed, gd=gd, sd=sd)
+        return yd.to_host().reshape(nrow, n)
+    finally:
+        for d in (xd, yd, gd, sd):
+            d.free()
+
+
+def _awgn_rows_host(x2d, out, mode, es_n0, ns, var_w, seed):
+    nrow, n = x2d.shape
+    if nrow == 0 or n == 0:
+        return np.zeros((nrow, n), dtype=out)
+    seed = _ffi.new_seed() if seed is None else seed
+    wide = x2d.astype(np.complex128 if x2d.dtype.kind == "c" else np.float64)
+    g, sigma = _ffi.awgn_sigma_host(np.var(wide, axis=1), mode, ns, es_n0, var_w)
+    return _ffi.awgn_rows_host(x2d, g, sigma, seed, out)
+
+
+def cpx_awgn(x, es_n0, ns, seed=None):
+    """y = cpx_awgn(x, es_n0, ns), sigsys.py:2335-2370: x + sqrt(ns var(x) 10^(-es_n0 / 10) / 2) (randn + 1j randn), the variance, the draw
+    and the sum on the GPU (csrc/symmap.hip's merge of partial moments, csrc/channel.hip: awgn_kernel).  x real or complex, one-dimensional.
+
+    Deliberate differences (tests/golden/g23_conventions.json): the normals are this library's counter-based stream of `seed` (None: 64 bits
+    of NumPy's global generator), not numpy.random.randn's values; float32 / complex64 in gives complex64 out (the float64 sum rounded once),
+    everything else complex128; an empty x gives an empty array."""
+    x, out = _awgn_input(x, "cpx_awgn", 1)
+    return _awgn_rows(x[None, :], out, _ffi.SIGMA_AWGN, es_n0, ns, 0.0, seed)[0]
+
+
+def cpx_awgn_host(x, es_n0, ns, seed=None):
+    """cpx_awgn in NumPy (no GPU): the same stream, np.var and the reference's expressions -- the yardstick of cpx_awgn."""
+    x, out = _awgn_input(x, "cpx_awgn", 1)
+    return _awgn_rows_host(x[None, :], out, _ffi.SIGMA_AWGN, es_n0, ns, 0.0, seed)[0]
+
+
+def cpx_awgn_rows(x2d, es_n0, ns, seed=None):
+    """Beyond the reference: cpx_awgn of every row of a frame set in one pass -- row r has its own variance and the stream of row r."""
+    x, out = _awgn_input(x2d, "cpx_awgn_rows", 2)
+    return _awgn_rows(x, out, _ffi.SIGMA_AWGN, es_n0, ns, 0.0, seed)
+
+
+def cpx_awgn2(x, es_n0, ns, var_w=0.0, seed=None):
+    """y = cpx_awgn2(x, es_n0, ns, var_w), sigsys.py:2373-2454: the noise variance held at 10^(var_w / 10), the signal scaled by
+    sqrt(1 / ns var_w / var(x) 10^(es_n0 / 10)).  Same kernels and the same deliberate differences as cpx_awgn."""
+    x, out = _awgn_input(x, "cpx_awgn2", 1)
+    return _awgn_rows(x[None, :], out, _ffi.SIGMA_AWGN2, es_n0, ns, var_w, seed)[0]
+
+
+def cpx_awgn2_host(x, es_n0, ns, var_w=0.0, seed=None):
+    """cpx_awgn2 in NumPy (no GPU): the yardstick of cpx_awgn2."""
+    x, out = _awgn_input(x, "cpx_awgn2", 1)
+    return _awgn_rows_host(x[None, :], out, _ffi.SIGMA_AWGN2, es_n0, ns, var_w, seed)[0]
+
+
+# ------------------------------------------------------------------------------------------------ bit sources (sigsys.py:1947-2050)
+# m_seq's feedback table: for register length m, the k in 1 ... m - 1 with taps[k] = 1 (its loop reads no other entry)
+_MSEQ_TAPS = {2: (1,), 3: (2,), 4: (3,), 5: (3,), 6: (5,), 7: (4,), 8: (4, 5, 6), 9: (5,), 10: (7,), 11: (9,), 12: (6, 8, 11), 13: (9, 10, 12),
+              14: (4, 8, 13), 15: (11,), 16: (2, 11, 15)}
+_MSEQ_CACHE = {}
+PN_HOST_MAX = 2 ** 16
+
+
+def _mseq_bytes(m):
+    """One period as uint8: an integer shift register started at all ones; out = the last cell, the new first cell = XOR over the taps k
+    of (last cell ^ cell m - 1 - k), bit for bit the reference's double loop."""
+    if m not in _MSEQ_TAPS:
+        raise ValueError('Invalid length specified')
+    if m not in _MSEQ_CACHE:
+        taps, sr, mask = _MSEQ_TAPS[m], (1 << m) - 1, (1 << m) - 1      # bit j = cell j
+        c = np.empty((1 << m) - 1, dtype=np.uint8)
+        for n in range(c.size):
+            last = (sr >> (m - 1)) & 1
+            c[n] = last
+            x = 0
+            for k in taps:
+                x ^= last ^ ((sr >> (m - 1 - k)) & 1)
+            sr = ((sr << 1) | x) & mask
+        _MSEQ_CACHE[m] = c
+    return _MSEQ_CACHE[m]
+
+
+def m_seq(m):
+    """One period (2^m - 1 values 0. / 1., float64) of the m-sequence, m = 2 ... 16, sigsys.py:1983-2050 (host: an integer register)."""
+    return _mseq_bytes(m).astype(np.float64)
+
+
+def pn_rows(nrow, n, m=5, phases=None):
+    """Beyond the reference: (nrow, n) uint8, row r = the m-sequence from phase phases[r] (default 0) (csrc/channel.hip: pn_kernel)."""
+    c = _mseq_bytes(m)
+    nrow, n = int(nrow), int(n)
+    if nrow < 0 or n < 0:
+        raise ValueError("pn_rows: negative size")
+    ph = np.zeros(nrow, dtype=np.int64) if phases is None else np.ascontiguousarray(phases, dtype=np.int64).reshape(-1)
+    if ph.size != nrow or np.any(ph < 0):
+        raise ValueError("pn_rows: one non-negative phase per row")
+    if nrow == 0 or n == 0:
+        return np.zeros((nrow, n), dtype=np.uint8)
+    cd, pd, yd = _ffi.device_bytes_of(c), _ffi.device_bytes_of(ph), _ffi.DeviceBytes(nrow * n)
+    try:
+        _ffi.pn_rows_dev(cd, c.size, yd, n, nrow, phases_d=pd)
+        return yd.read().reshape(nrow, n)
+    finally:
+        for d in (cd, pd, yd):
+            d.free()
+
+
+def pn_gen_host(n_bits, m=5):
+    """pn_gen in NumPy (no GPU)."""
+    return np.resize(m_seq(m), int(n_bits))
+
+
+def pn_gen(n_bits, m=5):
+    """n_bits values 0. / 1. (float64) of the m-sequence repeated, sigsys.py:1947-1980; past 2^16 values the period is tiled on the GPU."""
+    if int(n_bits) <= PN_HOST_MAX:
+        return pn_gen_host(n_bits, m)
+    return pn_rows(1, n_bits, m)[0].astype(np.float64)
+
+
+def random_bits_rows(nrow, n, seed=None):
+    """Beyond the reference (its encoders draw np.random.randint on the host): (nrow, n) uint8 bits 0 / 1 of the counter-based bit stream of
+    `seed`, row r = stream row r (csrc/channel.hip: randbits_kernel); _ffi.random_bits_host gives the same bits without a GPU."""
+    nrow, n = int(nrow), int(n)
+    if nrow < 0 or n < 0:
+        raise ValueError("random_bits_rows: negative size")
+    if nrow == 0 or n == 0:
+        return np.zeros((nrow, n), dtype=np.uint8)
+    seed = _ffi.new_seed() if seed is None else seed
+    yd = _ffi.DeviceBytes(nrow * n)
+    try:
+        _ffi.random_bits_rows_dev(yd, n, nrow, seed)
+        return yd.read().reshape(nrow, n)
+    finally:
+        yd.free()
