@@ -341,6 +341,30 @@ int skdsp_awgn_sigma_rows_dev(const void *x_dev, int64_t x_stride, int64_t n, in
 int skdsp_random_bits_rows_dev(uint8_t *y_dev, int64_t y_stride, int64_t n, int64_t nrow, uint64_t seed, int64_t first_index, int64_t first_row);
 int skdsp_pn_rows_dev(const uint8_t *period_dev, int q, const int64_t *phases_dev, uint8_t *y_dev, int64_t y_stride, int64_t n, int64_t nrow, int64_t first_index);
 
+/* OFDM modulation and demodulation over the rows of a frame set (csrc/ofdm.hip, csrc/ofdm_core.hpp): digitalcom.ofdm_tx / ofdm_rx /
+ * chan_est_equalize (digitalcom.py:1322-1547; mux_pilot_blocks is index arithmetic inside the transmitter).  complex64 or complex128 rows,
+ * computed in float64 and rounded once; strides in elements, pointers aligned to the element; not in place.  nc: a power of two in 64 ... 4096,
+ * nf even in 2 ... nc - 2 (carrier c in bin c + 1 for c < nf / 2, else bin nc - nf + c), 0 <= ncp <= nc (ignored unless cp), npb the pilot
+ * period: 0 none, >= 2 a pilot (all ones) in front of every npb - 1 data symbols.
+ *   ofdm_tx_rows:       nsym data symbols of nf carriers per row -> T (nc + ncp) samples, T = nsym (npb = 0) or nsym + nsym / (npb - 1) + 1; where
+ *                       npb - 1 divides nsym the last symbol is all zeros, as in the reference.
+ *   ofdm_rx_rows:       nsym received symbols per row (stride nc + ncp behind a prefix of ncp samples with cp, else stride nc) -> the nf carriers of
+ *                       its data symbols, (nsym - ceil(nsym / npb)) nf elements for npb > 0, else nsym nf.  hht: the known channel on the nf filled
+ *                       carriers, complex128 on the HOST, or null.  npb = -1: every symbol divided by hht.  npb > 0: symbols k with k % npb == 0
+ *                       are pilots and run H = z[0], H = alpha H + (1 - alpha) z[k]; data symbols are divided by hht if given (the reference), else
+ *                       by the estimate of the latest pilot in front of them; h[r] (nf complex128 per row, npb > 0 only) is the row's last estimate.
+ *   ofdm_equalize_rows: the same estimator and division on the rows of a caller's z, nsym symbols of nf carriers each (npb >= 2).
+ * nsym = 0 and nrow = 0 are valid. */
+int skdsp_ofdm_tx_rows(const void *x, int64_t nsym, int64_t nrow, int dtype, int nf, int nc, int npb, int cp, int ncp, void *y);
+int skdsp_ofdm_tx_rows_dev(const void *x_dev, int64_t x_stride, int64_t nsym, int64_t nrow, int dtype, int nf, int nc, int npb, int cp, int ncp, void *y_dev,
+                           int64_t y_stride);
+int skdsp_ofdm_rx_rows(const void *x, int64_t nsym, int64_t nrow, int dtype, int nf, int nc, int npb, int cp, int ncp, double alpha, const double *hht, void *z, void *h);
+int skdsp_ofdm_rx_rows_dev(const void *x_dev, int64_t x_stride, int64_t nsym, int64_t nrow, int dtype, int nf, int nc, int npb, int cp, int ncp, double alpha,
+                           const double *hht, void *z_dev, int64_t z_stride, void *h_dev);
+int skdsp_ofdm_equalize_rows(const void *z, int64_t nsym, int64_t nrow, int dtype, int nf, int npb, double alpha, const double *hht, void *out, void *h);
+int skdsp_ofdm_equalize_rows_dev(const void *z_dev, int64_t z_stride, int64_t nsym, int64_t nrow, int dtype, int nf, int npb, double alpha, const double *hht,
+                                 void *out_dev, int64_t out_stride, void *h_dev);
+
 /* Host-pointer entry points of a float32/complex64 handle deliver y as float64/complex128 (the
  * reference's result dtype, multirate_helper.py:108 etc.): widened on the device before the copy
  * back, so y must hold twice the bytes.  Device-pointer (_dev) entry points are not affected. */

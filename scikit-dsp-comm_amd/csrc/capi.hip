@@ -567,4 +567,90 @@ int skdsp_awgn_sigma_rows_dev(const void *x_dev, int64_t x_stride, int64_t n, in
     return awgn_sigma_launch(mode, ns, p, var_w, nrow, g_dev, sigma_dev, ctx().stream);
 }
 
+// ---------------------------------------------------------------- OFDM (ofdm.hip): ofdm_tx / ofdm_rx / chan_est_equalize over rows
+// the pilots, the estimates, the raw data rows and the channel table of a launch live in workspace 3 of the calling slot
+int skdsp_ofdm_tx_rows_dev(const void *x_dev, int64_t x_stride, int64_t nsym, int64_t nrow, int dtype, int nf, int nc, int npb, int cp, int ncp, void *y_dev,
+                           int64_t y_stride)
+{
+    int rc = ofdm_tx_check(nsym, nrow, dtype, nf, nc, npb, cp, ncp, x_stride, y_stride);   // (argument errors need no device)
+    if (rc || nrow == 0) return rc;
+    API_BEGIN;
+    return ofdm_tx_launch(x_dev, x_stride, nsym, nrow, dtype, nf, nc, npb, cp, ncp, y_dev, y_stride, ctx().stream);
+}
+
+int skdsp_ofdm_tx_rows(const void *x, int64_t nsym, int64_t nrow, int dtype, int nf, int nc, int npb, int cp, int ncp, void *y)
+{
+    const int64_t n_in = nsym * nf, n_out = npb == 1 ? 0 : (npb > 0 ? nsym + nsym / (npb - 1) + 1 : nsym) * (nc + (cp ? ncp : 0));
+    int rc = ofdm_tx_check(nsym, nrow, dtype, nf, nc, npb, cp, ncp, n_in, n_out);
+    if (rc || nrow == 0) return rc;
+    if (n_out == 0) return SKDSP_OK;
+    SK_CHECK(y && (x || n_in == 0), SKDSP_ERR_BADARG, "ofdm_tx: null pointer");
+    API_BEGIN;
+    const size_t esz = dtype_size(dtype);
+    void *x_dev = nullptr, *y_dev = nullptr;
+    if ((rc = stage_in(x, (size_t)n_in * (size_t)nrow * esz, &x_dev))) return rc;
+    if ((rc = ws_reserve(1, (size_t)n_out * (size_t)nrow * esz + 256, &y_dev))) return rc;
+    if ((rc = ofdm_tx_launch(x_dev, n_in, nsym, nrow, dtype, nf, nc, npb, cp, ncp, y_dev, n_out, ctx().stream))) return rc;
+    return stage_out(y, y_dev, (size_t)n_out * (size_t)nrow * esz);
+}
+
+int skdsp_ofdm_rx_rows_dev(const void *x_dev, int64_t x_stride, int64_t nsym, int64_t nrow, int dtype, int nf, int nc, int npb, int cp, int ncp, double alpha,
+                           const double *hht, void *z_dev, int64_t z_stride, void *h_dev)
+{
+    int rc = ofdm_rx_check(nsym, nrow, dtype, nf, nc, npb, cp, ncp, hht != nullptr, x_stride, z_stride);   // (argument errors need no device)
+    if (rc || nrow == 0 || nsym == 0) return rc;
+    API_BEGIN;
+    void *scratch = nullptr;
+    if ((rc = ws_reserve(3, ofdm_scratch_bytes(nsym, nrow, nf), &scratch))) return rc;
+    return ofdm_rx_launch(x_dev, x_stride, nsym, nrow, dtype, nf, nc, npb, cp, ncp, alpha, hht, scratch, z_dev, z_stride, h_dev, ctx().stream);
+}
+
+int skdsp_ofdm_rx_rows(const void *x, int64_t nsym, int64_t nrow, int dtype, int nf, int nc, int npb, int cp, int ncp, double alpha, const double *hht, void *z, void *h)
+{
+    const int64_t n_in = nsym * (cp ? nc + ncp : nc);
+    const int64_t n_out = (nsym - (npb > 0 ? (nsym + npb - 1) / npb : 0)) * nf;
+    int rc = ofdm_rx_check(nsym, nrow, dtype, nf, nc, npb, cp, ncp, hht != nullptr, n_in, n_out);
+    if (rc || nrow == 0 || nsym == 0) return rc;
+    SK_CHECK(x && (z || n_out == 0) && (h || npb <= 0), SKDSP_ERR_BADARG, "ofdm_rx: null pointer");
+    API_BEGIN;
+    const size_t esz = dtype_size(dtype), z_bytes = (size_t)n_out * (size_t)nrow * esz, h_off = round_up(z_bytes, 256), h_bytes = npb > 0 ? (size_t)nrow * nf * 16 : 0;
+    void *x_dev = nullptr, *out_dev = nullptr, *scratch = nullptr;
+    if ((rc = stage_in(x, (size_t)n_in * (size_t)nrow * esz, &x_dev))) return rc;
+    if ((rc = ws_reserve(1, h_off + h_bytes + 256, &out_dev))) return rc;
+    if ((rc = ws_reserve(3, ofdm_scratch_bytes(nsym, nrow, nf), &scratch))) return rc;
+    void *h_dev = (char *)out_dev + h_off;
+    if ((rc = ofdm_rx_launch(x_dev, n_in, nsym, nrow, dtype, nf, nc, npb, cp, ncp, alpha, hht, scratch, out_dev, n_out, h_dev, ctx().stream))) return rc;
+    if (h_bytes && (rc = stage_out(h, h_dev, h_bytes))) return rc;
+    return z_bytes ? stage_out(z, out_dev, z_bytes) : sync_checked();
+}
+
+int skdsp_ofdm_equalize_rows_dev(const void *z_dev, int64_t z_stride, int64_t nsym, int64_t nrow, int dtype, int nf, int npb, double alpha, const double *hht,
+                                 void *out_dev, int64_t out_stride, void *h_dev)
+{
+    int rc = ofdm_equalize_check(nsym, nrow, dtype, nf, npb, z_stride, out_stride);   // (argument errors need no device)
+    if (rc || nrow == 0 || nsym == 0) return rc;
+    API_BEGIN;
+    void *scratch = nullptr;
+    if ((rc = ws_reserve(3, ofdm_scratch_bytes(nsym, nrow, nf), &scratch))) return rc;
+    return ofdm_equalize_launch(z_dev, z_stride, nsym, nrow, dtype, nf, npb, alpha, hht, scratch, out_dev, out_stride, h_dev, ctx().stream);
+}
+
+int skdsp_ofdm_equalize_rows(const void *z, int64_t nsym, int64_t nrow, int dtype, int nf, int npb, double alpha, const double *hht, void *out, void *h)
+{
+    const int64_t n_in = nsym * nf, n_out = npb < 2 ? 0 : (nsym - (nsym + npb - 1) / npb) * nf;
+    int rc = ofdm_equalize_check(nsym, nrow, dtype, nf, npb, n_in, n_out);
+    if (rc || nrow == 0 || nsym == 0) return rc;
+    SK_CHECK(z && h && (out || n_out == 0), SKDSP_ERR_BADARG, "ofdm_equalize: null pointer");
+    API_BEGIN;
+    const size_t esz = dtype_size(dtype), o_bytes = (size_t)n_out * (size_t)nrow * esz, h_off = round_up(o_bytes, 256), h_bytes = (size_t)nrow * nf * 16;
+    void *z_dev = nullptr, *out_dev = nullptr, *scratch = nullptr;
+    if ((rc = stage_in(z, (size_t)n_in * (size_t)nrow * esz, &z_dev))) return rc;
+    if ((rc = ws_reserve(1, h_off + h_bytes + 256, &out_dev))) return rc;
+    if ((rc = ws_reserve(3, ofdm_scratch_bytes(nsym, nrow, nf), &scratch))) return rc;
+    void *h_dev = (char *)out_dev + h_off;
+    if ((rc = ofdm_equalize_launch(z_dev, n_in, nsym, nrow, dtype, nf, npb, alpha, hht, scratch, out_dev, n_out, h_dev, ctx().stream))) return rc;
+    if ((rc = stage_out(h, h_dev, h_bytes))) return rc;
+    return o_bytes ? stage_out(out, out_dev, o_bytes) : SKDSP_OK;
+}
+
 }  // extern "C"

@@ -382,4 +382,18 @@ int pn_check(int Q, int64_t n, int64_t nrow, int64_t y_stride, int64_t first);  
 int pn_launch(const uint8_t *period_dev, int Q, const int64_t *phases_dev, uint8_t *y_dev, int64_t y_stride, int64_t n, int64_t nrow, int64_t first, hipStream_t s);
 int awgn_sigma_launch(int mode, double ns, double p, double var_w, int64_t nrow, double *g_dev, double *sigma_dev, hipStream_t s);
 
+// ---- OFDM (ofdm.hip): digitalcom.ofdm_tx / ofdm_rx / chan_est_equalize over rows; the argument rules, the plans and the per-thread phases are ofdm_core.hpp ----
+// complex64 / complex128 rows, strides in elements.  nsym: the data symbols of a row (tx), its received symbols (rx), the rows of its z (equalize).
+// hht_host: the known channel on the nf filled carriers (complex128 on the HOST) or null; scratch_dev: ofdm_scratch_bytes, 256-byte aligned.
+int ofdm_tx_check(int64_t nsym, int64_t nrow, int dtype, int nf, int nc, int npb, int cp, int ncp, int64_t x_stride, int64_t y_stride);   // host-only
+int ofdm_tx_launch(const void *x_dev, int64_t x_stride, int64_t nsym, int64_t nrow, int dtype, int nf, int nc, int npb, int cp, int ncp, void *y_dev, int64_t y_stride,
+                   hipStream_t s);
+int ofdm_rx_check(int64_t nsym, int64_t nrow, int dtype, int nf, int nc, int npb, int cp, int ncp, int has_table, int64_t x_stride, int64_t z_stride);   // host-only
+size_t ofdm_scratch_bytes(int64_t nsym, int64_t nrow, int nf);                                                                                          // host-only
+int ofdm_rx_launch(const void *x_dev, int64_t x_stride, int64_t nsym, int64_t nrow, int dtype, int nf, int nc, int npb, int cp, int ncp, double alpha,
+                   const double *hht_host, void *scratch_dev, void *z_dev, int64_t z_stride, void *h_dev, hipStream_t s);
+int ofdm_equalize_check(int64_t nsym, int64_t nrow, int dtype, int nf, int npb, int64_t z_stride, int64_t out_stride);   // host-only
+int ofdm_equalize_launch(const void *z_dev, int64_t z_stride, int64_t nsym, int64_t nrow, int dtype, int nf, int npb, double alpha, const double *hht_host,
+                         void *scratch_dev, void *out_dev, int64_t out_stride, void *h_dev, hipStream_t s);
+
 }  // namespace skdsp

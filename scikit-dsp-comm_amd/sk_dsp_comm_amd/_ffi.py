@@ -43,6 +43,7 @@ SYMBOLS = [
     "skdsp_gray_map_rows", "skdsp_gray_map_rows_dev", "skdsp_qam_scale_rows", "skdsp_qam_scale_rows_dev", "skdsp_qam_demap_rows", "skdsp_qam_demap_rows_dev",
     "skdsp_mpsk_demap_rows", "skdsp_mpsk_demap_rows_dev",
     "skdsp_awgn_rows_dev", "skdsp_awgn_bits_rows_dev", "skdsp_awgn_sigma_rows_dev", "skdsp_random_bits_rows_dev", "skdsp_pn_rows_dev",
+    "skdsp_ofdm_tx_rows", "skdsp_ofdm_tx_rows_dev", "skdsp_ofdm_rx_rows", "skdsp_ofdm_rx_rows_dev", "skdsp_ofdm_equalize_rows", "skdsp_ofdm_equalize_rows_dev",
     "skdsp_dist_unique_id", "skdsp_dist_init", "skdsp_dist_shutdown", "skdsp_dist_comm_count", "skdsp_dist_barrier",
     "skdsp_dist_allreduce_max", "skdsp_dist_allreduce_sum", "skdsp_dist_sendrecv", "skdsp_dist_allgather", "skdsp_dist_halo_exchange", "skdsp_fir_filter_shard_dev",
 ]
@@ -181,6 +182,14 @@ def load():
             L.skdsp_awgn_sigma_rows_dev.argtypes = [vp, i64, i64, i64, ci, ci, dbl, dbl, dbl, vp, vp]
             L.skdsp_random_bits_rows_dev.argtypes = [vp, i64, i64, i64, u64, i64, i64]
             L.skdsp_pn_rows_dev.argtypes = [vp, ci, vp, vp, i64, i64, i64, i64]
+        if hasattr(L, "skdsp_ofdm_tx_rows_dev"):
+            dbl = ctypes.c_double
+            L.skdsp_ofdm_tx_rows.argtypes = [vp, i64, i64, ci, ci, ci, ci, ci, ci, vp]
+            L.skdsp_ofdm_tx_rows_dev.argtypes = [vp, i64, i64, i64, ci, ci, ci, ci, ci, ci, vp, i64]
+            L.skdsp_ofdm_rx_rows.argtypes = [vp, i64, i64, ci, ci, ci, ci, ci, ci, dbl, vp, vp, vp]
+            L.skdsp_ofdm_rx_rows_dev.argtypes = [vp, i64, i64, i64, ci, ci, ci, ci, ci, ci, dbl, vp, vp, i64, vp]
+            L.skdsp_ofdm_equalize_rows.argtypes = [vp, i64, i64, ci, ci, ci, dbl, vp, vp, vp]
+            L.skdsp_ofdm_equalize_rows_dev.argtypes = [vp, i64, i64, i64, ci, ci, ci, dbl, vp, vp, i64, vp]
         L.skdsp_dist_unique_id.argtypes = [vp]
         L.skdsp_dist_init.argtypes = [ci, ci, vp]
         L.skdsp_dist_comm_count.argtypes = [ctypes.POINTER(ci)]
@@ -1230,6 +1239,88 @@ def random_bits_rows_dev(yd, n, nrow, seed, y_stride=None, first_index=0, first_
 def pn_rows_dev(period_d, q, yd, n, nrow, phases_d=None, y_stride=None, first_index=0):
     """yd[r, i] = period[(phases[r] + first_index + i) mod q] (pn_kernel); period_d: q bytes, phases_d: nrow int64 or None, on the device"""
     check(load().skdsp_pn_rows_dev(_dp(period_d), int(q), _dp(phases_d), _dp(yd), int(n if y_stride is None else y_stride), int(n), int(nrow), int(first_index)))
+
+
+# --------------------------------------------------------------------------
+# OFDM (csrc/ofdm.hip): ofdm_tx / ofdm_rx / chan_est_equalize over the rows of a frame set
+# --------------------------------------------------------------------------
+def ofdm_tx_symbols(nsym, npb):
+    """symbols a row of nsym data symbols leaves the transmitter with"""
+    return nsym + nsym // (npb - 1) + 1 if npb > 0 else nsym
+
+
+def ofdm_rx_data_symbols(nsym, npb):
+    """data symbols among nsym received ones"""
+    return nsym - (nsym + npb - 1) // npb if npb > 0 else nsym
+
+
+def _hht_ptr(hht, nf):
+    """the known channel on the filled carriers as the library takes it: nf complex128 on the host (the array is returned to keep it alive)"""
+    if hht is None:
+        return None, ctypes.c_void_p(0)
+    hht = np.ascontiguousarray(hht, dtype=np.complex128)
+    if hht.shape != (nf,):
+        raise ValueError("ofdm: the channel table holds one value per filled carrier")
+    return hht, _ptr(hht)
+
+
+def ofdm_tx_rows_dev(xd, yd, nsym, nrow, nf, nc, npb=0, cp=False, ncp=0, x_stride=None, y_stride=None, dtype=None):
+    """yd[r] = ofdm_tx of the nsym nf symbols of xd[r] (csrc/ofdm.hip: ofdm_tx_kernel).  xd, yd: DeviceArrays (or addresses with dtype) of
+    complex64 / complex128; strides in elements (default: the rows back to back)."""
+    n_out = ofdm_tx_symbols(nsym, npb) * (nc + (ncp if cp else 0))
+    check(load().skdsp_ofdm_tx_rows_dev(_dp(xd), int(nsym * nf if x_stride is None else x_stride), int(nsym), int(nrow), code_of(xd.dtype if dtype is None else dtype),
+                                        int(nf), int(nc), int(npb), int(bool(cp)), int(ncp), _dp(yd), int(n_out if y_stride is None else y_stride)))
+
+
+def ofdm_rx_rows_dev(xd, zd, nsym, nrow, nf, nc, npb=0, cp=False, ncp=0, alpha=0.95, hht=None, hd=None, x_stride=None, z_stride=None, dtype=None):
+    """zd[r] = the equalised carriers of the nsym received symbols of xd[r] (ofdm_rx_kernel, then the estimator kernels for npb > 0); hht: the
+    known channel on the nf filled carriers (a host array) or None; hd: nrow nf complex128 for the rows' last estimates (npb > 0)."""
+    keep, hp = _hht_ptr(hht, nf)
+    n_in, n_out = nsym * (nc + ncp if cp else nc), ofdm_rx_data_symbols(nsym, npb) * nf
+    check(load().skdsp_ofdm_rx_rows_dev(_dp(xd), int(n_in if x_stride is None else x_stride), int(nsym), int(nrow), code_of(xd.dtype if dtype is None else dtype), int(nf),
+                                        int(nc), int(npb), int(bool(cp)), int(ncp), float(alpha), hp, _dp(zd), int(n_out if z_stride is None else z_stride), _dp(hd)))
+    del keep
+
+
+def ofdm_equalize_rows_dev(zd, od, nsym, nrow, nf, npb, alpha, hd, hht=None, z_stride=None, out_stride=None, dtype=None):
+    """chan_est_equalize on the rows of zd, nsym symbols of nf carriers each (ofdm_chanest_kernel, ofdm_equalize_kernel): the data rows to od,
+    the rows' last estimates to hd (nrow nf complex128)"""
+    keep, hp = _hht_ptr(hht, nf)
+    check(load().skdsp_ofdm_equalize_rows_dev(_dp(zd), int(nsym * nf if z_stride is None else z_stride), int(nsym), int(nrow), code_of(zd.dtype if dtype is None else dtype),
+                                              int(nf), int(npb), float(alpha), hp, _dp(od), int(ofdm_rx_data_symbols(nsym, npb) * nf if out_stride is None else out_stride),
+                                              _dp(hd)))
+    del keep
+
+
+def ofdm_tx_rows(x2d, nf, nc, npb, cp, ncp):
+    """host arrays through skdsp_ofdm_tx_rows: x2d (nrow, nsym nf) complex64 / complex128, contiguous"""
+    nrow, nsym = x2d.shape[0], x2d.shape[1] // nf
+    y = np.empty((nrow, ofdm_tx_symbols(nsym, npb) * (nc + (ncp if cp else 0))), dtype=x2d.dtype)
+    check(load().skdsp_ofdm_tx_rows(_ptr(x2d), nsym, nrow, code_of(x2d.dtype), int(nf), int(nc), int(npb), int(bool(cp)), int(ncp), _ptr(y)))
+    return y
+
+
+def ofdm_rx_rows(x2d, nsym, nf, nc, npb, cp, ncp, alpha, hht):
+    """host arrays through skdsp_ofdm_rx_rows: x2d (nrow, nsym symbols) -> z (nrow, ndata nf) of x2d's dtype, h (nrow, nf) complex128 (npb > 0) or None"""
+    nrow = x2d.shape[0]
+    z = np.empty((nrow, ofdm_rx_data_symbols(nsym, npb) * nf), dtype=x2d.dtype)
+    h = np.empty((nrow, nf), dtype=np.complex128) if npb > 0 else None
+    keep, hp = _hht_ptr(hht, nf)
+    check(load().skdsp_ofdm_rx_rows(_ptr(x2d), int(nsym), nrow, code_of(x2d.dtype), int(nf), int(nc), int(npb), int(bool(cp)), int(ncp), float(alpha), hp, _ptr(z),
+                                    _ptr(h) if h is not None else ctypes.c_void_p(0)))
+    del keep
+    return z, h
+
+
+def ofdm_equalize_rows(z3d, npb, alpha, hht):
+    """host arrays through skdsp_ofdm_equalize_rows: z3d (nrow, nsym, nf) -> (nrow, ndata, nf) of z3d's dtype, h (nrow, nf) complex128"""
+    nrow, nsym, nf = z3d.shape
+    out = np.empty((nrow, ofdm_rx_data_symbols(nsym, npb), nf), dtype=z3d.dtype)
+    h = np.empty((nrow, nf), dtype=np.complex128)
+    keep, hp = _hht_ptr(hht, nf)
+    check(load().skdsp_ofdm_equalize_rows(_ptr(z3d), nsym, nrow, code_of(z3d.dtype), nf, int(npb), float(alpha), hp, _ptr(out), _ptr(h)))
+    del keep
+    return out, h
 
 
 def device_bytes_of(a):

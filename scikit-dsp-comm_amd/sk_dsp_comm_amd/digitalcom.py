@@ -598,3 +598,219 @@ def awgn_channel_host(x_bits, eb_n0_dB, seed=None):
         return np.zeros(0)
     seed = _ffi.new_seed() if seed is None else seed
     return _decisions_as_float(_ffi.awgn_bits_rows_host(bits[None, :], _channel_sigma(eb_n0_dB), seed)[0])
+
+
+# ------------------------------------------------------------------------------------------------ OFDM (digitalcom.py:1284-1547)
+# What the reference computes, its quirks included, and the deliberate differences: tests/golden/g24_conventions.json, DESIGN.md 4.19.
+def _ofdm_check(name, nf, nc, npb, ncp, rx=False, ht=None):
+    nf, nc, npb, ncp = int(nf), int(nc), int(npb), int(ncp)
+    if nf < 2 or nf % 2 or nf > nc - 2:
+        raise ValueError("%s: nf must be even and 2 <= nf <= nc - 2 (nf = %d, nc = %d)" % (name, nf, nc))
+    if npb == 1:
+        raise ValueError("%s: npb = 1 leaves no data symbols (the reference divides by zero)" % name)
+    if npb < (-1 if rx else 0):
+        raise ValueError("%s: npb must be %s0 or at least 2 (npb = %d)" % (name, "-1, " if rx else "", npb))
+    if ncp < 0 or ncp > nc:
+        raise ValueError("%s: need 0 <= ncp <= nc (ncp = %d, nc = %d)" % (name, ncp, nc))
+    if rx and npb == -1 and ht is None:
+        raise ValueError("%s: npb = -1 equalises with the known channel: pass ht" % name)
+    return nf, nc, npb, ncp
+
+
+def _ofdm_on_gpu(nc):
+    return 64 <= nc <= 4096 and nc & (nc - 1) == 0
+
+
+def _ofdm_input(x, name, ndim):
+    """complex64 / float32 stay single precision (computed in float64, rounded once); everything else is complex128"""
+    x = np.asarray(x)
+    if x.ndim != ndim:
+        raise ValueError("%s: a %d-D array" % (name, ndim))
+    single = x.dtype in (np.dtype(np.complex64), np.dtype(np.float32))
+    return x.astype(np.complex64 if single else np.complex128, copy=False)
+
+
+def _ofdm_hht(ht, nf, nc, name):
+    """the channel impulse response on the filled carriers: fft(ht, nc) picked by the carrier map"""
+    if ht is None:
+        return None
+    ht = np.asarray(ht)
+    if ht.ndim != 1 or ht.size == 0 or ht.size > nc:
+        raise ValueError("%s: ht must hold 1 ... nc = %d taps" % (name, nc))
+    Ht = np.fft.fft(ht.astype(np.complex128), nc)
+    return np.hstack((Ht[1:nf // 2 + 1], Ht[nc - nf // 2:]))
+
+
+def mux_pilot_blocks(iq_data, npb):
+    """IQ_datap = mux_pilot_blocks(iq_data, npb), digitalcom.py:1284-1319, vectorised on the host: a row of ones in front of every npb - 1
+    rows of the (N, nf) data.  T = N + N // (npb - 1) + 1 rows, complex128; where npb - 1 divides N the last row is all zeros, not a pilot,
+    as in the reference (it assigns into an empty slice there).  npb < 2 raises ValueError (the reference divides by zero at npb = 1)."""
+    d = np.asarray(iq_data)
+    if d.ndim != 2:
+        raise ValueError("mux_pilot_blocks: a 2-D array, one OFDM symbol per row")
+    npb = int(npb)
+    if npb < 2:
+        raise ValueError("mux_pilot_blocks: npb must be at least 2")
+    N, nf = d.shape
+    out = np.zeros((N + N // (npb - 1) + 1, nf), dtype=np.complex128)
+    j = np.arange(out.shape[0])
+    pilot = j % npb == 0
+    out[pilot] = 1.0
+    out[~pilot] = d[j[~pilot] - j[~pilot] // npb - 1]
+    if N % (npb - 1) == 0:
+        out[-1] = 0.0
+    return out
+
+
+def ofdm_tx_host(iq_data, nf, nc, npb=0, cp=False, ncp=0):
+    """ofdm_tx in NumPy (no GPU), float64: the yardstick of the kernel and the path of every nc the kernels do not take."""
+    nf, nc, npb, ncp = _ofdm_check("ofdm_tx", nf, nc, npb, ncp)
+    x = _ofdm_input(iq_data, "ofdm_tx", 1)
+    N = x.size // nf
+    s2p = x[:N * nf].reshape(N, nf).astype(np.complex128)
+    if npb > 0:
+        s2p = mux_pilot_blocks(s2p, npb)
+    T, L = s2p.shape[0], nc + (ncp if cp else 0)
+    if T == 0:
+        return np.zeros(0, dtype=x.dtype)
+    buff = np.zeros((T, nc), dtype=np.complex128)
+    buff[:, 1:nf // 2 + 1] = s2p[:, :nf // 2]
+    buff[:, nc - nf // 2:] = s2p[:, nf // 2:]
+    t = np.fft.ifft(buff, axis=1)
+    if cp:
+        t = np.hstack((t[:, nc - ncp:], t))
+    return t.reshape(T * L).astype(x.dtype)
+
+
+def chan_est_equalize_host(z, npbp, alpha, ht=None):
+    """chan_est_equalize in NumPy (no GPU), float64: rows k % npbp == 0 of z are pilots and run H = z[0], H = alpha H + (1 - alpha) z[k];
+    the other rows are divided by ht where it is given (the reference), else by the estimate of the latest pilot in front of them."""
+    z = _ofdm_input(z, "chan_est_equalize", 2)
+    npbp = int(npbp)
+    if npbp < 2:
+        raise ValueError("chan_est_equalize: npbp must be at least 2")
+    N, nf = z.shape
+    if ht is not None:
+        ht = np.asarray(ht, dtype=np.complex128)
+        if ht.shape != (nf,):
+            raise ValueError("chan_est_equalize: ht holds the channel on the nf carriers")
+    if N == 0:
+        return np.zeros((0, nf), dtype=z.dtype), np.full(nf, np.nan + 0j)
+    pilots = z[::npbp].astype(np.complex128)
+    est = np.empty_like(pilots)
+    est[0] = pilots[0]
+    for p in range(1, pilots.shape[0]):
+        est[p] = alpha * est[p - 1] + (1 - alpha) * pilots[p]
+    k = np.arange(N)
+    data = k[k % npbp != 0]
+    div = ht[None, :] if ht is not None else est[data // npbp]
+    with np.errstate(all="ignore"):
+        zz = z[data].astype(np.complex128) / div
+    return zz.astype(z.dtype), est[-1].copy()
+
+
+def ofdm_rx_host(x, nf, nc, npb=0, cp=False, ncp=0, alpha=0.95, ht=None):
+    """ofdm_rx in NumPy (no GPU), float64: the yardstick of the kernels and the path of every nc they do not take."""
+    nf, nc, npb, ncp = _ofdm_check("ofdm_rx", nf, nc, npb, ncp, True, ht)
+    x = _ofdm_input(x, "ofdm_rx", 1)
+    hht = _ofdm_hht(ht, nf, nc, "ofdm_rx")
+    nsym = x.size // (nc + ncp)
+    stride, off = (nc + ncp, ncp) if cp else (nc, 0)
+    if nsym == 0:
+        z = np.zeros((0, nf), dtype=np.complex128)
+    else:
+        Y = np.fft.fft(x[:nsym * stride].reshape(nsym, stride)[:, off:].astype(np.complex128), axis=1)
+        z = np.hstack((Y[:, 1:nf // 2 + 1], Y[:, nc - nf // 2:]))
+    if npb > 0:
+        z, H = chan_est_equalize_host(z, npb, alpha, hht)
+    elif npb == -1:
+        H = hht
+        with np.errstate(all="ignore"):
+            z = z / H[None, :]
+    else:
+        H = np.ones(nf)
+    return z.reshape(-1).astype(x.dtype), H
+
+
+def ofdm_tx_rows(iq2d, nf, nc, npb=0, cp=False, ncp=0):
+    """Beyond the reference: ofdm_tx of every row of a frame set in one launch (csrc/ofdm.hip: ofdm_tx_kernel); row r equals
+    ofdm_tx(iq2d[r], ...).  An nc that is not a power of two in 64 ... 4096 runs ofdm_tx_host row by row."""
+    nf, nc, npb, ncp = _ofdm_check("ofdm_tx", nf, nc, npb, ncp)
+    x = _ofdm_input(iq2d, "ofdm_tx_rows", 2)
+    nrow, N = x.shape[0], x.shape[1] // nf
+    n_out = _ffi.ofdm_tx_symbols(N, npb) * (nc + (ncp if cp else 0))
+    if nrow == 0 or n_out == 0:
+        return np.zeros((nrow, n_out), dtype=x.dtype)
+    if not _ofdm_on_gpu(nc):
+        log.info("ofdm_tx: nc = %d is not a power of two in 64 ... 4096: host float64 path", nc)
+        return np.stack([ofdm_tx_host(r, nf, nc, npb, cp, ncp) for r in x])
+    return _ffi.ofdm_tx_rows(np.ascontiguousarray(x[:, :N * nf]), nf, nc, npb, cp, ncp)
+
+
+def ofdm_tx(iq_data, nf, nc, npb=0, cp=False, ncp=0):
+    """x_out = ofdm_tx(iq_data, nf, nc, npb=0, cp=False, ncp=0), digitalcom.py:1322-1386, on the GPU: the input cut to a multiple of nf,
+    pilots multiplexed in for npb > 0 (mux_pilot_blocks, its trailing zero row included), carrier c in bin c + 1 (c < nf / 2) or
+    nc - nf + c, one inverse transform per symbol scaled 1 / nc, and with cp=True the last ncp samples in front of each symbol.
+
+    Deliberate differences (tests/golden/g24_conventions.json): nothing is printed; complex64 / float32 input gives complex64 (computed in
+    float64, rounded once), everything else complex128; ValueError for an odd nf, nf > nc - 2, npb = 1, npb < 0, ncp < 0 or ncp > nc; an
+    input shorter than a symbol gives what the reference's arithmetic gives (empty without pilots)."""
+    x = _ofdm_input(iq_data, "ofdm_tx", 1)
+    return ofdm_tx_rows(x[None, :], nf, nc, npb, cp, ncp)[0]
+
+
+def _rx_h_rows(npb, nrow, nf, hht, h):
+    if npb > 0:
+        return h
+    return np.tile(hht, (nrow, 1)) if npb == -1 else np.ones((nrow, nf))
+
+
+def ofdm_rx_rows(x2d, nf, nc, npb=0, cp=False, ncp=0, alpha=0.95, ht=None):
+    """Beyond the reference: (z2d, H2d) = ofdm_rx of every row of a frame set (csrc/ofdm.hip: ofdm_rx_kernel and, for npb > 0, the estimator
+    kernels); row r equals ofdm_rx(x2d[r], ...).  An nc that is not a power of two in 64 ... 4096 runs ofdm_rx_host row by row."""
+    nf, nc, npb, ncp = _ofdm_check("ofdm_rx", nf, nc, npb, ncp, True, ht)
+    x = _ofdm_input(x2d, "ofdm_rx_rows", 2)
+    hht = _ofdm_hht(ht, nf, nc, "ofdm_rx")
+    nrow, nsym = x.shape[0], x.shape[1] // (nc + ncp)
+    n_out = _ffi.ofdm_rx_data_symbols(nsym, npb) * nf
+    if nrow == 0 or nsym == 0:
+        return np.zeros((nrow, n_out), dtype=x.dtype), _rx_h_rows(npb, nrow, nf, hht, np.full((nrow, nf), np.nan + 0j))
+    if not _ofdm_on_gpu(nc):
+        log.info("ofdm_rx: nc = %d is not a power of two in 64 ... 4096: host float64 path", nc)
+        rows = [ofdm_rx_host(r, nf, nc, npb, cp, ncp, alpha, ht) for r in x]
+        return np.stack([r[0] for r in rows]), np.stack([r[1] for r in rows])
+    n_in = nsym * (nc + ncp if cp else nc)
+    z, h = _ffi.ofdm_rx_rows(np.ascontiguousarray(x[:, :n_in]), nsym, nf, nc, npb, cp, ncp, alpha, hht)
+    return z, _rx_h_rows(npb, nrow, nf, hht, h)
+
+
+def ofdm_rx(x, nf, nc, npb=0, cp=False, ncp=0, alpha=0.95, ht=None):
+    """z_out, H = ofdm_rx(x, nf, nc, npb=0, cp=False, ncp=0, alpha=0.95, ht=None), digitalcom.py:1459-1547, on the GPU.  As the reference
+    computes it: len(x) // (nc + ncp) symbols also with cp=False (their stride is then nc); npb = 0: no equalisation, H = ones(nf);
+    npb = -1: every symbol divided by fft(ht, nc) on the filled carriers, which is H; npb > 0 with ht: symbols k % npb == 0 are pilots and
+    run the recursive estimate, the data symbols are divided by the channel of ht (not by the estimate), H is the last estimate.
+
+    Deliberate differences (tests/golden/g24_conventions.json): npb > 0 with ht=None runs the documented intent -- data symbols divided by
+    the estimate of the latest pilot in front of them -- where the reference raises; nothing is plotted; complex64 / float32 input gives
+    complex64 z; ValueError for the argument errors of ofdm_tx, npb < -1, npb = -1 without ht and len(ht) > nc; an input shorter than a
+    symbol gives an empty z (H as above; all nan where no pilot was seen)."""
+    xin = _ofdm_input(x, "ofdm_rx", 1)
+    z, H = ofdm_rx_rows(xin[None, :], nf, nc, npb, cp, ncp, alpha, ht)
+    return z[0], H[0]
+
+
+def chan_est_equalize(z, npbp, alpha, ht=None):
+    """zz_out, H = chan_est_equalize(z, npbp, alpha, ht=None), digitalcom.py:1389-1456, on the GPU (csrc/ofdm.hip: ofdm_chanest_kernel,
+    ofdm_equalize_kernel): the pilot rows k % npbp == 0 of the (N, nf) array z run H = z[0], H = alpha H + (1 - alpha) z[k] and are removed;
+    the data rows are divided by ht (the channel on the nf carriers) where it is given, as in the reference, else by the estimate of the
+    latest pilot in front of them (the reference's dead branch; it raises there).  H is the last estimate.  Nothing is plotted."""
+    zin = _ofdm_input(z, "chan_est_equalize", 2)
+    N, nf = zin.shape
+    if N == 0 or nf > 4096 or nf == 0:
+        return chan_est_equalize_host(zin, npbp, alpha, ht)
+    if int(npbp) < 2:
+        raise ValueError("chan_est_equalize: npbp must be at least 2")
+    if ht is not None and np.shape(ht) != (nf,):
+        raise ValueError("chan_est_equalize: ht holds the channel on the nf carriers")
+    out, h = _ffi.ofdm_equalize_rows(np.ascontiguousarray(zin)[None], int(npbp), alpha, ht)
+    return out[0], h[0]
