@@ -365,6 +365,30 @@ int skdsp_ofdm_equalize_rows(const void *z, int64_t nsym, int64_t nrow, int dtyp
 int skdsp_ofdm_equalize_rows_dev(const void *z_dev, int64_t z_stride, int64_t nsym, int64_t nrow, int dtype, int nf, int npb, double alpha, const double *hht,
                                  void *out_dev, int64_t out_stride, void *h_dev);
 
+/* Symbol-error tools of the classical BER loops (csrc/symerr.hip, csrc/symerr_core.hpp): digitalcom.xcorr (digitalcom.py:1163-1179), qam_sep
+ * (digitalcom.py:495-582), qpsk_bep (:723-790) and bpsk_bep (:793-846).  Streams are float32 / complex64 / float64 / complex128 (a real stream has
+ * imaginary part 0), widened at the load; pointers aligned to the element.
+ *   lag_corr:        R[i] = sum_{n < K} a[(n + l) mod K] conj(b[n]), l = first_lag + i, K = 2 floor(len / 2), over the lags the reference keeps:
+ *                    first_lag = -min(n_lags, K / 2), n_out = min(2 n_lags + 1, K) (skdsp_lag_corr_len).  r: n_out complex128, e: (sum |a|^2, sum |b|^2);
+ *                    in the _dev form both are device pointers, 16-byte aligned.  Sums are float64 in a fixed order: integer-valued streams give exact
+ *                    integers, two runs the same bits.  quant_levels = M in {2, 4, 8, 16} passes each component of a through qam_sep's quantiser
+ *                    2 clip(rint((M - 1)(v + 1) / 2), 0, M - 1) - (M - 1) at the load; 0: none.  lags (host form): n_out int64, may be null.
+ *   sym_count_rows:  per row, over n symbols: tx symbol i = tx[r tx_stride + t0 + i], rx symbol i = x[r x_stride + start + (r0 + i) step], rx rotated by
+ *                    (1j)^kphase (mode 2: (-1)^kphase).  mode 0 (QAM, levels = M as above): rx quantised, then rotated; counts[4 r] = symbols whose
+ *                    two Gaussian integers differ.  mode 1 (QPSK): with tI = int16((re tx + 1) / 2), rI likewise of rx, tQ / rQ of the imaginary parts,
+ *                    counts[4 r ...] = sum(tI ^ rI), sum(tQ ^ rQ), sum((tI ^ rI) | (tQ ^ rQ)) -- the reference's integers, also on soft values.
+ *                    mode 2 (BPSK): the real parts only, counts[4 r] = sum(tI ^ rI).  counts[4 r + 3] = the symbols left out because a value is not
+ *                    finite, tx is not integer-valued (mode 0) or |(v + 1) / 2| >= 32768 (modes 1, 2): a caller treats a non-zero count as an error.
+ *                    Strides in elements; exact and identical from run to run.
+ * len = 0, n = 0 and nrow = 0 are valid and launch nothing. */
+int skdsp_lag_corr_len(int64_t len, int64_t n_lags, int64_t *n_out, int64_t *first_lag);
+int skdsp_lag_corr(const void *a, int a_dtype, const void *b, int b_dtype, int64_t len, int64_t n_lags, int quant_levels, int64_t *lags, void *r, double *e);
+int skdsp_lag_corr_dev(const void *a_dev, int a_dtype, const void *b_dev, int b_dtype, int64_t len, int64_t n_lags, int quant_levels, void *r_dev, double *e_dev);
+int skdsp_sym_count_rows(const void *tx, int tx_dtype, int64_t tx_stride, int64_t t0, const void *x, int x_dtype, int64_t x_stride, int64_t start, int64_t step,
+                         int64_t r0, int64_t n, int64_t nrow, int mode, int levels, int kphase, int64_t *counts);
+int skdsp_sym_count_rows_dev(const void *tx_dev, int tx_dtype, int64_t tx_stride, int64_t t0, const void *x_dev, int x_dtype, int64_t x_stride, int64_t start,
+                             int64_t step, int64_t r0, int64_t n, int64_t nrow, int mode, int levels, int kphase, int64_t *counts_dev);
+
 /* Host-pointer entry points of a float32/complex64 handle deliver y as float64/complex128 (the
  * reference's result dtype, multirate_helper.py:108 etc.): widened on the device before the copy
  * back, so y must hold twice the bytes.  Device-pointer (_dev) entry points are not affected. */

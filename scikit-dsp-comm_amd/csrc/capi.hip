@@ -653,4 +653,85 @@ int skdsp_ofdm_equalize_rows(const void *z, int64_t nsym, int64_t nrow, int dtyp
     return o_bytes ? stage_out(out, out_dev, o_bytes) : SKDSP_OK;
 }
 
+// ---------------------------------------------------------------- symbol-error tools (symerr.hip): xcorr / qam_sep / qpsk_bep / bpsk_bep
+int skdsp_lag_corr_len(int64_t len, int64_t n_lags, int64_t *n_out, int64_t *first_lag)
+{
+    SK_CHECK(n_out && first_lag, SKDSP_ERR_BADARG, "lag_corr_len: null pointer");
+    return lagcorr_check(len, n_lags, 0, 0, 0, n_out, first_lag);
+}
+
+// the partials of a launch live in workspace 3 of the calling slot
+int skdsp_lag_corr_dev(const void *a_dev, int a_dtype, const void *b_dev, int b_dtype, int64_t len, int64_t n_lags, int quant_levels, void *r_dev, double *e_dev)
+{
+    int64_t nl = 0;
+    int rc = lagcorr_check(len, n_lags, a_dtype, b_dtype, quant_levels, &nl, nullptr);   // (argument errors need no device)
+    if (rc || nl == 0) return rc;
+    SK_CHECK(a_dev && b_dev && r_dev && e_dev, SKDSP_ERR_BADARG, "lag_corr: null pointer");
+    API_BEGIN;
+    void *scratch = nullptr;
+    if ((rc = ws_reserve(3, lagcorr_scratch_bytes(len, n_lags), &scratch))) return rc;
+    return lagcorr_launch(a_dev, a_dtype, b_dev, b_dtype, len, n_lags, quant_levels, scratch, r_dev, e_dev, ctx().stream);
+}
+
+// host form: the first K elements of both streams are copied
+int skdsp_lag_corr(const void *a, int a_dtype, const void *b, int b_dtype, int64_t len, int64_t n_lags, int quant_levels, int64_t *lags, void *r, double *e)
+{
+    int64_t nl = 0, l0 = 0;
+    int rc = lagcorr_check(len, n_lags, a_dtype, b_dtype, quant_levels, &nl, &l0);
+    if (rc) return rc;
+    if (lags)
+        for (int64_t i = 0; i < nl; ++i) lags[i] = l0 + i;
+    if (nl == 0) return SKDSP_OK;
+    SK_CHECK(a && b && r && e, SKDSP_ERR_BADARG, "lag_corr: null pointer");
+    API_BEGIN;
+    const int64_t K = 2 * (len / 2);
+    const size_t a_bytes = (size_t)K * dtype_size(a_dtype), b_bytes = (size_t)K * dtype_size(b_dtype), r_off = round_up(b_bytes, 256), r_bytes = (size_t)nl * 16;
+    const size_t e_off = r_off + round_up(r_bytes, 256);
+    void *a_dev = nullptr, *b_dev = nullptr, *scratch = nullptr;
+    if ((rc = ws_reserve(1, e_off + 256, &b_dev))) return rc;
+    if ((rc = ws_reserve(3, lagcorr_scratch_bytes(len, n_lags), &scratch))) return rc;
+    if ((rc = stage_in(a, a_bytes, &a_dev))) return rc;
+    SK_HIP(hipMemcpyAsync(b_dev, b, b_bytes, hipMemcpyHostToDevice, ctx().stream));
+    void *r_dev = (char *)b_dev + r_off;
+    double *e_dev = reinterpret_cast<double *>((char *)b_dev + e_off);
+    if ((rc = lagcorr_launch(a_dev, a_dtype, b_dev, b_dtype, len, n_lags, quant_levels, scratch, r_dev, e_dev, ctx().stream))) return rc;
+    SK_HIP(hipMemcpyAsync(e, e_dev, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx().stream));
+    return stage_out(r, r_dev, r_bytes);
+}
+
+int skdsp_sym_count_rows_dev(const void *tx_dev, int tx_dtype, int64_t tx_stride, int64_t t0, const void *x_dev, int x_dtype, int64_t x_stride, int64_t start,
+                             int64_t step, int64_t r0, int64_t n, int64_t nrow, int mode, int levels, int kphase, int64_t *counts_dev)
+{
+    int rc = symcount_check(tx_dtype, tx_stride, t0, x_dtype, x_stride, start, step, r0, n, nrow, mode, levels, kphase);   // (argument errors need no device)
+    if (rc || nrow == 0) return rc;
+    SK_CHECK(counts_dev && ((uintptr_t)counts_dev & 7) == 0, SKDSP_ERR_BADARG, "sym_count: the counts must be an 8-byte aligned pointer");
+    SK_CHECK(n == 0 || (tx_dev && x_dev), SKDSP_ERR_BADARG, "sym_count: null pointer");
+    API_BEGIN;
+    return symcount_launch(tx_dev, tx_dtype, tx_stride, t0, x_dev, x_dtype, x_stride, start, step, r0, n, nrow, mode, levels, kphase, counts_dev, ctx().stream);
+}
+
+// host form: both arrays are copied whole -- through the last element a row reads
+int skdsp_sym_count_rows(const void *tx, int tx_dtype, int64_t tx_stride, int64_t t0, const void *x, int x_dtype, int64_t x_stride, int64_t start, int64_t step,
+                         int64_t r0, int64_t n, int64_t nrow, int mode, int levels, int kphase, int64_t *counts)
+{
+    int rc = symcount_check(tx_dtype, tx_stride, t0, x_dtype, x_stride, start, step, r0, n, nrow, mode, levels, kphase);
+    if (rc || nrow == 0) return rc;
+    SK_CHECK(counts, SKDSP_ERR_BADARG, "sym_count: null counts");
+    if (n == 0) {
+        for (int64_t i = 0; i < 4 * nrow; ++i) counts[i] = 0;
+        return SKDSP_OK;
+    }
+    SK_CHECK(tx && x, SKDSP_ERR_BADARG, "sym_count: null pointer");
+    API_BEGIN;
+    const size_t tx_bytes = (size_t)((nrow - 1) * tx_stride + t0 + n) * dtype_size(tx_dtype);
+    const size_t x_bytes = (size_t)((nrow - 1) * x_stride + start + (r0 + n - 1) * step + 1) * dtype_size(x_dtype), cnt_off = round_up(x_bytes, 256);
+    void *tx_dev = nullptr, *x_dev = nullptr;
+    if ((rc = ws_reserve(1, cnt_off + (size_t)nrow * 4 * sizeof(int64_t) + 256, &x_dev))) return rc;
+    if ((rc = stage_in(tx, tx_bytes, &tx_dev))) return rc;
+    SK_HIP(hipMemcpyAsync(x_dev, x, x_bytes, hipMemcpyHostToDevice, ctx().stream));
+    int64_t *counts_dev = reinterpret_cast<int64_t *>((char *)x_dev + cnt_off);
+    if ((rc = symcount_launch(tx_dev, tx_dtype, tx_stride, t0, x_dev, x_dtype, x_stride, start, step, r0, n, nrow, mode, levels, kphase, counts_dev, ctx().stream))) return rc;
+    return stage_out(counts, counts_dev, (size_t)nrow * 4 * sizeof(int64_t));
+}
+
 }  // extern "C"

@@ -396,4 +396,16 @@ int ofdm_equalize_check(int64_t nsym, int64_t nrow, int dtype, int nf, int npb, 
 int ofdm_equalize_launch(const void *z_dev, int64_t z_stride, int64_t nsym, int64_t nrow, int dtype, int nf, int npb, double alpha, const double *hht_host,
                          void *scratch_dev, void *out_dev, int64_t out_stride, void *h_dev, hipStream_t s);
 
+// ---- symbol-error tools (symerr.hip): digitalcom.xcorr / qam_sep / qpsk_bep / bpsk_bep; the plans and the per-element decisions are symerr_core.hpp ----
+// R[l] = sum_n a[(n + l) mod K] conj(b[n]) over the reference's lag window, float64, with E1 = sum |a|^2 and E2 = sum |b|^2; quant_levels M > 0 passes a through
+// qam_sep's quantiser at the load.  The count: tx symbol i = tx[t0 + i], rx symbol i = x[start + (r0 + i) step] of its row, strides in elements.
+int lagcorr_check(int64_t len, int64_t n_lags, int a_dtype, int b_dtype, int quant_levels, int64_t *n_out, int64_t *first_lag);   // host-only
+size_t lagcorr_scratch_bytes(int64_t len, int64_t n_lags);                                                                        // host-only
+int lagcorr_launch(const void *a_dev, int a_dtype, const void *b_dev, int b_dtype, int64_t len, int64_t n_lags, int quant_levels, void *scratch_dev, void *r_dev,
+                   double *e_dev, hipStream_t s);
+int symcount_check(int tx_dtype, int64_t tx_stride, int64_t t0, int x_dtype, int64_t x_stride, int64_t start, int64_t step, int64_t r0, int64_t n, int64_t nrow, int mode,
+                   int levels, int kphase);   // host-only
+int symcount_launch(const void *tx_dev, int tx_dtype, int64_t tx_stride, int64_t t0, const void *x_dev, int x_dtype, int64_t x_stride, int64_t start, int64_t step,
+                    int64_t r0, int64_t n, int64_t nrow, int mode, int levels, int kphase, int64_t *counts_dev, hipStream_t s);
+
 }  // namespace skdsp

@@ -44,6 +44,7 @@ SYMBOLS = [
     "skdsp_mpsk_demap_rows", "skdsp_mpsk_demap_rows_dev",
     "skdsp_awgn_rows_dev", "skdsp_awgn_bits_rows_dev", "skdsp_awgn_sigma_rows_dev", "skdsp_random_bits_rows_dev", "skdsp_pn_rows_dev",
     "skdsp_ofdm_tx_rows", "skdsp_ofdm_tx_rows_dev", "skdsp_ofdm_rx_rows", "skdsp_ofdm_rx_rows_dev", "skdsp_ofdm_equalize_rows", "skdsp_ofdm_equalize_rows_dev",
+    "skdsp_lag_corr_len", "skdsp_lag_corr", "skdsp_lag_corr_dev", "skdsp_sym_count_rows", "skdsp_sym_count_rows_dev",
     "skdsp_dist_unique_id", "skdsp_dist_init", "skdsp_dist_shutdown", "skdsp_dist_comm_count", "skdsp_dist_barrier",
     "skdsp_dist_allreduce_max", "skdsp_dist_allreduce_sum", "skdsp_dist_sendrecv", "skdsp_dist_allgather", "skdsp_dist_halo_exchange", "skdsp_fir_filter_shard_dev",
 ]
@@ -190,6 +191,11 @@ def load():
             L.skdsp_ofdm_rx_rows_dev.argtypes = [vp, i64, i64, i64, ci, ci, ci, ci, ci, ci, dbl, vp, vp, i64, vp]
             L.skdsp_ofdm_equalize_rows.argtypes = [vp, i64, i64, ci, ci, ci, dbl, vp, vp, vp]
             L.skdsp_ofdm_equalize_rows_dev.argtypes = [vp, i64, i64, i64, ci, ci, ci, dbl, vp, vp, i64, vp]
+        if hasattr(L, "skdsp_lag_corr"):
+            L.skdsp_lag_corr_len.argtypes = [i64, i64, p64, p64]
+            L.skdsp_lag_corr.argtypes = [vp, ci, vp, ci, i64, i64, ci, vp, vp, vp]
+            L.skdsp_lag_corr_dev.argtypes = [vp, ci, vp, ci, i64, i64, ci, vp, vp]
+            L.skdsp_sym_count_rows.argtypes = L.skdsp_sym_count_rows_dev.argtypes = [vp, ci, i64, i64, vp, ci, i64, i64, i64, i64, i64, i64, ci, ci, ci, vp]
         L.skdsp_dist_unique_id.argtypes = [vp]
         L.skdsp_dist_init.argtypes = [ci, ci, vp]
         L.skdsp_dist_comm_count.argtypes = [ctypes.POINTER(ci)]
@@ -1321,6 +1327,150 @@ def ofdm_equalize_rows(z3d, npb, alpha, hht):
     check(load().skdsp_ofdm_equalize_rows(_ptr(z3d), nsym, nrow, code_of(z3d.dtype), nf, int(npb), float(alpha), hp, _ptr(out), _ptr(h)))
     del keep
     return out, h
+
+
+
+# --------------------------------------------------------------------------
+# symbol-error tools (csrc/symerr.hip, csrc/symerr_core.hpp): the lag-window correlation behind xcorr / qam_sep and the fused count
+# --------------------------------------------------------------------------
+SYM_QAM, SYM_QPSK, SYM_BPSK = 0, 1, 2
+QAM_LEVELS = {'qpsk': 2, '16qam': 4, '64qam': 8, '256qam': 16}
+
+
+def lag_corr_len(n, n_lags):
+    """(number of lags, first lag) that xcorr keeps of streams of n samples: K = 2 (n // 2), min(2 n_lags + 1, K) lags from -min(n_lags, K / 2)"""
+    nl, l0 = ctypes.c_int64(0), ctypes.c_int64(0)
+    check(load().skdsp_lag_corr_len(int(n), int(n_lags), ctypes.byref(nl), ctypes.byref(l0)))
+    return nl.value, l0.value
+
+
+def _stream(x, what):
+    """x as the symbol-error kernels take it: float32 / complex64 / float64 / complex128 kept, integers as float64, anything else numeric widened"""
+    x = np.asarray(x)
+    if x.dtype.kind in "biu":
+        x = x.astype(np.float64)
+    if x.dtype.kind not in "fc":
+        raise TypeError("%s: a numeric array (got %s)" % (what, x.dtype))
+    if x.dtype not in _CODE_OF:
+        x = x.astype(np.complex128 if x.dtype.kind == "c" else np.float64)
+    return np.ascontiguousarray(x)
+
+
+def qam_quantise_host(x, levels):
+    """qam_sep's quantiser (digitalcom.py:525-536), componentwise: 2 clip(rint((M - 1)(v + 1) / 2), 0, M - 1) - (M - 1), float64 / complex128"""
+    x = np.asarray(x)
+    def comp(v):
+        q = np.rint((levels - 1) * (v.astype(np.float64) + 1.0) / 2.)
+        q = np.where(q > levels - 1, float(levels - 1), q)
+        q = np.where(q < 0, 0.0, q)
+        return 2 * q - (levels - 1)
+    if x.dtype.kind == "c":
+        return comp(x.real) + 1j * comp(x.imag)
+    return comp(x) + 1j * comp(np.zeros(x.shape))
+
+
+def lag_corr(a, b, n_lags, quant_levels=0):
+    """(R complex128, lags int64, E1, E2): R[i] = sum_n a[(n + lags[i]) mod K] conj(b[n]) over the first K = 2 (len(a) // 2) samples of both streams,
+    unnormalised, float64 sums in a fixed order (csrc/symerr.hip: lagcorr_kernel); quant_levels M > 0: a through qam_sep's quantiser at the load"""
+    a, b = _stream(a, "lag_corr"), _stream(b, "lag_corr")
+    if a.ndim != 1 or b.ndim != 1:
+        raise ValueError("lag_corr: one-dimensional streams")
+    K = 2 * (a.size // 2)
+    if b.size < K:
+        raise ValueError("lag_corr: the second stream holds fewer than K = %d samples" % K)
+    nl, _ = lag_corr_len(a.size, n_lags)
+    lags, r, e = np.zeros(nl, dtype=np.int64), np.zeros(nl, dtype=np.complex128), np.zeros(2)
+    check(load().skdsp_lag_corr(_ptr(a), code_of(a.dtype), _ptr(b), code_of(b.dtype), a.size, int(n_lags), int(quant_levels), _ptr(lags), _ptr(r), _ptr(e)))
+    return r, lags, float(e[0]), float(e[1])
+
+
+def lag_corr_host(a, b, n_lags, quant_levels=0):
+    """lag_corr by direct summation in NumPy (no GPU): the yardstick of the kernel at test sizes (O(K lags))"""
+    a, b = _stream(a, "lag_corr"), _stream(b, "lag_corr")
+    K = 2 * (a.size // 2)
+    half = K // 2
+    nl, l0 = (K, -half) if n_lags >= half else (2 * n_lags + 1, -n_lags)
+    a = a[:K].astype(np.complex128) if not quant_levels else qam_quantise_host(a[:K], quant_levels)
+    b = b[:K].astype(np.complex128)
+    lags = l0 + np.arange(nl, dtype=np.int64)
+    r = np.array([np.sum(np.roll(a, -int(l)) * np.conj(b)) for l in lags], dtype=np.complex128).reshape(nl)
+    return r, lags, float(np.sum(a.real ** 2 + a.imag ** 2)), float(np.sum(b.real ** 2 + b.imag ** 2))
+
+
+def lag_corr_dev(ad, bd, n, n_lags, rd, ed, quant_levels=0, a_dtype=None, b_dtype=None):
+    """Device-resident form: ad / bd hold the streams (DeviceArray or pointers with a_dtype / b_dtype), rd receives min(2 n_lags + 1, K) complex128,
+    ed the two energies (float64)"""
+    check(load().skdsp_lag_corr_dev(_dp(ad), code_of(a_dtype or ad.dtype), _dp(bd), code_of(b_dtype or bd.dtype), int(n), int(n_lags), int(quant_levels), _dp(rd), _dp(ed)))
+
+
+def _sym_mode_check(mode, levels, kphase):
+    if mode not in (SYM_QAM, SYM_QPSK, SYM_BPSK):
+        raise ValueError("sym_count: mode SYM_QAM, SYM_QPSK or SYM_BPSK")
+    if mode == SYM_QAM and levels not in (2, 4, 8, 16):
+        raise ValueError("sym_count: QAM of 2, 4, 8 or 16 levels per component")
+    if int(kphase) != kphase or not 0 <= kphase <= (1 if mode == SYM_BPSK else 3):
+        raise ValueError("sym_count: the rotation is 0 ... 3 (BPSK: 0 or 1)")
+
+
+def _rot_host(x, mode, kphase):
+    """x (1j)^k as swaps and negations (BPSK: (-1)^k on the real part)"""
+    re, im = x.real.astype(np.float64), x.imag.astype(np.float64)
+    if mode == SYM_BPSK:
+        return (-re if kphase & 1 else re), im
+    return [(re, im), (-im, re), (-re, -im), (im, -re)][kphase]
+
+
+def sym_count_rows_host(tx2d, x2d, mode, levels=0, kphase=0, start=0, step=1, n=None, t0=0, r0=0):
+    """sym_count_rows in NumPy (no GPU): int64 (nrow, 4) -- the sums of the mode, then the symbols that break a precondition (left out of the sums)"""
+    _sym_mode_check(mode, levels, kphase)
+    tx, x = np.atleast_2d(_stream(tx2d, "sym_count")), np.atleast_2d(_stream(x2d, "sym_count"))
+    if n is None:
+        n = min(tx.shape[1] - t0, sym_count(x.shape[1], start, step) - r0)
+    t = tx[:, t0:t0 + n].astype(np.complex128)
+    r = x[:, start + r0 * step::step][:, :n].astype(np.complex128)
+    out = np.zeros((tx.shape[0], 4), dtype=np.int64)
+    with np.errstate(all="ignore"):
+        if mode == SYM_QAM:
+            ok = np.isfinite(t.real) & np.isfinite(t.imag) & np.isfinite(r.real) & np.isfinite(r.imag) & (t.real == np.rint(t.real)) & (t.imag == np.rint(t.imag))
+            qr, qi = _rot_host(qam_quantise_host(r, levels), mode, kphase)
+            out[:, 0] = np.sum(ok & ((qr != t.real) | (qi != t.imag)), axis=1)
+        else:
+            xr, xi = _rot_host(r, mode, kphase)
+            parts = [(t.real, xr)] if mode == SYM_BPSK else [(t.real, xr), (t.imag, xi)]
+            ok = np.isfinite(xr) if mode == SYM_BPSK else np.isfinite(xr) & np.isfinite(xi)
+            halves = [((a + 1) / 2, (b + 1) / 2) for a, b in parts]
+            for ha, hb in halves:
+                ok = ok & (np.abs(ha) < 32768) & (np.abs(hb) < 32768)
+            errs = [np.where(ok, ha, 0).astype(np.int16) ^ np.where(ok, hb, 0).astype(np.int16) for ha, hb in halves]
+            out[:, 0] = np.sum(errs[0].astype(np.int64), axis=1)
+            if mode == SYM_QPSK:
+                out[:, 1] = np.sum(errs[1].astype(np.int64), axis=1)
+                out[:, 2] = np.sum((errs[0] | errs[1]).astype(np.int64), axis=1)
+        out[:, 3] = np.sum(~ok, axis=1)
+    return out
+
+
+def sym_count_rows(tx2d, x2d, mode, levels=0, kphase=0, start=0, step=1, n=None, t0=0, r0=0):
+    """int64 (nrow, 4) per row of two 2-D arrays, in one launch (csrc/symerr.hip: symcount_kernel): tx symbol i = tx2d[r, t0 + i], rx symbol i =
+    x2d[r, start + (r0 + i) step] rotated by (1j)^kphase; the sums of the mode (skdsp.h), then the count of symbols that break a precondition"""
+    _sym_mode_check(mode, levels, kphase)
+    tx, x = _stream(tx2d, "sym_count"), _stream(x2d, "sym_count")
+    if tx.ndim != 2 or x.ndim != 2 or tx.shape[0] != x.shape[0]:
+        raise ValueError("sym_count_rows: two 2-D arrays with the same number of rows")
+    if n is None:
+        n = min(tx.shape[1] - t0, sym_count(x.shape[1], start, step) - r0)
+    if n < 0 or t0 < 0 or r0 < 0 or t0 + n > tx.shape[1] or (n and start + (r0 + n - 1) * step >= x.shape[1]):
+        raise ValueError("sym_count_rows: symbols beyond a row")
+    counts = np.zeros((tx.shape[0], 4), dtype=np.int64)
+    check(load().skdsp_sym_count_rows(_ptr(tx), code_of(tx.dtype), tx.shape[1], int(t0), _ptr(x), code_of(x.dtype), x.shape[1], int(start), int(step), int(r0), int(n),
+                                      tx.shape[0], int(mode), int(levels), int(kphase), _ptr(counts)))
+    return counts
+
+
+def sym_count_rows_dev(tx, tx_dtype, tx_stride, t0, x, x_dtype, x_stride, start, step, r0, n, nrow, mode, levels, kphase, counts):
+    """Device-resident form: tx / x / counts are DeviceArray / DeviceBytes or pointers; counts receives nrow x int64[4] (zeroed by the call)"""
+    check(load().skdsp_sym_count_rows_dev(_dp(tx), code_of(tx_dtype), int(tx_stride), int(t0), _dp(x), code_of(x_dtype), int(x_stride), int(start), int(step), int(r0),
+                                          int(n), int(nrow), int(mode), int(levels), int(kphase), _dp(counts)))
 
 
 def device_bytes_of(a):

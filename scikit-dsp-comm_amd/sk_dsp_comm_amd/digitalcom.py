@@ -11,6 +11,8 @@ the GPU (sigsys.pulse_shape -> multirate_FIR.up -> fir_direct.hip / fir_ols.hip)
   bit_errors(tx_data, rx_data, n_corr, n_transient)                      digitalcom.py:353-415    (the count: csrc/convcode.hip)
   qam_gray_decode(x_hat, mod), mpsk_gray_decode(x_hat, mod)              digitalcom.py:1684-1739, 1829-1883  (csrc/symmap.hip)
   qam_gray_map_rows, mpsk_gray_map_rows, qam_gray_decode_rows, mpsk_gray_decode_rows: frame sets, one launch (csrc/symmap.hip)
+  xcorr(x1, x2, n_lags), qam_sep, qpsk_bep, bpsk_bep                     digitalcom.py:1163-1179, 495-582, 723-790, 793-846  (csrc/symerr.hip)
+  qam_sep_rows, qpsk_bep_rows, bpsk_bep_rows: aligned frame sets, no search, one launch of the fused count (csrc/symerr.hip)
 
 farrow_resample, the arbitrary-ratio resampler, is its own engine (csrc/farrow.hip): each output is a 4-tap FIR whose taps
 are polynomials in a fractional delay, evaluated on the GPU for all outputs at once (the reference loops over them in Python).
@@ -814,3 +816,340 @@ def chan_est_equalize(z, npbp, alpha, ht=None):
         raise ValueError("chan_est_equalize: ht holds the channel on the nf carriers")
     out, h = _ffi.ofdm_equalize_rows(np.ascontiguousarray(zin)[None], int(npbp), alpha, ht)
     return out[0], h[0]
+
+
+# ------------------------------------------------------------------------------------------------ xcorr, qam_sep, qpsk_bep, bpsk_bep
+# (digitalcom.py:1163-1179, 495-582, 723-790, 793-846).  What the reference computes, its quirks included, and the deliberate differences:
+# tests/golden/g25_conventions.json, DESIGN.md 4.20.
+class _SymStream:
+    """A one-dimensional stream for the symbol-error tools: a host sequence (uploaded on first use) or an _ffi.DeviceArray (never copied whole)"""
+
+    def __init__(self, v, name):
+        self.owned = None
+        if isinstance(v, _ffi.DeviceArray):
+            self.dev, self.host, self.n, self.dtype = v, None, v.n, v.dtype
+        else:
+            a = _ffi._stream(v, name)
+            if a.ndim != 1:
+                raise ValueError("%s must be one-dimensional (got shape %r)" % (name, a.shape))
+            self.dev, self.host, self.n, self.dtype = None, a, a.size, a.dtype
+
+    def head(self, at, count):
+        count = max(0, min(count, self.n - at))
+        return self.host[at:at + count] if self.host is not None else self.dev.to_host(at, count)
+
+    def ptr(self, at):
+        if self.dev is None:
+            self.dev = self.owned = _ffi.DeviceArray.from_host(self.host)
+        return self.dev.ptr + int(at) * self.dtype.itemsize
+
+    def free(self):
+        if self.owned is not None:
+            self.owned.free()
+            self.owned = self.dev = None
+
+
+def _sep_levels(mod):
+    levels = _ffi.QAM_LEVELS.get(mod.lower()) if isinstance(mod, str) else None
+    if levels is None:
+        raise ValueError('Unknown mod_type')
+    return levels
+
+
+def _normalise(R, E1, E2, name):
+    if not (np.all(np.isfinite(R.real)) and np.all(np.isfinite(R.imag)) and np.isfinite(E1) and np.isfinite(E2)):
+        raise ValueError("%s: a sample is not finite" % name)
+    if R.size and (E1 == 0 or E2 == 0):
+        raise ValueError("%s: a stream has zero energy" % name)
+    return R / np.sqrt(E1 * E2) if R.size else R
+
+
+def _lag_corr_streams(a, b, at, n, n_lags, levels):
+    """lagcorr_kernel on n samples of two _SymStreams from element `at`: (R, lags, E1, E2), unnormalised"""
+    nl, l0 = _ffi.lag_corr_len(n, n_lags)
+    lags = l0 + np.arange(nl, dtype=np.int64)
+    if nl == 0:
+        return np.zeros(0, dtype=np.complex128), lags, 0.0, 0.0
+    out = _ffi.DeviceArray(nl + 1, np.complex128)
+    try:
+        _ffi.lag_corr_dev(a.ptr(at), b.ptr(at), n, n_lags, out.ptr, out.ptr + 16 * nl, levels, a.dtype, b.dtype)
+        res = out.to_host()
+    finally:
+        out.free()
+    return res[:nl], lags, float(res[nl].real), float(res[nl].imag)
+
+
+def xcorr_host(x1, x2, n_lags):
+    """xcorr in NumPy (no GPU), the reference's FFT form in float64 / complex128: the yardstick of xcorr."""
+    x1, x2 = _SymStream(x1, "x1").host, _SymStream(x2, "x2").host
+    K = 2 * (x1.size // 2)
+    if x2.size < K or int(n_lags) != n_lags or n_lags < 0:
+        raise ValueError("xcorr: x2 must hold at least K = %d samples and n_lags be a non-negative integer" % K)
+    a, b = x1[:K].astype(np.complex128), x2[:K].astype(np.complex128)
+    k = np.arange(K) - K // 2
+    keep = np.abs(k) <= n_lags
+    R = np.fft.fftshift(np.fft.ifft(np.fft.fft(a) * np.conj(np.fft.fft(b)))) if K else np.zeros(0, dtype=np.complex128)
+    return _normalise(R[keep], float(np.sum(np.abs(a) ** 2)), float(np.sum(np.abs(b) ** 2)), "xcorr"), k[keep]
+
+
+def xcorr(x1, x2, n_lags):
+    """r12, k = xcorr(x1, x2, n_lags), digitalcom.py:1163-1179: the energy-normalised circular cross-correlation of the first K = 2 (len(x1) // 2)
+    samples, r12[i] = sum_n x1[(n + k[i]) mod K] conj(x2[n]) / sqrt(E1 E2), for the lags |k| <= n_lags behind the reference's fftshift (k from
+    -K / 2 to K / 2 - 1).  The reference takes four whole-length FFTs; here only the lag window is computed, by direct float64 summation on the GPU
+    (csrc/symerr.hip: lagcorr_kernel), 2e-17 from the exact value where the FFT form lies 3.5e-16 from it.  r12 is complex128, k int64.
+    x1 / x2: sequences or _ffi.DeviceArray.
+
+    Deliberate differences (tests/golden/g25_conventions.json): ValueError for a non-finite sample, a stream of zero energy (the reference returns
+    nan) and an x2 shorter than K (the reference fails to broadcast)."""
+    a, b = _SymStream(x1, "x1"), _SymStream(x2, "x2")
+    K = 2 * (a.n // 2)
+    if b.n < K or int(n_lags) != n_lags or n_lags < 0:
+        raise ValueError("xcorr: x2 must hold at least K = %d samples and n_lags be a non-negative integer" % K)
+    try:
+        R, lags, E1, E2 = _lag_corr_streams(a, b, 0, a.n, int(n_lags), 0)
+    finally:
+        a.free()
+        b.free()
+    return _normalise(R, E1, E2, "xcorr"), lags
+
+
+def _pick_rotation(R, lags, bpsk=False):
+    """(kmax, taumax) from one correlation: rotation k's candidate is Re((1j)^k R) (BPSK: (-1)^k); the largest maximum, ties to the smallest k, then
+    the first lag"""
+    cands = [R.real, -R.real] if bpsk else [R.real, -R.imag, -R.real, R.imag]
+    tops = np.array([c.max() for c in cands])
+    kmax = int(np.argmax(tops))
+    return kmax, int(lags[int(np.argmax(cands[kmax]))])
+
+
+def _integer_valued(x):
+    return bool(np.all(np.isfinite(x.real)) and np.all(np.isfinite(x.imag)) and np.all(x.real == np.rint(x.real)) and np.all(x.imag == np.rint(x.imag)))
+
+
+def _exact_circular(a, b):
+    """sum_n a[(n + m) mod N] conj(b[n]) of two integer-valued complex vectors of equal length as exact Gaussian integers (float64 holds them), or
+    None where a float64 FFT cannot guarantee them: every value is an integer below N max|a| max|b|, the FFT's error is some 1e-15 of that"""
+    N = a.size
+    bound = N * (np.max(np.abs(a)) if N else 0) * (np.max(np.abs(b)) if N else 0)
+    if bound >= 2.0 ** 40:
+        return None
+    R = np.fft.ifft(np.fft.fft(a) * np.conj(np.fft.fft(b)))
+    return np.rint(R.real) + 1j * np.rint(R.imag)
+
+
+def qam_sep_search(tx, rx_q, n_corr):
+    """(kmax, taumax) of qam_sep's search in exact integers on the host: tx integer-valued, rx_q quantised, equal lengths."""
+    K = 2 * (tx.size // 2)
+    R = _exact_circular(rx_q[:K].astype(np.complex128), tx[:K].astype(np.complex128))
+    if R is None:
+        raise ValueError("qam_sep: streams too long or too large for the exact host search")
+    k = np.arange(K) - K // 2
+    keep = np.abs(k) <= n_corr
+    return _pick_rotation(np.fft.fftshift(R)[keep], k[keep])
+
+
+def _sep_result(count, counts, SEP_disp):
+    if counts[3]:
+        raise ValueError("qam_sep: %d symbols of the overlap are not finite or tx_data is not integer-valued there" % counts[3])
+    errors = int(counts[0])
+    if SEP_disp:
+        log.info('Symbols = %d, Errors %d, SEP = %1.2e' % (count, errors, errors / float(count)))
+    return count, errors, errors / float(count)
+
+
+def qam_sep_host(tx_data, rx_data, mod, n_corr=1024, n_transient=0, SEP_disp=True):
+    """qam_sep in NumPy (no GPU): the yardstick of qam_sep."""
+    levels = _sep_levels(mod)
+    n_corr, n_transient = _check_n_corr(n_corr, n_transient)
+    tx, rx = _SymStream(tx_data, "tx_data").host[n_transient:], _SymStream(rx_data, "rx_data").host[n_transient:]
+    n = min(tx.size, rx.size)
+    if n < 2:
+        raise ValueError("qam_sep: fewer than two symbols behind the transient")
+    tx, rx = tx[:n].astype(np.complex128), rx[:n]
+    if not (np.all(np.isfinite(rx.real)) and np.all(np.isfinite(rx.imag))):
+        raise ValueError("qam_sep: a sample is not finite")
+    if not _integer_valued(tx):
+        raise ValueError("qam_sep: tx_data must hold integer-valued symbols (qam_bb's tx_data)")
+    rq = _ffi.qam_quantise_host(rx, levels)
+    if not np.any(tx[:2 * (n // 2)]) or not np.any(rq[:2 * (n // 2)]):
+        raise ValueError("qam_sep: a stream has zero energy")
+    kmax, taumax = qam_sep_search(tx, rq, n_corr)
+    if SEP_disp:
+        log.info('Phase ambiquity = (1j)**%d, taumax = %d' % (kmax, taumax))
+    t0, r0, count = _overlap(n, n, taumax)
+    if count <= 0:
+        raise ValueError("qam_sep: the streams do not overlap at lag %d" % taumax)
+    counts = _ffi.sym_count_rows_host(tx[None, t0:t0 + count], rx[None, r0:r0 + count], _ffi.SYM_QAM, levels, kmax)[0]
+    return _sep_result(count, counts, SEP_disp)
+
+
+def _count_streams(tx, rx, t_at, r_at, count, mode, levels, kphase):
+    """symcount_kernel on one row of `count` symbols of two _SymStreams: int64[4]"""
+    cnt = _ffi.DeviceBytes(32)
+    try:
+        _ffi.sym_count_rows_dev(tx.ptr(t_at), tx.dtype, 0, 0, rx.ptr(r_at), rx.dtype, 0, 0, 1, 0, count, 1, mode, levels, kphase, cnt)
+        return cnt.read().view(np.int64)
+    finally:
+        cnt.free()
+
+
+def qam_sep(tx_data, rx_data, mod, n_corr=1024, n_transient=0, SEP_disp=True):
+    """Nsymb, Nerr, SEP_hat = qam_sep(tx_data, rx_data, mod, n_corr=1024, n_transient=0, SEP_disp=True), digitalcom.py:495-582: the soft symbols
+    of rx_data (on the unit square) are quantised to the M levels of mod ('qpsk', '16qam', '64qam', '256qam'), the lag |tau| <= n_corr and the
+    rotation (1j)^k between the streams are found from xcorr over the WHOLE stream, and the symbols that differ are counted over the overlap.
+
+    The reference takes sixteen whole-length FFTs for the search.  Here the quantiser runs at the load of one lag-window correlation on the GPU
+    (csrc/symerr.hip: lagcorr_kernel): quantised rx and qam_bb's tx_data are Gaussian integers, so every correlation value is an exact integer,
+    rotation k's candidate is Re((1j)^k R0), and the pick is the exact maximum -- ties to the smallest k, then the first lag, as bit_errors_search.
+    Only the 2 n_corr + 1 values cross to the host.  The count (quantise, rotate, compare) is one fused kernel over the overlap (symcount_kernel).
+    Returns (int, int, float) and logs the reference's two lines.  tx_data / rx_data: sequences or _ffi.DeviceArray.
+
+    Deliberate differences (tests/golden/g25_conventions.json): n_corr follows bit_errors' rules (even, at most 65536); ValueError for an unknown
+    mod, a non-finite sample, a tx_data that is not integer-valued, a stream of zero energy and an empty overlap."""
+    levels = _sep_levels(mod)
+    n_corr, n_transient = _check_n_corr(n_corr, n_transient)
+    tx, rx = _SymStream(tx_data, "tx_data"), _SymStream(rx_data, "rx_data")
+    n = min(tx.n, rx.n) - n_transient
+    if n < 2:
+        raise ValueError("qam_sep: fewer than two symbols behind the transient")
+    try:
+        R, lags, E1, E2 = _lag_corr_streams(rx, tx, n_transient, n, n_corr, levels)
+        _normalise(R, E1, E2, "qam_sep")
+        if not _integer_valued(R):
+            raise ValueError("qam_sep: tx_data must hold integer-valued symbols (qam_bb's tx_data)")
+        kmax, taumax = _pick_rotation(R, lags)
+        if SEP_disp:
+            log.info('Phase ambiquity = (1j)**%d, taumax = %d' % (kmax, taumax))
+        t0, r0, count = _overlap(n, n, taumax)
+        if count <= 0:
+            raise ValueError("qam_sep: the streams do not overlap at lag %d" % taumax)
+        counts = _count_streams(tx, rx, n_transient + t0, n_transient + r0, count, _ffi.SYM_QAM, levels, kmax)
+    finally:
+        tx.free()
+        rx.free()
+    return _sep_result(count, counts, SEP_disp)
+
+
+def bep_search(tx_head, rx_head, n_corr, bpsk=False, exact=True):
+    """(kmax, taumax) of qpsk_bep's / bpsk_bep's search: the length-n_corr circular correlation of the two heads (cut or zero-padded to n_corr),
+    lag 0 at n_corr / 2 behind the fftshift.  Integer-valued heads: exact integers, one correlation, the candidates Re((1j)^k R0) (BPSK: +-Re R0),
+    ties to the smallest k, then the first lag.  Otherwise (or with exact=False) the reference's own float64 FFT expression per rotation."""
+    def fit(v):
+        out = np.zeros(n_corr, dtype=np.float64 if bpsk else np.complex128)
+        v = np.asarray(v)[:n_corr]
+        out[:v.size] = v.real if bpsk else v
+        return out
+    t, r = fit(tx_head), fit(rx_head)
+    if not (np.all(np.isfinite(t.real)) and np.all(np.isfinite(t.imag)) and np.all(np.isfinite(r.real)) and np.all(np.isfinite(r.imag))):
+        raise ValueError("%s: a sample is not finite" % ("bpsk_bep" if bpsk else "qpsk_bep"))
+    lags = np.arange(n_corr) - n_corr // 2
+    R = _exact_circular(r, t) if exact and _integer_valued(t) and _integer_valued(r) else None
+    if R is not None:
+        return _pick_rotation(np.fft.fftshift(R), lags, bpsk)
+    T = np.conj(np.fft.fft(t, n_corr))
+    rots = (1, -1) if bpsk else (1, 1j, -1, -1j)
+    cands = [np.fft.fftshift(np.fft.ifft(np.fft.fft(r if k == 0 else rot * r, n_corr) * T)).real for k, rot in enumerate(rots)]
+    kmax = int(np.argmax(np.array([c.max() for c in cands])))
+    return kmax, int(lags[int(np.argmax(cands[kmax]))])
+
+
+def _bep(name, mode, host, tx_data, rx_data, n_corr, n_transient):
+    n_corr, n_transient = _check_n_corr(n_corr, n_transient)
+    tx, rx = _SymStream(tx_data, "tx_data"), _SymStream(rx_data, "rx_data")
+    n_tx, n_rx = tx.n - n_transient, rx.n - n_transient
+    if n_tx <= 0 or n_rx <= 0:
+        raise ValueError("%s: no symbols behind the transient" % name)
+    kmax, taumax = bep_search(tx.head(n_transient, n_corr), rx.head(n_transient, n_corr), n_corr, mode == _ffi.SYM_BPSK)
+    log.info('kmax =  %d, taumax = %d' % (kmax, taumax))
+    t0, r0, count = _overlap(n_tx, n_rx, taumax)
+    try:
+        if count <= 0:
+            counts = np.zeros(4, dtype=np.int64)
+        elif host:
+            counts = _ffi.sym_count_rows_host(tx.host[None, n_transient + t0:n_transient + t0 + count], rx.host[None, n_transient + r0:n_transient + r0 + count], mode, 0, kmax)[0]
+        else:
+            counts = _count_streams(tx, rx, n_transient + t0, n_transient + r0, count, mode, 0, kmax)
+    finally:
+        tx.free()
+        rx.free()
+    if counts[3]:
+        raise ValueError("%s: %d symbols of the overlap are not finite or beyond int16 as (v + 1) / 2" % (name, counts[3]))
+    return max(count, 0), counts
+
+
+def qpsk_bep(tx_data, rx_data, n_corr=1024, n_transient=0):
+    """S_count, I_errors, Q_errors, S_errors = qpsk_bep(tx_data, rx_data, n_corr=1024, n_transient=0), digitalcom.py:723-790: lag and rotation
+    (1j)^k from the first n_corr symbols behind the transient (bep_search, on the host: only 2 n_corr elements leave the device), then over the
+    whole overlap tI = int16((re tx + 1) / 2), rI likewise of the rotated rx, the same for Q, and sum(tI ^ rI), sum(tQ ^ rQ),
+    sum((tI ^ rI) | (tQ ^ rQ)) on the GPU (csrc/symerr.hip: symcount_kernel) -- the reference's integers also where soft values make them other
+    than 0 / 1.  Returns (int, numpy.int64, numpy.int64, numpy.int64).  tx_data / rx_data: sequences or _ffi.DeviceArray.
+
+    Deliberate differences (tests/golden/g25_conventions.json): the reference raises TypeError on every call with NumPy 2 (its float taumax is
+    used as a slice index); this builds the documented intent, int(taumax), as bpsk_bep does.  n_corr follows bit_errors' rules; ValueError for a
+    non-finite sample and for |(v + 1) / 2| >= 32768; integer-valued heads are searched in exact integers (ties: smallest k, first lag)."""
+    count, c = _bep("qpsk_bep", _ffi.SYM_QPSK, False, tx_data, rx_data, n_corr, n_transient)
+    return count, c[0], c[1], c[2]
+
+
+def qpsk_bep_host(tx_data, rx_data, n_corr=1024, n_transient=0):
+    """qpsk_bep in NumPy (no GPU): the yardstick of qpsk_bep."""
+    count, c = _bep("qpsk_bep", _ffi.SYM_QPSK, True, tx_data, rx_data, n_corr, n_transient)
+    return count, c[0], c[1], c[2]
+
+
+def bpsk_bep(tx_data, rx_data, n_corr=1024, n_transient=0):
+    """S_count, S_errors = bpsk_bep(tx_data, rx_data, n_corr=1024, n_transient=0), digitalcom.py:793-846: as qpsk_bep on the real parts with the
+    sign (-1)^k; S_errors = sum(int16((tx + 1) / 2) ^ int16((rx + 1) / 2)) over the overlap, numpy.int64."""
+    count, c = _bep("bpsk_bep", _ffi.SYM_BPSK, False, tx_data, rx_data, n_corr, n_transient)
+    return count, c[0]
+
+
+def bpsk_bep_host(tx_data, rx_data, n_corr=1024, n_transient=0):
+    """bpsk_bep in NumPy (no GPU): the yardstick of bpsk_bep."""
+    count, c = _bep("bpsk_bep", _ffi.SYM_BPSK, True, tx_data, rx_data, n_corr, n_transient)
+    return count, c[0]
+
+
+def _sym_rows(name, fn, tx2d, rx2d, mode, levels, kphase, start, step):
+    counts = fn(tx2d, rx2d, mode, levels, kphase, start, step)
+    if np.any(counts[:, 3]):
+        raise ValueError("%s: %d symbols break a precondition (not finite, tx not integer-valued, or beyond int16 as (v + 1) / 2)" % (name, int(counts[:, 3].sum())))
+    tx, rx = np.asarray(tx2d), np.asarray(rx2d)
+    return min(tx.shape[1], _ffi.sym_count(rx.shape[1], start, step)), counts
+
+
+def qam_sep_rows(tx2d, rx2d, mod, kphase=0, start=0, step=1):
+    """Beyond the reference: (symbols_per_row, errors int64[nrow]) of aligned rows, no search, one launch of the fused count (csrc/symerr.hip):
+    row r's rx symbols rx2d[r, start::step], quantised to mod's levels and rotated by (1j)^kphase, against tx2d[r, :].  Mirrors bit_errors_rows."""
+    n, c = _sym_rows("qam_sep_rows", _ffi.sym_count_rows, tx2d, rx2d, _ffi.SYM_QAM, _sep_levels(mod), kphase, start, step)
+    return n, c[:, 0].copy()
+
+
+def qam_sep_rows_host(tx2d, rx2d, mod, kphase=0, start=0, step=1):
+    """qam_sep_rows in NumPy (no GPU)."""
+    n, c = _sym_rows("qam_sep_rows", _ffi.sym_count_rows_host, tx2d, rx2d, _ffi.SYM_QAM, _sep_levels(mod), kphase, start, step)
+    return n, c[:, 0].copy()
+
+
+def qpsk_bep_rows(tx2d, rx2d, kphase=0, start=0, step=1):
+    """Beyond the reference: (symbols_per_row, I_errors, Q_errors, S_errors), each int64[nrow], of aligned rows in one launch."""
+    n, c = _sym_rows("qpsk_bep_rows", _ffi.sym_count_rows, tx2d, rx2d, _ffi.SYM_QPSK, 0, kphase, start, step)
+    return n, c[:, 0].copy(), c[:, 1].copy(), c[:, 2].copy()
+
+
+def qpsk_bep_rows_host(tx2d, rx2d, kphase=0, start=0, step=1):
+    """qpsk_bep_rows in NumPy (no GPU)."""
+    n, c = _sym_rows("qpsk_bep_rows", _ffi.sym_count_rows_host, tx2d, rx2d, _ffi.SYM_QPSK, 0, kphase, start, step)
+    return n, c[:, 0].copy(), c[:, 1].copy(), c[:, 2].copy()
+
+
+def bpsk_bep_rows(tx2d, rx2d, kphase=0, start=0, step=1):
+    """Beyond the reference: (symbols_per_row, S_errors int64[nrow]) of aligned rows in one launch."""
+    n, c = _sym_rows("bpsk_bep_rows", _ffi.sym_count_rows, tx2d, rx2d, _ffi.SYM_BPSK, 0, kphase, start, step)
+    return n, c[:, 0].copy()
+
+
+def bpsk_bep_rows_host(tx2d, rx2d, kphase=0, start=0, step=1):
+    """bpsk_bep_rows in NumPy (no GPU)."""
+    n, c = _sym_rows("bpsk_bep_rows", _ffi.sym_count_rows_host, tx2d, rx2d, _ffi.SYM_BPSK, 0, kphase, start, step)
+    return n, c[:, 0].copy()
