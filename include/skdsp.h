@@ -389,6 +389,26 @@ int skdsp_sym_count_rows(const void *tx, int tx_dtype, int64_t tx_stride, int64_
 int skdsp_sym_count_rows_dev(const void *tx_dev, int tx_dtype, int64_t tx_stride, int64_t t0, const void *x_dev, int x_dtype, int64_t x_stride, int64_t start,
                              int64_t step, int64_t r0, int64_t n, int64_t nrow, int mode, int levels, int kphase, int64_t *counts_dev);
 
+/* Pulse shaping and matched filtering over the rows of a frame set (csrc/pulse.hip, csrc/pulse_core.hpp): the two filtering stages of a single-carrier
+ * BER loop, every row a frame that starts from rest.  b: ntaps real float64 taps; dtype: the signal's (any of the four).
+ *   pulse_shape_rows:  y[r, k ns + p] = c * sum_j b[p + j ns] x[r, k - j] (0 <= p < ns, 0 <= k < n, every j with p + j ns < ntaps) -- per row
+ *                      lfilter(b, 1, upsample(x, ns)), n ns outputs.  scale: null, or a HOST pointer to the real factor c (one float64 multiplication per
+ *                      component behind the sum).
+ *   pulse_mf_rows:     y[r, k] = sum_i b[i] x[r, start + k step - i], 0 <= k < n_out = max(0, ceil((n - start) / step)) (skdsp_pulse_mf_out_len) -- per
+ *                      row lfilter(b, 1, x)[start::step]; step = 1 is a plain from-rest FIR over the rows.
+ * One arithmetic recipe for every dtype: elements widened exactly, float64 products and sums without fused multiply-adds, the terms of an output added
+ * from the oldest sample to the newest (acc = b x + acc from +0), real and imaginary parts apart, one rounding at the store -- identical from run to run
+ * and to the NumPy restatements of the Python layer.  _dev forms: x_stride / y_stride elements between rows as in skdsp_fir_filter_rows_dev; host forms:
+ * rows contiguous.  SKDSP_ERR_BADARG unless x_stride >= n and y_stride >= the output row length, and where input and output overlap (in place is not
+ * supported); SKDSP_ERR_UNSUPPORTED outside 1 <= ns, step <= 64 and ntaps <= 2049.  n = 0 and nrow = 0 are valid and launch nothing.  The handle is
+ * freed by skdsp_destroy. */
+int skdsp_pulse_create(const double *b, int ntaps, int dtype, skdsp_handle *out);
+int skdsp_pulse_mf_out_len(int64_t n, int64_t start, int64_t step, int64_t *n_out);
+int skdsp_pulse_shape_rows(skdsp_handle h, const void *x, int64_t n, int64_t nrow, int ns, const double *scale, void *y);
+int skdsp_pulse_shape_rows_dev(skdsp_handle h, const void *x_dev, int64_t n, int64_t nrow, int64_t x_stride, int ns, const double *scale, void *y_dev, int64_t y_stride);
+int skdsp_pulse_mf_rows(skdsp_handle h, const void *x, int64_t n, int64_t nrow, int64_t start, int64_t step, void *y);
+int skdsp_pulse_mf_rows_dev(skdsp_handle h, const void *x_dev, int64_t n, int64_t nrow, int64_t x_stride, int64_t start, int64_t step, void *y_dev, int64_t y_stride);
+
 /* Host-pointer entry points of a float32/complex64 handle deliver y as float64/complex128 (the
  * reference's result dtype, multirate_helper.py:108 etc.): widened on the device before the copy
  * back, so y must hold twice the bytes.  Device-pointer (_dev) entry points are not affected. */

@@ -734,4 +734,76 @@ int skdsp_sym_count_rows(const void *tx, int tx_dtype, int64_t tx_stride, int64_
     return stage_out(counts, counts_dev, (size_t)nrow * 4 * sizeof(int64_t));
 }
 
+// ---------------------------------------------------------------- pulse shaping and matched filtering over rows (pulse.hip): sigsys.pulse_shape_rows / matched_filter_rows
+int skdsp_pulse_create(const double *b, int ntaps, int dtype, skdsp_handle *out)
+{
+    SK_CHECK(out, SKDSP_ERR_BADARG, "pulse_create: null out");
+    HandleBase *h = nullptr;
+    int rc = pulse_create(b, ntaps, dtype, &h);   // (no device: the taps are uploaded by the first launch)
+    if (rc) return rc;
+    *out = h;
+    return SKDSP_OK;
+}
+
+int skdsp_pulse_mf_out_len(int64_t n, int64_t start, int64_t step, int64_t *n_out) { return pulse_mf_out_len(n, start, step, n_out); }
+
+int skdsp_pulse_shape_rows_dev(skdsp_handle hh, const void *x_dev, int64_t n, int64_t nrow, int64_t x_stride, int ns, const double *scale, void *y_dev, int64_t y_stride)
+{
+    HandleBase *h = as_handle<HandleBase>(hh, H_PULSE);
+    SK_CHECK(h, SKDSP_ERR_BADARG, "pulse_shape: not a pulse handle");
+    int rc = pulse_shape_check(h, n, nrow, ns, x_stride, y_stride);   // (argument errors need no device)
+    if (rc || n == 0 || nrow == 0) return rc;
+    SK_CHECK(x_dev && y_dev, SKDSP_ERR_BADARG, "pulse_shape: null pointer");
+    API_BEGIN;
+    return pulse_shape_launch(h, x_dev, n, nrow, ns, x_stride, y_stride, scale != nullptr, scale ? *scale : 1.0, y_dev, ctx().stream);
+}
+
+// host form: rows contiguous in x (n each) and in y (n ns each)
+int skdsp_pulse_shape_rows(skdsp_handle hh, const void *x, int64_t n, int64_t nrow, int ns, const double *scale, void *y)
+{
+    HandleBase *h = as_handle<HandleBase>(hh, H_PULSE);
+    SK_CHECK(h, SKDSP_ERR_BADARG, "pulse_shape: not a pulse handle");
+    int rc = pulse_shape_check(h, n, nrow, ns, n, n * ns);
+    if (rc || n == 0 || nrow == 0) return rc;
+    SK_CHECK(x && y, SKDSP_ERR_BADARG, "pulse_shape: null pointer");
+    API_BEGIN;
+    const size_t esz = dtype_size(h->dtype), y_bytes = (size_t)n * (size_t)ns * (size_t)nrow * esz;
+    void *x_dev = nullptr, *y_dev = nullptr;
+    if ((rc = ws_reserve(1, y_bytes + 256, &y_dev))) return rc;
+    if ((rc = stage_in(x, (size_t)n * (size_t)nrow * esz, &x_dev))) return rc;
+    if ((rc = pulse_shape_launch(h, x_dev, n, nrow, ns, n, n * ns, scale != nullptr, scale ? *scale : 1.0, y_dev, ctx().stream))) return rc;
+    return stage_out(y, y_dev, y_bytes);
+}
+
+int skdsp_pulse_mf_rows_dev(skdsp_handle hh, const void *x_dev, int64_t n, int64_t nrow, int64_t x_stride, int64_t start, int64_t step, void *y_dev, int64_t y_stride)
+{
+    HandleBase *h = as_handle<HandleBase>(hh, H_PULSE);
+    SK_CHECK(h, SKDSP_ERR_BADARG, "pulse_mf: not a pulse handle");
+    int rc = pulse_mf_check(h, n, nrow, start, step, x_stride, y_stride);   // (argument errors need no device)
+    if (rc || nrow == 0 || n <= start) return rc;
+    SK_CHECK(x_dev && y_dev, SKDSP_ERR_BADARG, "pulse_mf: null pointer");
+    API_BEGIN;
+    return pulse_mf_launch(h, x_dev, n, nrow, start, step, x_stride, y_stride, y_dev, ctx().stream);
+}
+
+// host form: rows contiguous in x (n each) and in y (skdsp_pulse_mf_out_len each)
+int skdsp_pulse_mf_rows(skdsp_handle hh, const void *x, int64_t n, int64_t nrow, int64_t start, int64_t step, void *y)
+{
+    HandleBase *h = as_handle<HandleBase>(hh, H_PULSE);
+    SK_CHECK(h, SKDSP_ERR_BADARG, "pulse_mf: not a pulse handle");
+    int64_t n_out = 0;
+    int rc = step >= 1 && step <= 64 ? pulse_mf_out_len(n, start, step, &n_out) : SKDSP_OK;   // (a step the kernel does not take: the check below says so)
+    if (rc) return rc;
+    rc = pulse_mf_check(h, n, nrow, start, step, n, n_out);
+    if (rc || nrow == 0 || n_out == 0) return rc;
+    SK_CHECK(x && y, SKDSP_ERR_BADARG, "pulse_mf: null pointer");
+    API_BEGIN;
+    const size_t esz = dtype_size(h->dtype), y_bytes = (size_t)n_out * (size_t)nrow * esz;
+    void *x_dev = nullptr, *y_dev = nullptr;
+    if ((rc = ws_reserve(1, y_bytes + 256, &y_dev))) return rc;
+    if ((rc = stage_in(x, (size_t)n * (size_t)nrow * esz, &x_dev))) return rc;
+    if ((rc = pulse_mf_launch(h, x_dev, n, nrow, start, step, n, n_out, y_dev, ctx().stream))) return rc;
+    return stage_out(y, y_dev, y_bytes);
+}
+
 }  // extern "C"

@@ -88,6 +88,8 @@ struct Options {
     int psd_f32_image = 0;    // the Welch primitive (psd.hip) on float32 / complex64 signals: 1 keeps the transform's LDS image in float32 (each pass
                               // still computed in float64 and rounded once at its store): the 1e-6 contract only, not the per-bin one
     int host_multi_slot = 1;  // 0: host-pointer FIR calls stay on the caller's slot even when several are bound
+    int pulse_mf_variant = 0; // the matched filter over rows (pulse.hip), A/B switch for timing only: 1 stages its window in its natural order (the naive
+                              // layout: lanes read `step` apart), 2 contracts each product and sum into one fused multiply-add (NOT the host form's bits)
 };
 Options &opt();
 
@@ -141,7 +143,7 @@ inline bool dtype_valid(int dt) { return dt >= 0 && dt <= 3; }
 constexpr int64_t kHeadroomBytes = 65536;
 
 // ------------------------------------------------------------------ handles
-enum HandleKind { H_FIR = 1, H_IIR = 2, H_FIRBANK = 3, H_VITERBI = 4, H_BLOCKCODE = 5, H_CONVCODE = 6 };
+enum HandleKind { H_FIR = 1, H_IIR = 2, H_FIRBANK = 3, H_VITERBI = 4, H_BLOCKCODE = 5, H_CONVCODE = 6, H_PULSE = 7 };
 
 struct HandleBase {
     int kind;
@@ -407,5 +409,17 @@ int symcount_check(int tx_dtype, int64_t tx_stride, int64_t t0, int x_dtype, int
                    int levels, int kphase);   // host-only
 int symcount_launch(const void *tx_dev, int tx_dtype, int64_t tx_stride, int64_t t0, const void *x_dev, int x_dtype, int64_t x_stride, int64_t start, int64_t step,
                     int64_t r0, int64_t n, int64_t nrow, int mode, int levels, int kphase, int64_t *counts_dev, hipStream_t s);
+
+// ---- pulse shaping and matched filtering over rows (pulse.hip): lfilter(b, 1, upsample(s, ns)) and lfilter(b, 1, x)[start::step] per row, from rest; the plans and
+// the per-thread functions are pulse_core.hpp ----
+// The handle (a HandleBase of kind H_PULSE) owns the real float64 taps (uploaded on first use); skdsp_destroy frees it.  Strides in elements; x and y must not overlap.
+int pulse_create(const double *b, int ntaps, int dtype, HandleBase **out);                                                              // host-only
+int pulse_mf_out_len(int64_t n, int64_t start, int64_t step, int64_t *n_out);                                                            // host-only
+int pulse_shape_check(HandleBase *h, int64_t n, int64_t nrow, int64_t ns, int64_t x_stride, int64_t y_stride);                           // host-only
+int pulse_shape_launch(HandleBase *h, const void *x_dev, int64_t n, int64_t nrow, int64_t ns, int64_t x_stride, int64_t y_stride, int has_scale, double scale,
+                       void *y_dev, hipStream_t s);
+int pulse_mf_check(HandleBase *h, int64_t n, int64_t nrow, int64_t start, int64_t step, int64_t x_stride, int64_t y_stride);             // host-only
+int pulse_mf_launch(HandleBase *h, const void *x_dev, int64_t n, int64_t nrow, int64_t start, int64_t step, int64_t x_stride, int64_t y_stride, void *y_dev,
+                    hipStream_t s);
 
 }  // namespace skdsp

@@ -45,6 +45,7 @@ SYMBOLS = [
     "skdsp_awgn_rows_dev", "skdsp_awgn_bits_rows_dev", "skdsp_awgn_sigma_rows_dev", "skdsp_random_bits_rows_dev", "skdsp_pn_rows_dev",
     "skdsp_ofdm_tx_rows", "skdsp_ofdm_tx_rows_dev", "skdsp_ofdm_rx_rows", "skdsp_ofdm_rx_rows_dev", "skdsp_ofdm_equalize_rows", "skdsp_ofdm_equalize_rows_dev",
     "skdsp_lag_corr_len", "skdsp_lag_corr", "skdsp_lag_corr_dev", "skdsp_sym_count_rows", "skdsp_sym_count_rows_dev",
+    "skdsp_pulse_create", "skdsp_pulse_mf_out_len", "skdsp_pulse_shape_rows", "skdsp_pulse_shape_rows_dev", "skdsp_pulse_mf_rows", "skdsp_pulse_mf_rows_dev",
     "skdsp_dist_unique_id", "skdsp_dist_init", "skdsp_dist_shutdown", "skdsp_dist_comm_count", "skdsp_dist_barrier",
     "skdsp_dist_allreduce_max", "skdsp_dist_allreduce_sum", "skdsp_dist_sendrecv", "skdsp_dist_allgather", "skdsp_dist_halo_exchange", "skdsp_fir_filter_shard_dev",
 ]
@@ -196,6 +197,14 @@ def load():
             L.skdsp_lag_corr.argtypes = [vp, ci, vp, ci, i64, i64, ci, vp, vp, vp]
             L.skdsp_lag_corr_dev.argtypes = [vp, ci, vp, ci, i64, i64, ci, vp, vp]
             L.skdsp_sym_count_rows.argtypes = L.skdsp_sym_count_rows_dev.argtypes = [vp, ci, i64, i64, vp, ci, i64, i64, i64, i64, i64, i64, ci, ci, ci, vp]
+        if hasattr(L, "skdsp_pulse_create"):
+            pd = ctypes.POINTER(ctypes.c_double)
+            L.skdsp_pulse_create.argtypes = [vp, ci, ci, pvp]
+            L.skdsp_pulse_mf_out_len.argtypes = [i64, i64, i64, p64]
+            L.skdsp_pulse_shape_rows.argtypes = [vp, vp, i64, i64, ci, pd, vp]
+            L.skdsp_pulse_shape_rows_dev.argtypes = [vp, vp, i64, i64, i64, ci, pd, vp, i64]
+            L.skdsp_pulse_mf_rows.argtypes = [vp, vp, i64, i64, i64, i64, vp]
+            L.skdsp_pulse_mf_rows_dev.argtypes = [vp, vp, i64, i64, i64, i64, i64, vp, i64]
         L.skdsp_dist_unique_id.argtypes = [vp]
         L.skdsp_dist_init.argtypes = [ci, ci, vp]
         L.skdsp_dist_comm_count.argtypes = [ctypes.POINTER(ci)]
@@ -931,6 +940,20 @@ def gray_table(kind, mod, dtype=np.complex128):
     return np.ascontiguousarray(pts.real), np.ascontiguousarray(pts.imag)
 
 
+def gray_levels(kind, mod, dtype=np.complex128):
+    """((tab_re, tab_im), scale): the points as the *_gray_encode_bb transmitters hold them BEFORE pulse shaping -- QAM of 4 points and more: the
+    integer levels 2 lut - x_m, which the transmitter divides by x_m = sqrt(mod) - 1 behind the shaping filter (scale = 1 / x_m: NumPy divides a
+    complex array by a real scalar as a multiplication of each component by the reciprocal) -- and None where there is no scale"""
+    if kind == QAM and mod > 2:
+        bps = sym_bits(kind, mod)
+        x_m = np.sqrt(mod) - 1
+        lv = np.ascontiguousarray(2 * _bin2gray(bps // 2) - x_m, dtype=np.float64)
+        if np.dtype(dtype) not in (np.dtype(np.complex64), np.dtype(np.complex128)):
+            raise TypeError("gray_map: complex64 or complex128 symbols (got %s)" % np.dtype(dtype))
+        return (lv, np.zeros_like(lv)), (None if x_m == 1 else float(1.0 / x_m))
+    return gray_table(kind, mod, dtype), None
+
+
 def _bin2gray(width):
     """the reference's bin2gray tables: entry k is the running XOR of k's bits from the MSB down"""
     v = np.arange(2 ** width)
@@ -982,13 +1005,13 @@ def gray_map_rows(bits, kind, mod, dtype=np.complex128):
     return y
 
 
-def gray_map_rows_host(bits, kind, mod, dtype=np.complex128):
-    """gray_map_rows in NumPy (no GPU): the same table, looked up by the MSB-first words -- the yardstick of the kernel."""
+def gray_map_rows_host(bits, kind, mod, dtype=np.complex128, table=None):
+    """gray_map_rows in NumPy (no GPU): the same table (or `table`, as gray_levels returns it), looked up by the MSB-first words -- the yardstick of the kernel."""
     bps = sym_bits(kind, mod)
     bits = np.asarray(bits)
     n = bits.shape[1] // bps
     words = (bits[:, :n * bps].reshape(bits.shape[0], n, bps).astype(np.int64) & 1) @ (2 ** np.arange(bps - 1, -1, -1))
-    tre, tim = gray_table(kind, mod, dtype)
+    tre, tim = gray_table(kind, mod, dtype) if table is None else table
     y = np.empty(words.shape, dtype=np.complex128)
     if kind == QAM and mod > 2:
         half = bps // 2
@@ -998,9 +1021,10 @@ def gray_map_rows_host(bits, kind, mod, dtype=np.complex128):
     return y.astype(dtype)
 
 
-def gray_map_rows_dev(bits_ptr, bits_stride, n, nrow, kind, mod, dtype, y_ptr, y_stride=None):
-    """Device pointers: n symbols per row from bps n bytes; bits_stride in bytes, y_stride in elements (default n)."""
-    tre, tim = gray_table(kind, mod, dtype)
+def gray_map_rows_dev(bits_ptr, bits_stride, n, nrow, kind, mod, dtype, y_ptr, y_stride=None, table=None):
+    """Device pointers: n symbols per row from bps n bytes; bits_stride in bytes, y_stride in elements (default n); table: (tab_re, tab_im) in place
+    of gray_table's (gray_levels: the points before the transmitter's scale)."""
+    tre, tim = gray_table(kind, mod, dtype) if table is None else table
     check(load().skdsp_gray_map_rows_dev(ctypes.c_void_p(bits_ptr), int(bits_stride), int(n), int(nrow), kind, mod, _ptr(tre), _ptr(tim), tre.size, code_of(dtype),
                                          ctypes.c_void_p(y_ptr), int(n if y_stride is None else y_stride)))
 
@@ -1471,6 +1495,147 @@ def sym_count_rows_dev(tx, tx_dtype, tx_stride, t0, x, x_dtype, x_stride, start,
     """Device-resident form: tx / x / counts are DeviceArray / DeviceBytes or pointers; counts receives nrow x int64[4] (zeroed by the call)"""
     check(load().skdsp_sym_count_rows_dev(_dp(tx), code_of(tx_dtype), int(tx_stride), int(t0), _dp(x), code_of(x_dtype), int(x_stride), int(start), int(step), int(r0),
                                           int(n), int(nrow), int(mode), int(levels), int(kphase), _dp(counts)))
+
+
+# --------------------------------------------------------------------------
+# Pulse shaping and matched filtering over frame sets (csrc/pulse.hip): the two filtering stages of a single-carrier BER loop
+# --------------------------------------------------------------------------
+PULSE_MAX_TAPS, PULSE_MAX_RATE = 2049, 64
+
+
+def pulse_served(ntaps, rate):
+    """does the kernel pair take this filter length and this ns / step?  (outside: the C calls return SKDSP_ERR_UNSUPPORTED)"""
+    return 1 <= int(ntaps) <= PULSE_MAX_TAPS and 1 <= int(rate) <= PULSE_MAX_RATE
+
+
+def _pulse_taps(b):
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    if b.ndim != 1 or b.size < 1:
+        raise ValueError("pulse: b must be a one-dimensional array of at least one real tap")
+    return b
+
+
+def _pulse_rows(x2d, what):
+    x = _stream(x2d, what)
+    if x.ndim != 2:
+        raise ValueError("%s: a 2-D array, one frame per row" % what)
+    return x
+
+
+def _planes(x):
+    """the float64 components of a widened signal: [re] or [re, im]"""
+    if x.dtype.kind == "c":
+        return [np.ascontiguousarray(x.real, dtype=np.float64), np.ascontiguousarray(x.imag, dtype=np.float64)]
+    return [x.astype(np.float64)]
+
+
+def _from_planes(planes, dtype):
+    """one rounding to the output dtype"""
+    if len(planes) == 1:
+        return planes[0].astype(dtype)
+    y = np.empty(planes[0].shape, dtype=np.complex128)
+    y.real, y.imag = planes
+    return y.astype(dtype)
+
+
+def pulse_shape_rows_host(x2d, b, ns, scale=None):
+    """PulseKernel.shape_rows in NumPy (no GPU), the kernel's arithmetic operation for operation: per row lfilter(b, 1, upsample(x, ns)) with float64
+    products and sums, acc = b x + acc from the oldest symbol to the newest and from +0, real and imaginary parts apart, the optional factor once behind
+    the sum, one rounding to x's dtype.  Vectorised over rows, symbols and phases; the loop runs over the taps of a phase."""
+    x, b, ns = _pulse_rows(x2d, "pulse_shape_rows"), _pulse_taps(b), int(ns)
+    if ns < 1:
+        raise ValueError("pulse_shape_rows: need ns >= 1")
+    nrow, n = x.shape
+    J = -(-b.size // ns)
+    H = J - 1
+    out = []
+    for s in _planes(x):
+        sp = np.zeros((nrow, H + n), dtype=np.float64)
+        sp[:, H:] = s
+        acc = np.zeros((nrow, n, ns), dtype=np.float64)
+        for j in range(J - 1, -1, -1):
+            pm = min(ns, b.size - j * ns)          # the phases that have a tap j
+            prod = b[j * ns:j * ns + pm][None, None, :] * sp[:, H - j:H - j + n, None]
+            acc[:, :, :pm] = prod + acc[:, :, :pm]
+        if scale is not None:
+            acc = acc * np.float64(scale)
+        out.append(acc.reshape(nrow, n * ns))
+    return _from_planes(out, x.dtype)
+
+
+def pulse_mf_rows_host(x2d, b, start=0, step=1):
+    """PulseKernel.mf_rows in NumPy (no GPU), the kernel's arithmetic operation for operation: per row lfilter(b, 1, x)[start::step], acc = b x + acc from
+    the oldest sample to the newest.  Vectorised over rows and outputs; the loop runs over the taps."""
+    x, b, start, step = _pulse_rows(x2d, "matched_filter_rows"), _pulse_taps(b), int(start), int(step)
+    nrow, n = x.shape
+    n_out = sym_count(n, start, step)
+    P = b.size
+    out = []
+    for s in _planes(x):
+        xp = np.zeros((nrow, P - 1 + n), dtype=np.float64)
+        xp[:, P - 1:] = s
+        acc = np.zeros((nrow, n_out), dtype=np.float64)
+        for i in range(P - 1, -1, -1):
+            prod = b[i] * xp[:, start + P - 1 - i::step][:, :n_out]
+            acc = prod + acc
+        out.append(acc)
+    return _from_planes(out, x.dtype)
+
+
+class PulseKernel:
+    """A pulse handle (csrc/pulse.hip) for one (real taps, signal dtype) pair: shaping and the decimating matched filter over the rows of a frame set,
+    every row from rest, in the one arithmetic recipe pulse_shape_rows_host / pulse_mf_rows_host restate.  Creating it needs no device."""
+
+    def __init__(self, b, dtype):
+        b = _pulse_taps(b)
+        self.ntaps, self.dtype, self.code = int(b.size), np.dtype(dtype), code_of(dtype)
+        h = ctypes.c_void_p(0)
+        check(load().skdsp_pulse_create(_ptr(b), self.ntaps, self.code, ctypes.byref(h)))
+        self.h = h.value
+        self._fin = weakref.finalize(self, _destroy, self.h)
+
+    @staticmethod
+    def mf_out_len(n, start=0, step=1):
+        v = ctypes.c_int64(0)
+        check(load().skdsp_pulse_mf_out_len(int(n), int(start), int(step), ctypes.byref(v)))
+        return v.value
+
+    @staticmethod
+    def _scale(scale):
+        return None if scale is None else ctypes.byref(ctypes.c_double(float(scale)))
+
+    def _rows(self, x2d, what):
+        x = _pulse_rows(x2d, what)
+        if x.dtype != self.dtype:
+            raise TypeError("%s: the handle was made for %s signals (got %s)" % (what, self.dtype, x.dtype))
+        return x
+
+    # host arrays -------------------------------------------------------
+    def shape_rows(self, x2d, ns, scale=None):
+        """(nrow, n) -> (nrow, n ns) of the same dtype"""
+        x = self._rows(x2d, "pulse_shape_rows")
+        y = np.empty((x.shape[0], x.shape[1] * int(ns)), dtype=x.dtype)
+        check(load().skdsp_pulse_shape_rows(ctypes.c_void_p(self.h), _ptr(x), x.shape[1], x.shape[0], int(ns), self._scale(scale), _ptr(y)))
+        return y
+
+    def mf_rows(self, x2d, start=0, step=1):
+        """(nrow, n) -> (nrow, len(row[start::step])) of the same dtype"""
+        x = self._rows(x2d, "matched_filter_rows")
+        y = np.empty((x.shape[0], sym_count(x.shape[1], int(start), int(step))), dtype=x.dtype)
+        check(load().skdsp_pulse_mf_rows(ctypes.c_void_p(self.h), _ptr(x), x.shape[1], x.shape[0], int(start), int(step), _ptr(y)))
+        return y
+
+    # device arrays -----------------------------------------------------
+    def shape_rows_dev(self, xd, yd, n, nrow, ns, scale=None, x_stride=None, y_stride=None):
+        """xd, yd: DeviceArrays or addresses of the handle's dtype; strides in elements (default n and n ns); the two must not overlap"""
+        check(load().skdsp_pulse_shape_rows_dev(ctypes.c_void_p(self.h), _dp(xd), int(n), int(nrow), int(n if x_stride is None else x_stride), int(ns),
+                                                self._scale(scale), _dp(yd), int(n * ns if y_stride is None else y_stride)))
+
+    def mf_rows_dev(self, xd, yd, n, nrow, start=0, step=1, x_stride=None, y_stride=None):
+        """strides in elements (default n and the output row length); the two must not overlap"""
+        n_out = sym_count(int(n), int(start), int(step))
+        check(load().skdsp_pulse_mf_rows_dev(ctypes.c_void_p(self.h), _dp(xd), int(n), int(nrow), int(n if x_stride is None else x_stride), int(start), int(step),
+                                             _dp(yd), int(n_out if y_stride is None else y_stride)))
 
 
 def device_bytes_of(a):

@@ -27,7 +27,7 @@ from . import _ffi, config
 
 log = getLogger(__name__)
 
-from .sigsys import upsample, downsample, cic, rc_imp, sqrt_rc_imp, pulse_shape, _pulse  # noqa: F401  (re-exported like digitalcom.py:40-47)
+from .sigsys import upsample, downsample, cic, rc_imp, sqrt_rc_imp, pulse_shape, _pulse, pulse_shape_rows, matched_filter_rows  # noqa: F401  (re-exported like digitalcom.py:40-47)
 
 
 def _farrow_len(n, Ts_old, Ts_new):
@@ -315,6 +315,71 @@ def qam_gray_map_rows(bits2d, mod=4, dtype=np.complex128):
 def mpsk_gray_map_rows(bits2d, mod=4, dtype=np.complex128):
     """Beyond the reference: the symbol sequence mpsk_gray_encode_bb builds before shaping (x_IQ), as qam_gray_map_rows."""
     return _map_rows(_ffi.MPSK, bits2d, mod, dtype, "mpsk_gray_map_rows")
+
+
+# ---- the Gray transmitters over frame sets: mapping and pulse shaping on the device (csrc/symmap.hip, csrc/pulse.hip, DESIGN.md 4.21) ----
+def _encode_rows_args(kind, bits2d, ns, mod, pulse, alpha, m_span, dtype, name):
+    """(bits uint8 (nrow, n bps), n, taps, returned b): the checks of the 1-D transmitters in their order and with their messages"""
+    bps = _ffi.sym_bits(kind, mod)
+    bits = np.asarray(bits2d)
+    if bits.ndim != 2:
+        raise ValueError("%s: a 2-D array of bits, one frame per row" % name)
+    if bits.size and np.any((bits != 0) & (bits != 1)):
+        raise ValueError("%s: bits 0 / 1 only" % name)
+    if np.dtype(dtype) not in (np.dtype(np.complex64), np.dtype(np.complex128)):
+        raise TypeError("%s: dtype must be complex64 or complex128" % name)
+    if int(ns) != ns or ns < 1:
+        raise ValueError("%s: ns must be a positive integer" % name)
+    n = bits.shape[1] // bps
+    bits = np.ascontiguousarray(bits[:, :n * bps], dtype=np.uint8)
+    if ns > 1:
+        taps = _pulse(pulse, int(ns), alpha, m_span, err='pulse shape must be src, rc, or rect')
+        return bits, n, np.ascontiguousarray(taps, dtype=np.float64), taps / sum(taps)
+    return bits, n, np.ones(1), 1
+
+
+def _encode_rows(kind, bits2d, ns, mod, pulse, alpha, m_span, dtype, name, host):
+    bits, n, taps, b = _encode_rows_args(kind, bits2d, ns, mod, pulse, alpha, m_span, dtype, name)
+    ns, dtype, nrow = int(ns), np.dtype(dtype), bits.shape[0]
+    table, scale = _ffi.gray_levels(kind, mod, dtype)
+    if host or not _ffi.pulse_served(taps.size, ns):
+        sym = _ffi.gray_map_rows_host(bits, kind, mod, dtype, table=table)
+        return (_ffi.pulse_shape_rows_host if host else pulse_shape_rows)(sym, taps, ns, scale), b
+    if nrow == 0 or n == 0:
+        return np.zeros((nrow, n * ns), dtype=dtype), b
+    bd, sd, yd = _ffi.device_bytes_of(bits), _ffi.DeviceArray(nrow * n, dtype), _ffi.DeviceArray(nrow * n * ns, dtype)
+    try:   # bits -> points -> waveform, nothing on the host in between
+        _ffi.gray_map_rows_dev(bd.ptr, bits.shape[1], n, nrow, kind, mod, dtype, sd.ptr, table=table)
+        _ffi.PulseKernel(taps, dtype).shape_rows_dev(sd, yd, n, nrow, ns, scale)
+        return yd.to_host().reshape(nrow, n * ns), b
+    finally:
+        for d in (bd, sd, yd):
+            d.free()
+
+
+def qam_gray_encode_bb_rows(bits2d, ns, mod=4, pulse='rect', alpha=0.35, m_span=6, dtype=np.complex128):
+    """Beyond the reference: qam_gray_encode_bb(None, ns, mod, pulse, alpha, m_span, ext_data=row) for every row of bits2d at once, on the device:
+    the Gray mapping kernel (the integer levels 2 lut - x_m), then the shaping kernel with the factor 1 / x_m behind its sum, with no host data in
+    between.  Returns (x2d, b): x2d (nrow, n_symb ns) of `dtype`, always complex (mod 2: imaginary part 0); b the reference's unity-gain
+    b / sum(b), or 1 for ns == 1.  Trailing bits that do not fill a symbol are dropped.  Each row lies within the summation-order bound of the
+    reference and equals qam_gray_encode_bb_rows_host bit for bit."""
+    return _encode_rows(_ffi.QAM, bits2d, ns, mod, pulse, alpha, m_span, dtype, "qam_gray_encode_bb_rows", False)
+
+
+def qam_gray_encode_bb_rows_host(bits2d, ns, mod=4, pulse='rect', alpha=0.35, m_span=6, dtype=np.complex128):
+    """qam_gray_encode_bb_rows in NumPy (no GPU): gray_map_rows_host on the same levels, then pulse_shape_rows_host with the same factor."""
+    return _encode_rows(_ffi.QAM, bits2d, ns, mod, pulse, alpha, m_span, dtype, "qam_gray_encode_bb_rows", True)
+
+
+def mpsk_gray_encode_bb_rows(bits2d, ns, mod=4, pulse='rect', alpha=0.35, m_span=6, dtype=np.complex128):
+    """Beyond the reference: mpsk_gray_encode_bb(None, ns, mod, pulse, alpha, m_span, ext_data=row) for every row of bits2d at once, as
+    qam_gray_encode_bb_rows (there is no scale: the points lie on the unit circle)."""
+    return _encode_rows(_ffi.MPSK, bits2d, ns, mod, pulse, alpha, m_span, dtype, "mpsk_gray_encode_bb_rows", False)
+
+
+def mpsk_gray_encode_bb_rows_host(bits2d, ns, mod=4, pulse='rect', alpha=0.35, m_span=6, dtype=np.complex128):
+    """mpsk_gray_encode_bb_rows in NumPy (no GPU)."""
+    return _encode_rows(_ffi.MPSK, bits2d, ns, mod, pulse, alpha, m_span, dtype, "mpsk_gray_encode_bb_rows", True)
 
 
 # ---- the remaining lfilter(b, 1, .) callers of digitalcom.py (488, 608, 666, 1047, 1130) ------------------------------

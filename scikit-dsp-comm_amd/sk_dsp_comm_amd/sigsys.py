@@ -301,6 +301,76 @@ def pulse_shape(symbols, b, ns):
     return mrh.multirate_FIR(np.asarray(b, dtype=np.float64) / ns).up(sym.astype(np.result_type(sym.dtype, np.float64)), ns)
 
 
+# ---- shaping and matched filtering over frame sets (csrc/pulse.hip) ---------------------------------------------------
+_pulse_fallback_logged = set()
+
+
+def _pulse_fallback(name, ntaps, rate):
+    """outside the kernels' range (1 <= ns, step <= 64, at most 2049 taps) the existing engines run; said once per function"""
+    if name not in _pulse_fallback_logged:
+        _pulse_fallback_logged.add(name)
+        log.info("%s: %d taps at rate %d is outside the row kernels' range (rate 1 ... %d, at most %d taps): the FIR engines run instead",
+                 name, ntaps, rate, _ffi.PULSE_MAX_RATE, _ffi.PULSE_MAX_TAPS)
+
+
+def _pulse_args(x2d, b, rate, name, rate_name):
+    x = _ffi._pulse_rows(x2d, name)
+    b = _ffi._pulse_taps(b)
+    if int(rate) != rate or rate < 1:
+        raise ValueError("%s: %s must be a positive integer" % (name, rate_name))
+    return x, b, int(rate)
+
+
+def pulse_shape_rows(sym2d, b, ns, scale=None):
+    """Beyond the reference: pulse_shape of every row of sym2d -- scale * lfilter(b, 1, upsample(row, ns)), each row a frame from rest -- in one
+    launch (csrc/pulse.hip: pulse_shape_rows_kernel).  b: real taps; rows float32 / complex64 / float64 / complex128 (integers run as float64),
+    returned in the same dtype, (nrow, n ns).  scale: None or a real factor applied once behind the sum (the x / x_m of qam_gray_encode_bb, which
+    NumPy computes as a multiplication by 1 / x_m).  The result equals pulse_shape_rows_host bit for bit.  Outside 1 <= ns <= 64 and 2049 taps:
+    multirate_FIR.up per row (logged once at INFO), within that engine's contract."""
+    x, b, ns = _pulse_args(sym2d, b, ns, "pulse_shape_rows", "ns")
+    if x.shape[0] == 0 or x.shape[1] == 0:
+        return np.zeros((x.shape[0], x.shape[1] * ns), dtype=x.dtype)
+    if not _ffi.pulse_served(b.size, ns):
+        _pulse_fallback("pulse_shape_rows", b.size, ns)
+        y = np.stack([np.asarray(pulse_shape(row, b, ns)) for row in x])
+        return (y if scale is None else y * np.float64(scale)).astype(x.dtype)
+    return _ffi.PulseKernel(b, x.dtype).shape_rows(x, ns, scale)
+
+
+def pulse_shape_rows_host(sym2d, b, ns, scale=None):
+    """pulse_shape_rows in NumPy (no GPU): the kernel's arithmetic operation for operation (_ffi.pulse_shape_rows_host), the same bits."""
+    x, b, ns = _pulse_args(sym2d, b, ns, "pulse_shape_rows", "ns")
+    return _ffi.pulse_shape_rows_host(x, b, ns, scale)
+
+
+def matched_filter_rows(x2d, b, start=0, step=1):
+    """Beyond the reference: lfilter(b, 1, row)[start::step] of every row of x2d, each row a frame from rest, in one launch that computes only the
+    outputs it keeps (csrc/pulse.hip: pulse_mf_rows_kernel); step = 1 is a plain FIR over the rows.  Same dtypes as pulse_shape_rows; the result,
+    (nrow, len(row[start::step])), equals matched_filter_rows_host bit for bit.  Outside 1 <= step <= 64 and 2049 taps: multirate_FIR.filter over
+    the rows and a slice (logged once at INFO), within that engine's contract."""
+    x, b, step = _pulse_args(x2d, b, step, "matched_filter_rows", "step")
+    if int(start) != start or start < 0:
+        raise ValueError("matched_filter_rows: start must be a non-negative integer")
+    start = int(start)
+    n_out = _ffi.sym_count(x.shape[1], start, step)
+    if x.shape[0] == 0 or n_out == 0:
+        return np.zeros((x.shape[0], n_out), dtype=x.dtype)
+    if not _ffi.pulse_served(b.size, step):
+        from . import multirate_helper as mrh
+        _pulse_fallback("matched_filter_rows", b.size, step)
+        y = np.asarray(mrh.multirate_FIR(b).filter(x))
+        return np.ascontiguousarray(y[:, start::step]).astype(x.dtype)
+    return _ffi.PulseKernel(b, x.dtype).mf_rows(x, start, step)
+
+
+def matched_filter_rows_host(x2d, b, start=0, step=1):
+    """matched_filter_rows in NumPy (no GPU): the kernel's arithmetic operation for operation (_ffi.pulse_mf_rows_host), the same bits."""
+    x, b, step = _pulse_args(x2d, b, step, "matched_filter_rows", "step")
+    if int(start) != start or start < 0:
+        raise ValueError("matched_filter_rows: start must be a non-negative integer")
+    return _ffi.pulse_mf_rows_host(x, b, int(start), step)
+
+
 def nrz_bits2(data, Ns, pulse='rect', alpha=0.25, M=6):
     """NRZ +-1 waveform from user bits with pulse shaping (sigsys.py:2163-2211): (x, b/Ns)."""
     data = np.asarray(data)
