@@ -2,6 +2,7 @@
 // No kernel unit includes this header.
 #pragma once
 #include "skdsp_internal.hpp"
+#include "stage_plan.hpp"
 #include <algorithm>
 
 namespace skdsp {
@@ -27,9 +28,13 @@ static inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; 
 int sync_checked();   // stream sync of the calling slot + the deferred failures of what ran on it
 
 // ---- host_pipe.hip ----------------------------------------------------------------------------------------------
-// a host vector into workspace slot 0 behind kHeadroomBytes of headroom / a result back (widened on the device for a wide_out handle), then sync_checked
-int stage_in(const void *x_host, size_t bytes, void **x_dev);
-int stage_out(void *y_host, const void *y_dev, size_t bytes, const HandleBase *h = nullptr);
+// the staging of a host-pointer call (stage_plan.hpp has the rules).  stage_begin: every workspace slot reserved once with its summed size, the
+// host-to-device copies issued.  stage_finish: the device-to-host copies (float32 / complex64 results widened on the device for a wide_out
+// handle), then the call's one sync_checked -- also with nothing to copy back.  launch_rc: what the launch between the two returned; a failure
+// is handed back as it is
+static_assert(kStageHeadroom == (size_t)kHeadroomBytes, "stage_plan.hpp keeps the primary input behind the same headroom");
+int stage_begin(StagePlan &p);
+int stage_finish(const StagePlan &p, int launch_rc, const HandleBase *h = nullptr);
 void pipe_free(Context &c);   // the slot's chunk pipeline state (skdsp_shutdown)
 
 // how a long vector is cut: chunk k covers inputs [k C, min((k+1) C, n)) and outputs [(k C L) / M, (end L) / M)

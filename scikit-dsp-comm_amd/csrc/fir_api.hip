@@ -309,15 +309,15 @@ static int fir_host_call(skdsp_handle hh, const void *x, int64_t n, int L, int M
         jobs.home = FirChunkJob{h, mode, L, M};
         return run_on_slots(p, (const char *)x, (char *)y, fir_chunk_kernel, fir_job_on_slot, &jobs, true, max_slots);
     }
-    void *x_dev = nullptr, *y_dev = nullptr;
-    int rc = stage_in(x, (size_t)n * esz, &x_dev);
+    StagePlan p;
+    p.input(x, (size_t)n * esz);
+    const int iy = p.add_out(y, (size_t)n_out * esz);
+    int rc = stage_begin(p);
     if (rc) return rc;
-    if ((rc = ws_reserve(1, (size_t)n_out * esz + 256, &y_dev))) return rc;
-    if (mode == 0) rc = fir_filter_any(h, x_dev, n, 0, y_dev);
-    else if (L == 1) rc = fir_dn_any(h, x_dev, n, 0, M, y_dev);
-    else rc = fir_updn_any(h, x_dev, n, 0, L, M, y_dev);
-    if (rc) return rc;
-    return stage_out(y, y_dev, (size_t)n_out * esz, h);
+    if (mode == 0) rc = fir_filter_any(h, p.in_dev(), n, 0, p.dev(iy));
+    else if (L == 1) rc = fir_dn_any(h, p.in_dev(), n, 0, M, p.dev(iy));
+    else rc = fir_updn_any(h, p.in_dev(), n, 0, L, M, p.dev(iy));
+    return stage_finish(p, rc, h);
 }
 
 // ---- N-D inputs: rows of one launch ---------------------------------------------------------------------------------

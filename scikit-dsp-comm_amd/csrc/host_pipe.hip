@@ -7,29 +7,41 @@
 
 namespace skdsp {
 
-// Stage a host vector into workspace slot 0 behind kHeadroomBytes of headroom.
-int stage_in(const void *x_host, size_t bytes, void **x_dev)
+// The staging of a host-pointer call (stage_plan.hpp): the primary input into workspace 0 behind the headroom, the further pieces into
+// workspace 1, the scratch in workspace 3 -- each slot reserved once, before any pointer into it is used.
+int stage_begin(StagePlan &p)
 {
-    void *base = nullptr;
-    int rc = ws_reserve(0, kHeadroomBytes + round_up(bytes, 256) + 256, &base);
-    if (rc) return rc;
-    *x_dev = (char *)base + kHeadroomBytes;
-    if (bytes) SK_HIP(hipMemcpyAsync(*x_dev, x_host, bytes, hipMemcpyHostToDevice, ctx().stream));
+    SK_CHECK(!p.overflow, SKDSP_ERR_BADARG, "staging: more than %d pieces declared", StagePlan::kMaxPieces);
+    int rc = SKDSP_OK;
+    if (p.scratch_bytes && (rc = ws_reserve(3, p.scratch_bytes, &p.scratch))) return rc;
+    if (!p.host) return SKDSP_OK;
+    if ((rc = ws_reserve(0, p.total0(), &p.base0))) return rc;
+    if (p.npiece && (rc = ws_reserve(1, p.total1(), &p.base1))) return rc;
+    if (p.in_bytes) SK_HIP(hipMemcpyAsync(p.in_dev(), p.in, p.in_bytes, hipMemcpyHostToDevice, ctx().stream));
+    for (int i = 0; i < p.npiece; ++i)
+        if (p.piece[i].src && p.piece[i].bytes) SK_HIP(hipMemcpyAsync(p.dev(i), p.piece[i].src, p.piece[i].bytes, hipMemcpyHostToDevice, ctx().stream));
     return SKDSP_OK;
 }
 
-int stage_out(void *y_host, const void *y_dev, size_t bytes, const HandleBase *h)
+int stage_finish(const StagePlan &p, int launch_rc, const HandleBase *h)
 {
-    if (bytes && h && h->wide_out && !dtype_double(h->dtype)) {
-        // widen on the device (slot 0 held x, which the kernels are done with in stream order)
-        void *wide = nullptr;
-        int rc = ws_reserve(0, 2 * bytes + 256, &wide);
-        if (rc) return rc;
-        if ((rc = widen_launch(y_dev, (int64_t)(bytes / 4), wide, ctx().stream))) return rc;
-        y_dev = wide;
-        bytes *= 2;
+    if (launch_rc || !p.host) return launch_rc;
+    // a wide_out handle: widen on the device into workspace 0 (it held the input, which the kernels are done with in stream order), piece i at
+    // twice its offset -- one reserve for all of them
+    const bool widen = h && h->wide_out && !dtype_double(h->dtype);
+    void *wide = nullptr;
+    int rc = SKDSP_OK;
+    if (widen && (rc = ws_reserve(0, 2 * p.total1(), &wide))) return rc;
+    for (int i = 0; i < p.npiece; ++i) {
+        const StagePlan::Piece &q = p.piece[i];
+        if (!q.dst || !q.bytes) continue;
+        const void *from = p.dev(i);
+        if (widen) {
+            if ((rc = widen_launch(from, (int64_t)(q.bytes / 4), (char *)wide + 2 * q.off, ctx().stream))) return rc;
+            from = (char *)wide + 2 * q.off;
+        }
+        SK_HIP(hipMemcpyAsync(q.dst, from, widen ? 2 * q.bytes : q.bytes, hipMemcpyDeviceToHost, ctx().stream));
     }
-    if (bytes) SK_HIP(hipMemcpyAsync(y_host, y_dev, bytes, hipMemcpyDeviceToHost, ctx().stream));
     return sync_checked();
 }
 

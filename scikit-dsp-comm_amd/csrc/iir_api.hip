@@ -439,12 +439,12 @@ int skdsp_iir_filter_rows(skdsp_handle hh, const void *x, int64_t n, int64_t nro
     SK_CHECK(x && y, SKDSP_ERR_BADARG, "iir_filter_rows: null buffer");
     std::lock_guard<std::mutex> lk(h->mu);
     const size_t esz = dtype_size(h->dtype), bytes = (size_t)n * (size_t)nrow * esz;
-    void *x_dev = nullptr, *y_dev = nullptr;
-    int rc = stage_in(x, bytes, &x_dev);
+    StagePlan p;
+    p.input(x, bytes);
+    const int iy = p.add_out(y, bytes);
+    int rc = stage_begin(p);
     if (rc) return rc;
-    if ((rc = ws_reserve(1, bytes + 256, &y_dev))) return rc;
-    if ((rc = iir_rows_dev(h, x_dev, n, nrow, n, n, y_dev))) return rc;
-    return stage_out(y, y_dev, bytes, h);
+    return stage_finish(p, iir_rows_dev(h, p.in_dev(), n, nrow, n, n, p.dev(iy)), h);
 }
 
 int skdsp_iir_state_len(skdsp_handle hh, int *len)
@@ -517,20 +517,15 @@ static int iir_host_call(skdsp_handle hh, const void *x, int64_t n, int L, int M
         job.state.assign((size_t)(dtype_complex(h->dtype) ? 2 : 1) * h->nsec * h->order, 0.0);
         return run_on_slots(p, (const char *)x, (char *)y, iir_chunk_kernel, iir_job_on_slot, &job, false);
     }
-    void *x_dev = nullptr, *y_dev = nullptr;
-    int rc = stage_in(x, (size_t)n * esz, &x_dev);
+    StagePlan p;
+    p.input(x, (size_t)n * esz);
+    const int iy = p.add_out(y, (size_t)n_out * esz);   // (the callers pass L = 1 or M = 1: n L, n / M or n samples)
+    int rc = stage_begin(p);
     if (rc) return rc;
-    if (L > 1) {
-        if ((rc = ws_reserve(1, (size_t)n * L * esz + 256, &y_dev))) return rc;
-        if ((rc = iir_up_any(h, x_dev, n, L, y_dev))) return rc;
-    } else if (M > 1) {
-        if ((rc = ws_reserve(1, (size_t)n_out * esz + 256, &y_dev))) return rc;
-        if ((rc = iir_dn_any(h, x_dev, n, M, y_dev))) return rc;  // K3 stores every M-th output itself
-    } else {
-        if ((rc = ws_reserve(1, (size_t)n * esz + 256, &y_dev))) return rc;
-        if ((rc = iir_any_dev(h, x_dev, n, y_dev))) return rc;
-    }
-    return stage_out(y, y_dev, (size_t)n_out * esz, h);
+    if (L > 1) rc = iir_up_any(h, p.in_dev(), n, L, p.dev(iy));
+    else if (M > 1) rc = iir_dn_any(h, p.in_dev(), n, M, p.dev(iy));  // K3 stores every M-th output itself
+    else rc = iir_any_dev(h, p.in_dev(), n, p.dev(iy));
+    return stage_finish(p, rc, h);
 }
 
 int skdsp_iir_filter(skdsp_handle h, const void *x, int64_t n, void *y) { return iir_host_call(h, x, n, 1, 1, y); }

@@ -162,3 +162,18 @@ def test_narrow_dtypes_and_determinism():
     assert rel_err(y1, farrow_restated(x, 48000, 44100))[0] <= 1e-6
     w1 = dc.farrow_resample(x, 48000, 44100)
     assert w1.dtype == np.complex128 and np.array_equal(w1, dc.farrow_resample(x, 48000, 44100))
+
+
+@pytest.mark.parametrize("n", [4, 37, 400])
+def test_host_form_equals_the_device_form_bit_for_bit(n):
+    """skdsp_farrow (host pointers) against skdsp_farrow_dev over the whole output, every order, narrow and wide results"""
+    rng = np.random.default_rng(67 + n)
+    for dtype in (np.float32, np.complex64, np.float64):
+        x = (rng.standard_normal(n) + (1j * rng.standard_normal(n) if np.dtype(dtype).kind == "c" else 0)).astype(dtype)
+        xd = _ffi.DeviceArray.from_host(x)
+        for i_ord in (1, 2, 3):
+            for wide in (False, True):
+                y = _ffi.farrow(x, 1 / 8000.0, 1 / 11025.0, i_ord, wide=wide)
+                yd = _ffi.DeviceArray(max(y.size, 1), y.dtype)
+                _ffi.farrow_dev(xd, yd, 1 / 8000.0, 1 / 11025.0, i_ord, wide=wide)
+                assert y.size == _ffi.farrow_len(n, 1 / 8000.0, 1 / 11025.0) > 0 and yd.to_host(0, y.size).tobytes() == y.tobytes(), (dtype, i_ord, wide)

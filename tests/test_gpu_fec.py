@@ -174,3 +174,29 @@ def test_errors_raise_without_a_launch():
     with pytest.raises(ValueError):
         k.decode(np.zeros(200, np.int16), k.SOFT, 13)
     assert _ffi.debug_path() == []
+
+
+def test_host_forms_equal_the_device_forms_bit_for_bit():
+    """skdsp_viterbi_decode[_rows] (host pointers) against skdsp_viterbi_decode[_rows]_dev on the same values: rows calls at 1 and 3 rows, and the
+    stateful call over three pieces -- the middle one shorter than the decision depth, so it returns no bit and only advances the state."""
+    rng = np.random.default_rng(61)
+    cc = fc.FECConv(HALF[5], 12)
+    for nrow, nsym in ((1, 40), (3, 75)):
+        x = np.trunc(noisy(cc, rng, nrow, nsym)).astype(np.int16)
+        k = _ffi.ViterbiKernel(HALF[5], 12)
+        y = k.decode_rows(x, k.SOFT, 3)
+        xd, yd = _ffi.DeviceBytes(x.nbytes), _ffi.DeviceBytes(max(y.size, 1))
+        xd.write(x.reshape(-1).view(np.uint8))
+        k.decode_rows_dev(xd.ptr, x.shape[1], nrow, k.SOFT, 3, yd.ptr)
+        assert y.shape == (nrow, k.out_len(x.shape[1])) and y.size and np.array_equal(yd.read(0, y.size), y.reshape(-1)), (nrow, nsym)
+    x = np.trunc(noisy(cc, rng, 1, 90)[0]).astype(np.int16)
+    kh, kd = _ffi.ViterbiKernel(HALF[5], 12), _ffi.ViterbiKernel(HALF[5], 12)
+    sizes = []
+    for piece in (x[:80], x[80:84], x[84:]):
+        y = kh.decode(piece, kh.SOFT, 3)
+        xd, yd = _ffi.DeviceBytes(piece.nbytes), _ffi.DeviceBytes(max(y.size, 1))
+        xd.write(piece.view(np.uint8))
+        kd.decode_dev(xd.ptr, piece.size, kd.SOFT, 3, yd.ptr)
+        assert np.array_equal(yd.read(0, y.size), y), piece.size
+        sizes.append(y.size)
+    assert sizes[0] > 0 and sizes[2] > 0

@@ -135,3 +135,22 @@ def test_c_abi_argument_errors_come_back_without_a_launch():
     assert L.skdsp_blockcode_decode(ctypes.c_void_p(vit.h), _ffi._ptr(host), 1, _ffi._ptr(host)) == -1
     assert L.skdsp_blockcode_decode(ctypes.c_void_p(kern.h), None, 1, _ffi._ptr(host)) == -1
     assert _ffi.debug_path() == []
+
+
+@pytest.mark.parametrize("nblocks", [1, 37])
+def test_host_forms_equal_the_device_forms_bit_for_bit(nblocks):
+    """skdsp_blockcode_encode / _decode (host pointers) against their _dev forms on the same bits, one error in every other code word"""
+    rng = np.random.default_rng(62 + nblocks)
+    for code in (fb.FECHamming(3), fb.FECCyclic('10011')):
+        k = code._kernel()
+        bits = rng.integers(0, 2, (nblocks, k.k), dtype=np.uint8)
+        cw = k.encode(bits)
+        din, dout = _ffi.DeviceBytes(bits.size), _ffi.DeviceBytes(cw.size)
+        din.write(bits.reshape(-1))
+        k.encode_dev(din.ptr, nblocks, dout.ptr)
+        assert np.array_equal(dout.read(), cw.reshape(-1))
+        cw[::2, rng.integers(0, k.n)] ^= 1
+        back = k.decode(cw)
+        dout.write(cw.reshape(-1))
+        k.decode_dev(dout.ptr, nblocks, din.ptr)
+        assert np.array_equal(back, bits) and np.array_equal(din.read(), back.reshape(-1))

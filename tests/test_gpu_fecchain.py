@@ -322,3 +322,40 @@ def test_c_abi_argument_errors_come_back_without_a_launch():
     buf.write(np.full(8, 7, dtype=np.uint8), 128)
     assert L.skdsp_bit_count_rows_dev(None, 0, None, 0, 0, 1, 0, p(128)) == 0 and not buf.read(128, 8).any() and _ffi.debug_path() == []      # n = 0: zero counts, no launch
     buf.free()
+
+
+# ---------------------------------------------------------------------------------------------------------------- host forms against device forms
+@pytest.mark.parametrize("nrow,n", [(1, 1), (3, 67), (2, 300)])
+def test_encoder_host_form_equals_the_device_form_with_states_per_row(nrow, n):
+    """skdsp_convcode_encode_rows (host pointers: the bits, the per-row initial states, the code and states_out are staged) against
+    skdsp_convcode_encode_rows_dev on the same data, bit for bit; also one shared state and no state, with and without states_out"""
+    rng = np.random.default_rng(63 + n)
+    for G in (('1111001', '1011011'), ('11110111', '11011001', '10010101')):
+        k, K, R = _ffi.ConvCodeKernel(G), len(G[0]), len(G)
+        bits = rng.integers(0, 2, (nrow, n), dtype=np.uint8)
+        dbits, dcode, dst, dso = _ffi.DeviceBytes(bits.size), _ffi.DeviceBytes(R * bits.size), _ffi.DeviceBytes(nrow), _ffi.DeviceBytes(nrow)
+        dbits.write(bits.reshape(-1))
+        for nst in (nrow, 1, 0):
+            st = rng.integers(0, 1 << (K - 1), nst).astype(np.uint8)
+            code, out = k.encode_rows(bits, st if nst else None)
+            if nst:
+                dst.write(st)
+            k.encode_rows_dev(dbits.ptr, n, nrow, dst.ptr if nst else 0, nst, dcode.ptr, dso.ptr)
+            assert np.array_equal(dcode.read(), code.reshape(-1)) and np.array_equal(dso.read(), out), (G, nst)
+            code2 = np.empty_like(code)      # states_out not wanted: the same code bits
+            _ffi.check(_ffi.load().skdsp_convcode_encode_rows(ctypes.c_void_p(k.h), _ffi._ptr(bits), n, nrow, _ffi._ptr(st), nst, _ffi._ptr(code2), None))
+            assert np.array_equal(code2, code), (G, nst)
+
+
+@pytest.mark.parametrize("nrow,n", [(1, 1), (3, 131), (2, 700)])
+def test_bit_count_host_form_equals_the_device_form(nrow, n):
+    """skdsp_bit_count_rows (host pointers, rows at two different strides) against skdsp_bit_count_rows_dev and NumPy"""
+    rng = np.random.default_rng(64 + n)
+    tx, rx = rng.integers(0, 2, (nrow, n + 5), dtype=np.uint8), rng.integers(0, 2, (nrow, n), dtype=np.uint8)
+    dtx, drx, dcnt = _ffi.DeviceBytes(tx.size), _ffi.DeviceBytes(rx.size), _ffi.DeviceBytes(8 * nrow)
+    dtx.write(tx.reshape(-1))
+    drx.write(rx.reshape(-1))
+    for invert in (False, True):
+        got = _ffi.bit_count_rows(tx, rx, invert, n)
+        _ffi.bit_count_rows_dev(dtx.ptr, n + 5, drx.ptr, n, n, nrow, invert, dcnt.ptr)
+        assert np.array_equal(dcnt.read().view(np.int64), got) and np.array_equal(got, np.sum((tx[:, :n] ^ rx) != invert, axis=1))

@@ -211,3 +211,40 @@ def test_interpolators_longer_than_one_launch(dt, P, L, M):
         assert max(rel_err(f.up(x, L), ref)) <= tol
     else:
         assert max(rel_err(f.updn(x, L, M), ref[::M][:(n * L) // M])) <= tol
+
+
+def test_host_forms_survive_workspace_regrowth():
+    """A fresh process (empty workspaces): a host form with a side result in workspace 1 and scratch in workspace 3 (ofdm_rx_rows with pilots: z and
+    the rows' last estimates) at a small size, at a size whose input (65 KiB headroom + 135 KiB against 66 KiB), outputs and scratch (each ~30x)
+    make slots 0, 1 and 3 all grow -- a workspace that grows is freed and allocated anew -- at the small size again, then a host form with another
+    layout (sym_count_rows: two inputs, one output).  Every host call runs BEFORE the device call of its size, so it is the one that meets the
+    regrowth; every result equals the device form's bit for bit (sym_count_rows: also the NumPy model).  A device pointer kept across a regrowth,
+    or taken before a slot's second reserve, reads or writes freed memory here."""
+    code = r"""
+import os, sys
+import numpy as np
+sys.path.insert(0, %r); sys.path.insert(0, os.path.join(%r, 'scikit-dsp-comm_amd'))
+from sk_dsp_comm_amd import _ffi
+_ffi.init()
+nf, nc, ncp, npb = 32, 64, 8, 4
+rng = np.random.default_rng(71)
+for nrow, nsym in ((1, 4), (3, 40), (1, 4)):
+    x = (rng.standard_normal((nrow, nsym * (nc + ncp))) + 1j * rng.standard_normal((nrow, nsym * (nc + ncp)))).astype(np.complex128)
+    z, h = _ffi.ofdm_rx_rows(x, nsym, nf, nc, npb, True, ncp, 0.9, None)
+    xd, zd, hd = _ffi.DeviceArray.from_host(x.reshape(-1)), _ffi.DeviceArray(z.size, np.complex128), _ffi.DeviceArray(nrow * nf, np.complex128)
+    _ffi.ofdm_rx_rows_dev(xd, zd, nsym, nrow, nf, nc, npb, True, ncp, 0.9, None, hd)
+    assert z.shape == (nrow, _ffi.ofdm_rx_data_symbols(nsym, npb) * nf) and np.any(z) and np.any(h), (nrow, nsym)
+    assert zd.to_host().tobytes() == z.tobytes() and hd.to_host().tobytes() == h.tobytes(), (nrow, nsym)
+nrow, n = 2, 75
+lv = (2 * rng.integers(0, 4, (nrow, n)) - 3) + 1j * (2 * rng.integers(0, 4, (nrow, n)) - 3)
+rx = np.zeros((nrow, 2 * n + 1), dtype=np.complex128)
+rx[:, 1::2] = lv / 3 + 0.2 * (rng.standard_normal((nrow, n)) + 1j * rng.standard_normal((nrow, n)))
+c = _ffi.sym_count_rows(lv, rx, _ffi.SYM_QAM, 4, 0, 1, 2)
+cd = _ffi.DeviceBytes(c.nbytes)
+_ffi.sym_count_rows_dev(_ffi.DeviceArray.from_host(lv.reshape(-1)), lv.dtype, n, 0, _ffi.DeviceArray.from_host(rx.reshape(-1)), rx.dtype, 2 * n + 1, 1, 2, 0, n, nrow,
+                        _ffi.SYM_QAM, 4, 0, cd)
+assert np.array_equal(cd.read().view(np.int64).reshape(nrow, 4), c) and np.array_equal(c, _ffi.sym_count_rows_host(lv, rx, _ffi.SYM_QAM, 4, 0, 1, 2)) and c[:, 0].min() > 0
+print('REGROWTH_OK')
+""" % (ROOT, ROOT)
+    out = subprocess.run([sys.executable, "-c", code], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
+    assert b"REGROWTH_OK" in out.stdout, out.stdout.decode()[-3000:]

@@ -1893,3 +1893,27 @@ def test_iir_single_pass_soak(dt):
     assert_close(yd.to_host(0, m), want, TOL32, "after the soak")
     xd.free()
     yd.free()
+
+
+@pytest.mark.parametrize("n", [1, 37, 1000])
+def test_resampler_host_forms_equal_the_device_forms_bit_for_bit(n):
+    """skdsp_upsample / skdsp_downsample (host pointers) against skdsp_upsample_dev (scale 1) / skdsp_downsample_dev on the same vector"""
+    import ctypes
+    L = _ffi.load()
+    vp = ctypes.c_void_p
+    rng = np.random.default_rng(68 + n)
+    for dt in (np.float32, np.complex64, np.float64, np.complex128):
+        x = (rng.standard_normal(n) + (1j * rng.standard_normal(n) if np.dtype(dt).kind == "c" else 0)).astype(dt)
+        xd = _ffi.DeviceArray.from_host(x)
+        for R in (1, 3):
+            up = _ffi.upsample(x, R)
+            yd = _ffi.DeviceArray(n * R, dt)
+            _ffi.check(L.skdsp_upsample_dev(vp(xd.ptr), n, R, _ffi.code_of(dt), ctypes.c_double(1.0), vp(yd.ptr)))
+            assert np.array_equal(up[::R], x) and yd.to_host().tobytes() == up.tobytes(), (dt, R)
+            for p in range(R):
+                if n // R == 0:
+                    continue
+                dn = _ffi.downsample(x, R, p)
+                yd = _ffi.DeviceArray(n // R, dt)
+                _ffi.check(L.skdsp_downsample_dev(vp(xd.ptr), n, R, p, _ffi.code_of(dt), vp(yd.ptr)))
+                assert np.array_equal(dn, x[p::R][:n // R]) and yd.to_host().tobytes() == dn.tobytes(), (dt, R, p)

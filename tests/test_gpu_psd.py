@@ -294,3 +294,16 @@ def test_engine_record_and_host_takeover(caplog):
     assert Sx.shape == (512,)
     Px, f = ss.my_psd(x[:700])
     assert _ffi.debug_path() == ["psd"] and Px.shape == (1024,)
+
+
+@pytest.mark.parametrize("n,ns,n_fft,step,nseg", [(64, 64, 64, 32, 1), (1000, 128, 256, 64, 14), (333, 100, 128, 50, 5)])
+def test_host_form_equals_the_device_form_bit_for_bit(n, ns, n_fft, step, nseg):
+    """skdsp_psd (host pointers: only the samples the segments reach are staged) against skdsp_psd_dev on the same vector"""
+    rng = np.random.default_rng(66 + n)
+    w = np.hanning(ns)
+    for dtype in (np.float32, np.complex64, np.complex128):
+        x = (rng.standard_normal(n) + (1j * rng.standard_normal(n) if np.dtype(dtype).kind == "c" else 0)).astype(dtype)
+        S = _ffi.psd_accum(x, w, n_fft, step, nseg)
+        xd, Sd = _ffi.DeviceArray.from_host(x), _ffi.DeviceArray(n_fft, np.float64)
+        _ffi.psd_accum_dev(xd, Sd, w, n_fft, step, nseg)
+        assert np.any(S > 0) and np.array_equal(Sd.to_host().view(np.uint64), S.view(np.uint64)), dtype

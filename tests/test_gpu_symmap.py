@@ -264,3 +264,16 @@ def test_refusals_by_message():
         _ffi.check(_ffi.load().skdsp_mpsk_demap_rows_dev(ctypes.c_void_p(x.ptr), 64, 0, 0, 64, 1, _ffi.C128, 8, 1.0, 0.0, ctypes.c_void_p(b.ptr), 192))
     x.free()
     b.free()
+
+
+@pytest.mark.parametrize("nrow,width,start,step", [(1, 1, 0, 1), (3, 77, 0, 1), (2, 301, 2, 3)])
+def test_qam_scale_host_form_equals_the_device_form(nrow, width, start, step):
+    """skdsp_qam_scale_rows (host pointers: the rows are staged whole, the scales come back) against skdsp_qam_scale_rows_dev, bit for bit"""
+    rng = np.random.default_rng(65 + width)
+    for dtype in (np.complex64, np.complex128):
+        x = (rng.standard_normal((nrow, width)) + 1j * rng.standard_normal((nrow, width)) + (0.5 if width == 1 else 0)).astype(dtype)
+        n = _ffi.sym_count(width, start, step)
+        r = _ffi.qam_scale_rows(x, 16, start, step)
+        xd, rd = _ffi.DeviceArray.from_host(x.reshape(-1)), _ffi.DeviceArray(nrow, np.float64)
+        _ffi.qam_scale_rows_dev(xd.ptr, width, start, step, n, nrow, dtype, 16, rd.ptr)
+        assert r.shape == (nrow,) and np.array_equal(rd.to_host().view(np.uint64), r.view(np.uint64)), (dtype, r)

@@ -156,6 +156,19 @@ def test_device_ownership_types_host_emulation(tmp_path):
     assert run.returncode == 0 and out.strip().endswith("OK"), out[-4000:]
 
 
+def test_host_staging_layout_host_run(tmp_path):
+    """Compiles csrc/stage_plan.hpp (standard headers only) with tests/host/stage_plan_emul.cpp, under the address and undefined-behaviour
+    sanitizers: where the pieces of a host-pointer call lie in their workspace slots -- piece sizes 0, 1, 255, 256, 257 and above 2^32: every
+    offset a multiple of 256, no two pieces sharing a byte (empty ones included), the primary input exactly the headroom into slot 0, each
+    slot's total covering its last piece and a 256-byte tail, and a piece past the plan's capacity reported and not stored."""
+    exe = str(tmp_path / "stage_plan_emul")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I", os.path.join(ROOT, "scikit-dsp-comm_amd", "csrc"), os.path.join(ROOT, "tests", "host", "stage_plan_emul.cpp"), "-o", exe])
+    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    out = run.stdout.decode()
+    assert run.returncode == 0 and out.strip().endswith("OK"), out[-4000:]
+
+
 @pytest.mark.parametrize("name", ["ols4k_emul", "ols2k_emul"])
 def test_interpolator_decimator_tiles_host_emulation(tmp_path, name):
     """Compiles csrc/ols4k_core.hpp (4096 points, 16 per thread) / csrc/ols2k_core.hpp (2048 points, 8 per thread) for the HOST and
