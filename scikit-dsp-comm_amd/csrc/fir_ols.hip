@@ -21,6 +21,7 @@
 #include "skdsp_internal.hpp"
 #include "ols_tables.hpp"
 #include "fir_route.hpp"
+#include "ols_walk.hpp"
 #include <cstdlib>
 #include <cstdio>
 
@@ -35,6 +36,12 @@ struct OlsPlan : TilePlan {   // key = (kind, L): build_plan
     int ov = 0;  // overlap (discarded head) in samples, multiple of 512
     int V = 0;   // valid outputs per tile
     DevTable<float4> T1, T2, Hp;
+    // the counters of the claimed walk (ols_walk.hpp): one block per stream that launched this plan, zeroed when it is made, put back by every launch
+    struct WalkCounters {
+        hipStream_t stream;
+        DevTable<unsigned> ctr;
+    };
+    std::vector<std::unique_ptr<WalkCounters>> walk;
 };
 
 struct OlsArgs {
@@ -75,7 +82,30 @@ struct OlsArgs {
     int rep_L, rep_lr;
     unsigned rep_magic;  // ceil(2^32 / rep_lr)
     int64_t n_in, rep_hist;
+    unsigned *walk_ctr;  // the claimed walk's counters (ols_walk.hpp); the dealt walk does not read it
+#ifdef SKDSP_OLS_TIMELINE_BUILD
+    unsigned long long *tl;   // the timeline of a launch (below); null: none
+    int tl_steps;             // steps a workgroup's record has room for
+#endif
 };
+
+#ifdef SKDSP_OLS_TIMELINE_BUILD
+// Diagnostic build (make timeline -> libskdsp_timeline.so; tools/ols_timeline.py): thread 0 of every workgroup of ols_tile_kernel stamps the
+// constant-rate counter (wall_clock64, 100 MHz) at entry, behind the table barrier, behind each tile's stores and at exit, into a buffer of the
+// caller's (skdsp_ols_timeline_arm), through ordinary stores.  Record of workgroup b: kTlHead + 2 * tl_steps words at b * that --
+// [entry, tables, exit, steps] then (stamp, tile) per step; steps beyond tl_steps are counted and not kept.
+constexpr int kTlHead = 4;
+static unsigned long long *g_tl_buf = nullptr;
+static int g_tl_steps = 0;
+extern "C" void skdsp_ols_timeline_arm(void *buf_dev, int steps)
+{
+    g_tl_buf = (unsigned long long *)buf_dev;
+    g_tl_steps = steps;
+}
+#define SK_TL(...) do { __VA_ARGS__; } while (0)
+#else
+#define SK_TL(...) do { } while (0)
+#endif
 
 // The owner of tile 0 calls this (whole workgroup, uniform) before its first load of that tile: one lane polls with
 // relaxed agent-scope loads, then ONE agent-scope acquire (invalidates this CU's L1; the samples were written by another
@@ -112,6 +142,10 @@ __device__ __forceinline__ float4 vld(const volatile float4 *p)
     r.x = p->x; r.y = p->y; r.z = p->z; r.w = p->w;
     return r;
 }
+
+// The pass-1 twiddle of a thread: the low half of T1's 16-byte entry i (the high half belongs to the odd column, which makes its own by mul_w8192):
+// fetched as the 8 bytes it is
+__device__ __forceinline__ cf t1_lo(const float4 *T1, int i) { return *reinterpret_cast<const cf *>(T1 + i); }
 
 // Addresses of the whole-tile requests: a uniform 64-bit base, advanced on the scalar unit, and ONE 32-bit byte offset per lane (16 t for the 16-byte requests,
 // zero-extended): the scalar-base form of global_load / global_store.  The blocks of a complex tile lie 4096 bytes apart, one more than the instruction's
@@ -599,12 +633,42 @@ __device__ __forceinline__ OlsCareful ols_careful_args(const OlsArgs &A, int ph,
 // UP: multirate_FIR.up for phases too long for the polyphase kernels (see OlsArgs::up): the same walk over (tile, phase) pairs, H of the
 // pair's phase fetched per pair, outputs stored with stride up.  Neighbouring walk indices are the phases of one input tile: they run on
 // one XCD at one time, so the tile is fetched from HBM once and the strided stores of its phases meet in that XCD's L2.
-template <bool REAL, bool DEC, bool UP = false, bool XR = false>   // XR: real signal into the complex tile (see load_tile_xr)
+// CLAIM: the claimed walk (ols_walk.hpp, option ols_walk = 1) -- the workgroup draws its walk indices from its XCD's range instead of being dealt
+// blockIdx.x, + gridDim.x, ...  Thread 0 draws; the other waves learn the value through LDS, behind barriers the tile has anyway:
+//   * the draw for step i + 2 leaves where step i + 1's x loads leave (just in front of them; thread 0 puts the value into walk_drawn right behind
+//     barrier 2 of the same tile), and is read by everybody where step i + 2's loads leave, one tile later: between that write and that read lies
+//     barrier 1 of the tile in between, between the read and the next write barrier 2.  One draw is in flight at a time, so a workgroup finds each
+//     range empty once.
+//   * a draw that finds its range empty is followed by thread 0 drawing from the next ranges at once (walk_box, one barrier): the tail only.
+template <bool REAL, bool DEC, bool UP = false, bool XR = false, bool CLAIM = false>   // XR: real signal into the complex tile (see load_tile_xr)
 __global__ __launch_bounds__(256, 2) void ols_tile_kernel(OlsArgs A)
 {
     __shared__ float4 lds[kLdsUnits];
     __shared__ float4 t2lds[2 * kT2Units];   // T2 and its transpose: an object of their own, so that a table read cannot alias an exchange write
     __shared__ unsigned long long ols_noted;   // poisoned tiles, by walk step (careful.hpp)
+    __shared__ int walk_tiles[CLAIM ? olswalk::kMaxSteps : 1];   // CLAIM: the walk index of every step (the poisoned-tile replay goes by step)
+    __shared__ unsigned walk_drawn;                              // the draw in flight
+    __shared__ int walk_box[2];                                  // thread 0's synchronous draws: (walk index or -1, ranges found empty)
+    olswalk::Walker wk = olswalk::walker((int)blockIdx.x);
+    unsigned drawn = 0;          // (thread 0)
+    bool in_flight = false;      // a draw whose value is (or will be) in walk_drawn
+    // thread 0: draw until a tile comes or the walk is over
+    auto draw_now = [&](olswalk::Walker u) {
+        int64_t idx = -1;
+        while (idx < 0 && !olswalk::walk_over(u)) idx = olswalk::take(u, A.ntiles, atomicAdd(A.walk_ctr + olswalk::draw_from(u), 1u));
+        walk_box[0] = (int)idx;
+        walk_box[1] = u.k;
+    };
+    // everybody, behind the barrier that follows draw_now: the walk index (ntiles: none)
+    auto read_box = [&]() -> int64_t {
+        const int idx = __builtin_amdgcn_readfirstlane(walk_box[0]);
+        wk.k = __builtin_amdgcn_readfirstlane(walk_box[1]);
+        if (idx < 0) return A.ntiles;
+        ++wk.steps;
+        return (int64_t)idx;
+    };
+    SK_TL(if (A.tl && threadIdx.x == 0) A.tl[(size_t)blockIdx.x * (kTlHead + 2 * A.tl_steps)] = wall_clock64());
+    if (CLAIM && threadIdx.x == 0) draw_now(wk);   // (published by the barrier behind the table load)
     if (threadIdx.x == 0) ols_noted = 0;       // (the barrier behind the table load lies between this and any note)
     // Decimating store (.dn): the last HS of the thread's 16 H registers are fetched per tile (HS x 4 KiB from L2, requested at the top of the
     // tile, used behind the forward transform).  With all 16 held across tiles hipcc spilled four of them and reloaded them from scratch INSIDE
@@ -622,10 +686,11 @@ __global__ __launch_bounds__(256, 2) void ols_tile_kernel(OlsArgs A)
     }
     cf tw[16];
 #pragma unroll
-    for (int k1 = 1; k1 < 16; ++k1) tw[k1] = lo(A.T1[k1 * 256 + t]);  // W_8192^(2t k1) = W_4096^(t k1)
+    for (int k1 = 1; k1 < 16; ++k1) tw[k1] = t1_lo(A.T1, k1 * 256 + t);  // W_8192^(2t k1) = W_4096^(t k1)
     tw[0] = make_float2(1.f, 0.f);
 
     __syncthreads();
+    SK_TL(if (A.tl && threadIdx.x == 0) A.tl[(size_t)blockIdx.x * (kTlHead + 2 * A.tl_steps) + 1] = wall_clock64());
     int it = 0;
     // This thread's 32 bins of H stay in registers for every tile it processes: streaming
     // them per tile cost 64 KiB of L2->CU traffic per tile, a third of everything the CU's
@@ -636,6 +701,7 @@ __global__ __launch_bounds__(256, 2) void ols_tile_kernel(OlsArgs A)
     // being fetched twice from HBM (the 7.6 % of traffic above the algorithmic bytes)
     int64_t tile = (gridDim.x % 8 == 0) ? (int64_t)(blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8
                                                                  : (int64_t)blockIdx.x;
+    if constexpr (CLAIM) tile = read_box();   // (thread 0's first draw, in front of the table barrier)
     // (sharded launches walk tile 0 last: walk index w stands for tile w + 1, the last index for tile 0)
     const bool t0_last = A.halo_flag != nullptr;
     // .up: pair w = (input tile w / up, phase w % up); w < 2^31 (checked at launch), so 32-bit divisions
@@ -651,6 +717,10 @@ __global__ __launch_bounds__(256, 2) void ols_tile_kernel(OlsArgs A)
     if (tile < A.ntiles) {
         if (t0_last && phys(tile) == 0) wait_halo(A);
         load_any<REAL, XR>(A, phys(tile), t, v);
+        if constexpr (CLAIM) {   // the draw for step 1
+            in_flight = !olswalk::walk_over(wk);
+            if (in_flight && t == 0) drawn = atomicAdd(A.walk_ctr + olswalk::draw_from(wk), 1u);
+        }
     }
     // the loop is entered with no load pending on either edge (see the note in front of the stores):
     // waits placed at the loop top for THIS load would otherwise also be paid by every later tile,
@@ -666,7 +736,9 @@ __global__ __launch_bounds__(256, 2) void ols_tile_kernel(OlsArgs A)
                      "v"(v[i + 3].x), "v"(v[i + 3].y), "v"(v[i + 4].x), "v"(v[i + 4].y), "v"(v[i + 5].x), "v"(v[i + 5].y),
                      "v"(v[i + 6].x), "v"(v[i + 6].y), "v"(v[i + 7].x), "v"(v[i + 7].y));
     }
-    for (; tile < A.ntiles; tile += gridDim.x, ++it) {
+    if (CLAIM && in_flight && t == 0) walk_drawn = drawn;
+    for (; tile < A.ntiles; tile += CLAIM ? 0 : gridDim.x, ++it) {
+        if (CLAIM && t == 0) walk_tiles[it] = (int)tile;
         if (HS > 0) {
             int tt = t;   // (opaque: the requests stay inside the tile loop)
             asm volatile("" : "+v"(tt));
@@ -691,16 +763,35 @@ __global__ __launch_bounds__(256, 2) void ols_tile_kernel(OlsArgs A)
         // whole inverse FFT (requested one phase earlier, right behind pass 1: 61 spilled VGPRs in the float32 variant and
         // 0.240 vs 0.236 ms for complex64: not kept).  The wave runs at raised priority while it issues memory
         // instructions (here and at the stores): -1.1 % (0.2314 vs 0.2339 ms, alternating runs)
-        const int64_t next = tile + gridDim.x;
+        int64_t next = tile + gridDim.x;
+        if constexpr (CLAIM) {   // what the draw of one tile ago brought (everybody, uniform)
+            next = A.ntiles;
+            if (in_flight) {
+                const int64_t idx = olswalk::take(wk, A.ntiles, (unsigned)__builtin_amdgcn_readfirstlane(walk_drawn));
+                if (idx >= 0) {
+                    next = idx;
+                } else if (!olswalk::walk_over(wk)) {   // that range is empty: the next ones, now
+                    if (t == 0) draw_now(wk);
+                    __syncthreads();
+                    next = read_box();
+                }
+            }
+            in_flight = next < A.ntiles && !olswalk::walk_over(wk);
+        }
         cf nx[32];
         __builtin_amdgcn_s_setprio(3);
         if (next < A.ntiles) {
             if (t0_last && phys(next) == 0) wait_halo(A);  // (uniform: the whole workgroup owns that tile)
+            // the draw for the step behind `next`, IN FRONT of the loads: vmcnt retires in order, so thread 0 can take the value (behind barrier 2) while the
+            // loads are still under way, and the register is free again for the last pass (behind the loads and held to the stores, the headline form
+            // spilled 16 VGPRs; so: none.  The float32 and decimating forms spill 2 - 4 either way)
+            if (CLAIM && in_flight && t == 0) drawn = atomicAdd(A.walk_ctr + olswalk::draw_from(wk), 1u);
             load_any<REAL, XR>(A, phys(next), t, nx);
         }
         __builtin_amdgcn_s_setprio(0);
         inv_pass32(t, T2t, lds, Z);
         __syncthreads();
+        if (CLAIM && in_flight && t == 0) walk_drawn = drawn;   // (read by everybody one tile on, behind barrier 1; the last read was in front of this barrier)
         inv_pass1(t, tw, lds, v);
         // Have hipcc wait for the prefetch HERE, while only loads are outstanding (they have had the
         // whole inverse FFT to land).  Otherwise the wait sits at the top of the next tile, behind the
@@ -734,8 +825,14 @@ __global__ __launch_bounds__(256, 2) void ols_tile_kernel(OlsArgs A)
             store_any<REAL, DEC>(A, phys(tile), t, v, lds);
         }
         __builtin_amdgcn_s_setprio(0);
+        SK_TL(if (A.tl && t == 0 && it < A.tl_steps) {   // (behind the ISSUE of the stores: waiting for them would change what is measured)
+            unsigned long long *rec = A.tl + (size_t)blockIdx.x * (kTlHead + 2 * A.tl_steps) + kTlHead + 2 * it;
+            rec[0] = wall_clock64();
+            rec[1] = (unsigned long long)phys(tile);
+        });
         // (all results of a tile are non-finite, or none; noted by walk step and recomputed behind the loop: careful.hpp)
         if (__builtin_expect(__any(not_finite(v[31].x) | not_finite(v[31].y)), 0)) careful_note(&ols_noted, it);
+        if constexpr (CLAIM) tile = next;
 #pragma unroll
         for (int i = 0; i < 32; ++i) v[i] = nx[i];
         // Every wave must be done reading the image before the next tile overwrites it -- unless nobody else ever touches what a thread overwrites:
@@ -750,13 +847,32 @@ __global__ __launch_bounds__(256, 2) void ols_tile_kernel(OlsArgs A)
         if constexpr (REAL || DEC || UP || XR) __syncthreads();
 #endif
     }
+    if (CLAIM && t == 0) {
+        // This workgroup has drawn for the last time (the values of all its draws are in).  Whoever completes the count knows that of every
+        // workgroup of the launch, and puts the counters back for the stream's next launch (ols_walk.hpp).
+        if (atomicAdd(A.walk_ctr + olswalk::kDone * olswalk::kCtrStride, 1u) == gridDim.x - 1)
+            for (int r = 0; r <= olswalk::kRanges; ++r) __hip_atomic_store(A.walk_ctr + r * olswalk::kCtrStride, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    SK_TL(if (A.tl && t == 0) {
+        unsigned long long *rec = A.tl + (size_t)blockIdx.x * (kTlHead + 2 * A.tl_steps);
+        rec[2] = wall_clock64();
+        rec[3] = (unsigned long long)it;
+    });
     const unsigned long long noted = careful_noted(&ols_noted);
     if (__builtin_expect(noted != 0, 0)) {
-        // (the walk again, as the loop made it)
+        // (the walk again, as the loop made it: dealt, or the indices the workgroup drew)
         int64_t w = (gridDim.x % 8 == 0) ? (int64_t)(blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8 : (int64_t)blockIdx.x;
+        if constexpr (CLAIM) {
+            for (int k = 0; k < it; ++k)
+                if (careful_step_noted(noted, k)) {
+                    w = __builtin_amdgcn_readfirstlane(walk_tiles[k]);
+                    careful_ols_tile<float, REAL, DEC, UP, XR>(ols_careful_args(A, UP ? phase_of(w) : 0, !(REAL || XR)), phys(w), UP ? phase_of(w) : 0, t);
+                }
+        } else {
         for (int64_t k = 0; w < A.ntiles; w += gridDim.x, ++k)
             if (careful_step_noted(noted, k))
                 careful_ols_tile<float, REAL, DEC, UP, XR>(ols_careful_args(A, UP ? phase_of(w) : 0, !(REAL || XR)), phys(w), UP ? phase_of(w) : 0, t);
+        }
     }
 }
 
@@ -785,7 +901,7 @@ __global__ __launch_bounds__(256, 2) void ols_fold_kernel(OlsArgs A)
     }
     cf tw[16];
 #pragma unroll
-    for (int k1 = 1; k1 < 16; ++k1) tw[k1] = lo(A.T1[k1 * 256 + t]);
+    for (int k1 = 1; k1 < 16; ++k1) tw[k1] = t1_lo(A.T1, k1 * 256 + t);
     tw[0] = make_float2(1.f, 0.f);
     __syncthreads();
     float4 hh[16];
@@ -969,7 +1085,7 @@ __global__ __launch_bounds__(256, 2) void ols_rep_kernel(OlsArgs A)
     }
     cf tw[16];
 #pragma unroll
-    for (int k1 = 1; k1 < 16; ++k1) tw[k1] = lo(A.T1[k1 * 256 + t]);
+    for (int k1 = 1; k1 < 16; ++k1) tw[k1] = t1_lo(A.T1, k1 * 256 + t);
     tw[0] = make_float2(1.f, 0.f);
     __syncthreads();
     float4 hh[16];
@@ -1102,6 +1218,33 @@ int fir_ols_publish_halo(unsigned *flag, unsigned seq, hipStream_t s)
     return SKDSP_OK;
 }
 
+// The walk of a launch of ols_tile_kernel.  Option ols_walk = 1 (the default) claims the walk (ols_walk.hpp) of the PLAIN filter -- .filter of one
+// GPU, complex64 and float32: the forms measured to gain by it (profiles/r18: -2.8 % and -1.5 %) --, 2 that of every form (the decimating store, the
+// walks of .up, the sharded filter: same bytes, not measured to gain, two to four spilled registers in the decimating and float32 forms), 0 none.
+// A launch is claimed only if its walk is short enough for the workgroups' step lists (walk_takes); then A.walk_ctr is the plan's counter block of
+// stream s (made and zeroed on first use -- under the handle's lock, like every table of a plan; no stream operation on any later call).
+static int walk_of_launch(OlsPlan *p, hipStream_t s, int64_t grid, bool plain, OlsArgs *A, bool *claim)
+{
+    A->walk_ctr = nullptr;
+    const int o = opt().ols_walk;
+    *claim = (o == 2 || (o == 1 && plain)) && olswalk::walk_takes(A->ntiles, grid);
+    if (!*claim) return SKDSP_OK;
+    for (auto &w : p->walk)
+        if (w->stream == s) { A->walk_ctr = w->ctr.dev; return SKDSP_OK; }
+    std::unique_ptr<OlsPlan::WalkCounters> w(new OlsPlan::WalkCounters());
+    w->stream = s;
+    const int rc = w->ctr.upload(std::vector<unsigned>(olswalk::kCtrWords, 0u));
+    if (rc) return rc;
+    A->walk_ctr = w->ctr.dev;
+    p->walk.push_back(std::move(w));
+    return SKDSP_OK;
+}
+#define SK_TILE(R, D, U, X)                                                                                           \
+    do {                                                                                                              \
+        if (claim) hipLaunchKernelGGL((ols_tile_kernel<R, D, U, X, true>), dim3((unsigned)grid), dim3(256), 0, s, A);  \
+        else hipLaunchKernelGGL((ols_tile_kernel<R, D, U, X>), dim3((unsigned)grid), dim3(256), 0, s, A);              \
+    } while (0)
+
 int fir_ols_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, void *y, hipStream_t s, int dec, int reserve_wgs,
                    const unsigned *halo_flag, unsigned halo_seq, unsigned *halo_err, int halo_spins)
 {
@@ -1123,8 +1266,8 @@ int fir_ols_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, void 
     A.T1 = p->T1.dev; A.T2 = p->T2.dev; A.Hp = p->Hp.dev;
     A.ov = p->ov; A.V = p->V; A.a0 = p->ov / 512; A.keep = ols_keep_blocks(A.a0);
     const bool real = h->dtype == SKDSP_F32;
-    // element alignment is all the vector accesses need: tile starts are odd multiples of the
-    // element size anyway (V = 8192 - (Ntaps-1) is odd for even tap counts)
+    // element alignment is all the vector accesses need (16-byte requests take any 4-byte aligned address).  Tile starts add nothing to the
+    // caller's alignment: V = 8192 - ov with ov a multiple of 512, so every tile begins a multiple of 512 elements behind x and y
     A.aligned = ((((uintptr_t)x) | ((uintptr_t)y)) & (real ? 3 : 7)) == 0;
     int64_t ntiles = (n + p->V - 1) / p->V;
     if (real) ntiles = (ntiles + 1) / 2;  // pairs of real tiles
@@ -1146,6 +1289,12 @@ int fir_ols_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, void 
     if (grid > ntiles) grid = ntiles;
     const int mf = A.dec % 16 == 0 ? 16 : (A.dec % 8 == 0 ? 8 : (A.dec % 4 == 0 ? 4 : (A.dec % 2 == 0 ? 2 : 1)));
     const bool fold = opt().fir_dn_fold && !halo_flag && mf > 1;
+    bool claim = false;   // (ols_fold_kernel stays dealt)
+    A.walk_ctr = nullptr;
+    if (!fold && (rc = walk_of_launch(p, s, grid, A.dec == 1 && !halo_flag, &A, &claim))) return rc;
+#ifdef SKDSP_OLS_TIMELINE_BUILD
+    A.tl = g_tl_buf; A.tl_steps = g_tl_steps;
+#endif
     if (fold) {   // the decimating inverse transform (ols_fold_kernel): M = mf x (what the store takes)
         const int mr = A.dec / mf;
         A.dec_magic = mr > 1 ? (unsigned)((((unsigned long long)1 << 32) + mr - 1) / mr) : 0u;   // (elements of the decimated run: below 2^14 + mr, exact for mr <= 4096)
@@ -1160,11 +1309,11 @@ int fir_ols_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, void 
         }
 #undef SK_FOLD
     } else if (A.dec > 1) {
-        if (real) hipLaunchKernelGGL((ols_tile_kernel<true, true>), dim3((unsigned)grid), dim3(256), 0, s, A);
-        else hipLaunchKernelGGL((ols_tile_kernel<false, true>), dim3((unsigned)grid), dim3(256), 0, s, A);
+        if (real) SK_TILE(true, true, false, false);
+        else SK_TILE(false, true, false, false);
     } else {
-        if (real) hipLaunchKernelGGL((ols_tile_kernel<true, false>), dim3((unsigned)grid), dim3(256), 0, s, A);
-        else hipLaunchKernelGGL((ols_tile_kernel<false, false>), dim3((unsigned)grid), dim3(256), 0, s, A);
+        if (real) SK_TILE(true, false, false, false);
+        else SK_TILE(false, false, false, false);
     }
     SK_HIP(hipGetLastError());
     return SKDSP_OK;
@@ -1214,17 +1363,22 @@ static int up_walk(FirHandle *h, int kind, const void *x, int64_t n, int64_t n_h
     const int reserve_wgs = opt().ols_reserve;
     if (reserve_wgs > 0 && grid >= 4 * (int64_t)reserve_wgs) grid -= reserve_wgs;
     if (grid > ntiles) grid = ntiles;
+    bool claim = false;
+    if ((rc = walk_of_launch(p, s, grid, false, &A, &claim))) return rc;
+#ifdef SKDSP_OLS_TIMELINE_BUILD
+    A.tl = nullptr; A.tl_steps = 0;
+#endif
     if (xr) {
         // (L = 2 is one pair: "row 0" of the rows form IS the output, written with the plain complex filter's full-width stores.  The
         // instantiation that also keeps H in registers -- UP = false -- compiles to 18 spilled registers with the real-input loads.)
         if (L == 2 && A.up_pitch == 0) A.up_pitch = 1;
-        hipLaunchKernelGGL((ols_tile_kernel<false, false, true, true>), dim3((unsigned)grid), dim3(256), 0, s, A);
+        SK_TILE(false, false, true, true);
     } else if (dec > 1) {
-        if (real) hipLaunchKernelGGL((ols_tile_kernel<true, true, true>), dim3((unsigned)grid), dim3(256), 0, s, A);
-        else hipLaunchKernelGGL((ols_tile_kernel<false, true, true>), dim3((unsigned)grid), dim3(256), 0, s, A);
+        if (real) SK_TILE(true, true, true, false);
+        else SK_TILE(false, true, true, false);
     } else {
-        if (real) hipLaunchKernelGGL((ols_tile_kernel<true, false, true>), dim3((unsigned)grid), dim3(256), 0, s, A);
-        else hipLaunchKernelGGL((ols_tile_kernel<false, false, true>), dim3((unsigned)grid), dim3(256), 0, s, A);
+        if (real) SK_TILE(true, false, true, false);
+        else SK_TILE(false, false, true, false);
     }
     SK_HIP(hipGetLastError());
     return SKDSP_OK;
@@ -1259,6 +1413,10 @@ int fir_ols_rep_launch(FirHandle *h, const void *x, int64_t n, int64_t n_hist, i
     A.rep_L = L; A.rep_lr = L / lf;
     A.rep_magic = A.rep_lr > 1 ? (unsigned)((((unsigned long long)1 << 32) + A.rep_lr - 1) / A.rep_lr) : 0u;
     A.n_in = n; A.rep_hist = n_hist;
+    A.walk_ctr = nullptr;   // (ols_rep_kernel stays dealt)
+#ifdef SKDSP_OLS_TIMELINE_BUILD
+    A.tl = nullptr; A.tl_steps = 0;
+#endif
     if ((rc = fir_careful(h, &A.cf))) return rc;
     int64_t grid = 2 * (int64_t)ctx().num_cus;
     const int reserve_wgs = opt().ols_reserve;

@@ -47,6 +47,7 @@ struct Options {
     int fir_bx_t16 = 1;       // the float32 plain filter on the matrix pipe stores its 256-output tiles as runs (a 4 x 4 transpose between registers and lane groups); 0: four 64-byte runs per store (A/B switch)
     int ols_keep_overlap = 1; // overlap-save tiles: the blocks a tile shares with its neighbours are loaded with ordinary (L2-resident) loads, the rest nontemporal; 0: all nontemporal, 2: all ordinary -- what every value executed before the policy was compiled per block (A/B switch; complex64 tiles of fir_ols.hip)
     int ols_reserve = 8;      // workgroup slots a persistent overlap-save launch leaves free
+    int ols_walk = 1;         // the walk of ols_tile_kernel: 0 dealt (workgroup b takes tiles first(b), + grid, ...), 1 claimed for the plain filter (ols_walk.hpp: workgroups draw tiles from per-XCD ranges), 2 claimed for every form of the kernel; the same bytes whichever (A/B switch; measured in profiles/r18)
     int iir_planar = 0;       // complex IIR through two real planes (tests compare it with the interleaved kernels)
     int iir_dn_full = 0;      // .dn as full-rate scan + downsample kernel
     int iir_no_mfma = 0;      // recurrence K1 instead of the matrix-pipe K1
