@@ -409,6 +409,31 @@ int skdsp_pulse_shape_rows_dev(skdsp_handle h, const void *x_dev, int64_t n, int
 int skdsp_pulse_mf_rows(skdsp_handle h, const void *x, int64_t n, int64_t nrow, int64_t start, int64_t step, void *y);
 int skdsp_pulse_mf_rows_dev(skdsp_handle h, const void *x_dev, int64_t n, int64_t nrow, int64_t x_stride, int64_t start, int64_t step, void *y_dev, int64_t y_stride);
 
+/* Decision-directed carrier phase tracking over the rows of a frame set (csrc/carrier.hip, csrc/carrier_core.hpp): synchronization.DD_carrier_sync per row, every
+ * row a frame from rest (theta_hat = 0, vi = 0), and the impairment helpers phase_step / time_step.  dtype: complex64 or complex128 (complex64 is storage only:
+ * the loop runs in float64).  Symbol k of a row is element start + k step; n: the symbols of a row; strides in elements; no handle.
+ *   carrier_rows:    per symbol z' = z exp(-1j theta_hat), the decision a_hat (family 0 QAM of mod 2, 4, 16, 64, 256; 1 MPSK of mod 2 ... 32), the detector
+ *                    (type 0 im(z') re(a) - re(z') im(a), 1 the wrapped angle difference, 2 im(z' / a)), vi += k2 e, theta_hat = mod(theta_hat + k1 e + vi, 2 pi).
+ *                    outputs: bit 0 z_prime, 1 a_hat (both of dtype), 2 e_phi, 3 theta_h (float64): only the selected ones are written (the others may be null);
+ *                    y_stride serves all four.  gains: null (k1, k2 serve every row) or nrow pairs (k1, k2).  r_dev: QAM, the rows' 1 / (std c) as
+ *                    skdsp_qam_scale_rows_dev writes them (the host form makes them itself from qam_c = sqrt(3 / (2 (mod - 1)))).  inv_sqrt2: the caller's
+ *                    1 / sqrt(2) (MPSK 4); tab_re, tab_im: HOST pointers to the mod decision points exp(1j 2 pi a / mod) (MPSK above 4), else null.
+ *   time_step_rows:  y[r, j] = x[r, j] for j < min(n, ns n_step), else x[r, j + t_step] where that lies inside the row, else 0; j < n_out.  t_steps_dev:
+ *                    null or nrow int64 on the device.
+ *   phase_step_rows: y[r, j] = x[r, j ns] f, j < ceil(n / ns), f = 1 + 0j before n_step and (f_re, f_im), the caller's exp(1j p_step), from there on;
+ *                    factors_dev: null or nrow pairs on the device.
+ * The device, the host emulation (tests/host/carrier_emul.cpp) and the NumPy restatement (_ffi.dd_carrier_rows_host) give the same bits. */
+int skdsp_carrier_rows(const void *x, int64_t n, int64_t nrow, int64_t x_stride, int64_t start, int64_t step, int dtype, int family, int mod, int type, int open_loop, double k1,
+                       double k2, const double *gains, double qam_c, double inv_sqrt2, const double *tab_re, const double *tab_im, int outputs, void *z, void *a, double *e,
+                       double *t);
+int skdsp_carrier_rows_dev(const void *x_dev, int64_t n, int64_t nrow, int64_t x_stride, int64_t start, int64_t step, int dtype, int family, int mod, int type, int open_loop,
+                           double k1, double k2, const double *gains_dev, const double *r_dev, double inv_sqrt2, const double *tab_re, const double *tab_im, int outputs,
+                           void *z_dev, void *a_dev, double *e_dev, double *t_dev, int64_t y_stride);
+int skdsp_time_step_rows_dev(const void *x_dev, int64_t n, int64_t nrow, int64_t x_stride, int dtype, int64_t ns, int64_t n_step, int64_t t_step, const int64_t *t_steps_dev,
+                             void *y_dev, int64_t n_out, int64_t y_stride);
+int skdsp_phase_step_rows_dev(const void *x_dev, int64_t n, int64_t nrow, int64_t x_stride, int dtype, int64_t ns, int64_t n_step, double f_re, double f_im,
+                              const double *factors_dev, void *y_dev, int64_t y_stride);
+
 /* Host-pointer entry points of a float32/complex64 handle deliver y as float64/complex128 (the
  * reference's result dtype, multirate_helper.py:108 etc.): widened on the device before the copy
  * back, so y must hold twice the bytes.  Device-pointer (_dev) entry points are not affected. */

@@ -391,6 +391,57 @@ static int pulse_mf_call(bool host, skdsp_handle hh, const void *x, int64_t n, i
     return stage_finish(p, pulse_mf_launch(h, p.in_dev(), n, nrow, start, step, x_stride, y_stride, p.dev(iy), ctx().stream));
 }
 
+// ---------------------------------------------------------------- carrier phase tracking and its impairment helpers over rows (carrier.hip): synchronization.DD_carrier_sync_rows,
+// phase_step_rows, time_step_rows
+// host form: rows x_stride apart in x, contiguous (n each) in the selected outputs; gains: null or nrow pairs on the HOST; the MQAM scales are made here, by the merge
+// behind skdsp_qam_scale_rows, in workspace 3 of the calling slot (the device form is handed them)
+static int carrier_call(bool host, const void *x, int64_t n, int64_t nrow, int64_t x_stride, int64_t start, int64_t step, int dtype, int family, int mod, int type,
+                        int open_loop, double k1, double k2, const double *gains, const double *r, double qam_c, double inv_sqrt2, const double *tab_re, const double *tab_im,
+                        int outputs, void *z, void *a, double *e, double *t, int64_t y_stride)
+{
+    int rc = carrier_check(family, mod, type, dtype, outputs, n, nrow, start, step, x_stride, y_stride);
+    if (rc || n == 0 || nrow == 0) return rc;
+    SK_CHECK(x, SKDSP_ERR_BADARG, "carrier_rows: null pointer");
+    SK_CHECK((!(outputs & 1) || z) && (!(outputs & 2) || a) && (!(outputs & 4) || e) && (!(outputs & 8) || t), SKDSP_ERR_BADARG, "carrier_rows: a selected output is null");
+    API_BEGIN;
+    StagePlan p(host);
+    p.input(x, sym_span(x_stride, start, step, n, nrow) * dtype_size(dtype));
+    const size_t rows = (size_t)y_stride * (size_t)nrow;
+    const int ig = p.add_in(gains, gains ? (size_t)nrow * 2 * sizeof(double) : 0);
+    const int iz = p.add_out((outputs & 1) ? z : nullptr, (outputs & 1) ? rows * dtype_size(dtype) : 0), ia = p.add_out((outputs & 2) ? a : nullptr, (outputs & 2) ? rows * dtype_size(dtype) : 0);
+    const int ie = p.add_out((outputs & 4) ? e : nullptr, (outputs & 4) ? rows * sizeof(double) : 0), it = p.add_out((outputs & 8) ? t : nullptr, (outputs & 8) ? rows * sizeof(double) : 0);
+    const bool scale_here = host && family == 0;
+    const size_t part = stage_round(symscale_scratch_bytes(n, nrow));
+    if (scale_here) p.scratch_bytes = part + stage_round((size_t)nrow * sizeof(double)) + 256;
+    if ((rc = stage_begin(p))) return rc;
+    const double *r_dev = r;
+    if (scale_here) {
+        double *made = reinterpret_cast<double *>(static_cast<char *>(p.scratch) + part);
+        if ((rc = symscale_launch(p.in_dev(), x_stride, start, step, n, nrow, dtype, mod, qam_c, p.scratch, made, ctx().stream))) return stage_finish(p, rc);
+        r_dev = made;
+    }
+    return stage_finish(p, carrier_launch(p.in_dev(), n, nrow, x_stride, start, step, dtype, family, mod, type, open_loop, k1, k2, gains ? (const double *)p.dev(ig) : nullptr,
+                                          r_dev, inv_sqrt2, tab_re, tab_im, outputs, p.dev(iz), p.dev(ia), (double *)p.dev(ie), (double *)p.dev(it), y_stride, ctx().stream));
+}
+
+// only the device forms are exported (the Python layer stages phase_step_rows / time_step_rows itself); the body is the shared shape, so host = true
+// would be the host form: contiguous rows (n in, n_out out), per-row values null or nrow of them on the HOST
+static int impair_call(bool host, int mode, const void *x, int64_t n, int64_t nrow, int64_t x_stride, int dtype, int64_t ns, int64_t n_step, int64_t shift,
+                       const int64_t *shifts, double c, double d, const double *factors, void *y, int64_t n_out, int64_t y_stride)
+{
+    int rc = impair_check(mode, dtype, n, n_out, nrow, ns, n_step, x_stride, y_stride);
+    if (rc || n_out == 0 || nrow == 0) return rc;
+    SK_CHECK(y && (x || n == 0), SKDSP_ERR_BADARG, "%s: null pointer", mode ? "phase_step" : "time_step");
+    API_BEGIN;
+    StagePlan p(host);
+    p.input(x, n ? (size_t)((nrow - 1) * x_stride + n) * dtype_size(dtype) : 0);
+    const int iy = p.add_out(y, (size_t)((nrow - 1) * y_stride + n_out) * dtype_size(dtype));
+    const int is = p.add_in(shifts, shifts ? (size_t)nrow * sizeof(int64_t) : 0), iff = p.add_in(factors, factors ? (size_t)nrow * 2 * sizeof(double) : 0);
+    if ((rc = stage_begin(p))) return rc;
+    return stage_finish(p, impair_launch(mode, p.in_dev(), n, nrow, x_stride, dtype, ns, n_step, shift, shifts ? (const int64_t *)p.dev(is) : nullptr, c, d,
+                                         factors ? (const double *)p.dev(iff) : nullptr, p.dev(iy), n_out, y_stride, ctx().stream));
+}
+
 extern "C" {
 
 // FIR bank (fir_bank.hip): argument errors need no device
@@ -720,6 +771,32 @@ int skdsp_pulse_mf_rows_dev(skdsp_handle h, const void *x_dev, int64_t n, int64_
 int skdsp_pulse_mf_rows(skdsp_handle h, const void *x, int64_t n, int64_t nrow, int64_t start, int64_t step, void *y)
 {
     return pulse_mf_call(true, h, x, n, nrow, n, start, step, y, 0);
+}
+
+// ---------------------------------------------------------------- carrier phase tracking and its impairment helpers over rows
+int skdsp_carrier_rows_dev(const void *x_dev, int64_t n, int64_t nrow, int64_t x_stride, int64_t start, int64_t step, int dtype, int family, int mod, int type, int open_loop,
+                           double k1, double k2, const double *gains_dev, const double *r_dev, double inv_sqrt2, const double *tab_re, const double *tab_im, int outputs,
+                           void *z_dev, void *a_dev, double *e_dev, double *t_dev, int64_t y_stride)
+{
+    return carrier_call(false, x_dev, n, nrow, x_stride, start, step, dtype, family, mod, type, open_loop, k1, k2, gains_dev, r_dev, 0.0, inv_sqrt2, tab_re, tab_im, outputs, z_dev,
+                        a_dev, e_dev, t_dev, y_stride);
+}
+int skdsp_carrier_rows(const void *x, int64_t n, int64_t nrow, int64_t x_stride, int64_t start, int64_t step, int dtype, int family, int mod, int type, int open_loop, double k1,
+                       double k2, const double *gains, double qam_c, double inv_sqrt2, const double *tab_re, const double *tab_im, int outputs, void *z, void *a, double *e,
+                       double *t)
+{
+    return carrier_call(true, x, n, nrow, x_stride, start, step, dtype, family, mod, type, open_loop, k1, k2, gains, nullptr, qam_c, inv_sqrt2, tab_re, tab_im, outputs, z, a, e, t, n);
+}
+
+int skdsp_time_step_rows_dev(const void *x_dev, int64_t n, int64_t nrow, int64_t x_stride, int dtype, int64_t ns, int64_t n_step, int64_t t_step, const int64_t *t_steps_dev,
+                             void *y_dev, int64_t n_out, int64_t y_stride)
+{
+    return impair_call(false, 0, x_dev, n, nrow, x_stride, dtype, ns, n_step, t_step, t_steps_dev, 1.0, 0.0, nullptr, y_dev, n_out, y_stride);
+}
+int skdsp_phase_step_rows_dev(const void *x_dev, int64_t n, int64_t nrow, int64_t x_stride, int dtype, int64_t ns, int64_t n_step, double f_re, double f_im,
+                              const double *factors_dev, void *y_dev, int64_t y_stride)
+{
+    return impair_call(false, 1, x_dev, n, nrow, x_stride, dtype, ns, n_step, 0, nullptr, f_re, f_im, factors_dev, y_dev, ns >= 1 ? (n + ns - 1) / ns : 0, y_stride);
 }
 
 }  // extern "C"

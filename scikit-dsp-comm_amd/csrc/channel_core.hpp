@@ -123,14 +123,10 @@ SK_HD double neg_ln_u(uint64_t k)
     // ln 2 = hi + lo, hi of 32 significant bits: ne hi is exact
     return ne * 0x1.62e42feep-1 + (ne * 0x1.a39ef35793c76p-33 - lnm);
 }
-// cos and sin of 2 pi k 2^-53, k = 0 ... 2^53 - 1
-SK_HD void sincos_2pi(uint64_t k, double *c, double *s)
+// the polynomial stage: sin and cos of x in [0, pi / 4] (shared with carrier_core.hpp's sincos_rad, which reduces an angle in radians to it)
+SK_HD void sincos_octant(double x, double *sin_x, double *cos_x)
 {
     SK_NO_CONTRACT
-    const int oct = (int)(k >> 50);
-    uint64_t f = k & (((uint64_t)1 << 50) - 1);
-    if (oct & 1) f = ((uint64_t)1 << 50) - f;                    // the mirror image within the octant: exact
-    const double x = ((double)f * 0x1p-53) * 0x1.921fb54442d18p+2;   // 2 pi t, t in [0, 1 / 8]
     const double z = x * x;
     double ps = 1.0 / 355687428096000.0;                          // 1 / 17!
     ps = -1.0 / 1307674368000.0 + z * ps;                         // 15!
@@ -149,8 +145,20 @@ SK_HD void sincos_2pi(uint64_t k, double *c, double *s)
     pc = 1.0 / 40320.0 + z * pc;                                  // 8!
     pc = -1.0 / 720.0 + z * pc;                                   // 6!
     pc = 1.0 / 24.0 + z * pc;                                     // 4!
-    const double cx = 1.0 - (0.5 * z - (z * z) * pc);
-    const bool sw = ((oct + 1) & 2) != 0;                         // octants 1, 2, 5, 6: the angle is measured from the imaginary axis
+    *sin_x = sx;
+    *cos_x = 1.0 - (0.5 * z - (z * z) * pc);
+}
+// cos and sin of 2 pi k 2^-53, k = 0 ... 2^53 - 1
+SK_HD void sincos_2pi(uint64_t k, double *c, double *s)
+{
+    SK_NO_CONTRACT
+    const int oct = (int)(k >> 50);
+    uint64_t f = k & (((uint64_t)1 << 50) - 1);
+    if (oct & 1) f = ((uint64_t)1 << 50) - f;                    // the mirror image within the octant: exact
+    const double x = ((double)f * 0x1p-53) * 0x1.921fb54442d18p+2;   // 2 pi t, t in [0, 1 / 8]
+    double sx, cx;
+    sincos_octant(x, &sx, &cx);
+    const bool sw =((oct + 1) & 2) != 0;                         // octants 1, 2, 5, 6: the angle is measured from the imaginary axis
     const double ca = sw ? sx : cx, sa = sw ? cx : sx;
     *c = ((oct + 2) & 4) ? -ca : ca;                              // octants 2 ... 5: the left half plane
     *s = (oct & 4) ? -sa : sa;                                    // octants 4 ... 7: the lower

@@ -423,4 +423,18 @@ int pulse_mf_check(HandleBase *h, int64_t n, int64_t nrow, int64_t start, int64_
 int pulse_mf_launch(HandleBase *h, const void *x_dev, int64_t n, int64_t nrow, int64_t start, int64_t step, int64_t x_stride, int64_t y_stride, void *y_dev,
                     hipStream_t s);
 
+// ---- carrier phase tracking and its impairment helpers over rows (carrier.hip): synchronization.DD_carrier_sync / phase_step / time_step; the step, the plans and
+// the per-thread functions are carrier_core.hpp ----
+// family 0 QAM, 1 MPSK; symbol k of a row is element start + k step; outputs: bit 0 z_prime, 1 a_hat, 2 e_phi, 3 theta_h (an output that is not selected is not
+// touched and may be null); y_stride serves the four outputs.  gains_dev: null (k1, k2 serve every row) or [nrow][2]; r_dev: the rows' 1 / scale (QAM; symscale_launch).
+// inv_sqrt2, tab_re_host, tab_im_host: the host's 1 / np.sqrt(2) and exp(1j 2 pi a / M), read for MPSK 4 and MPSK above 4.  No handle.
+int carrier_check(int family, int mod, int type, int dtype, int outputs, int64_t n, int64_t nrow, int64_t start, int64_t step, int64_t x_stride, int64_t y_stride);   // host-only
+int carrier_launch(const void *x_dev, int64_t n, int64_t nrow, int64_t x_stride, int64_t start, int64_t step, int dtype, int family, int mod, int type, int open_loop,
+                   double k1, double k2, const double *gains_dev, const double *r_dev, double inv_sqrt2, const double *tab_re_host, const double *tab_im_host, int outputs,
+                   void *z_dev, void *a_dev, double *e_dev, double *t_dev, int64_t y_stride, hipStream_t s);
+// mode 0 time_step (shift / shifts_dev: t_step, one or [nrow] int64), mode 1 phase_step ((c, d) / factors_dev: exp(1j p_step), one or [nrow][2])
+int impair_check(int mode, int dtype, int64_t n, int64_t n_out, int64_t nrow, int64_t ns, int64_t n_step, int64_t x_stride, int64_t y_stride);   // host-only
+int impair_launch(int mode, const void *x_dev, int64_t n, int64_t nrow, int64_t x_stride, int dtype, int64_t ns, int64_t n_step, int64_t shift, const int64_t *shifts_dev,
+                  double c, double d, const double *factors_dev, void *y_dev, int64_t n_out, int64_t y_stride, hipStream_t s);
+
 }  // namespace skdsp

@@ -10,11 +10,12 @@ from . import multirate_helper
 from . import digitalcom
 from . import fec_conv
 from . import fec_block
+from . import synchronization
 from .multirate_helper import rate_change, multirate_FIR, multirate_IIR
 from .sigsys import upsample, downsample, cic
 
 __version__ = "0.1.0"
-__all__ = ["sigsys", "multirate_helper", "digitalcom", "fec_conv", "fec_block", "rate_change", "multirate_FIR", "multirate_IIR", "upsample", "downsample",
+__all__ = ["sigsys", "multirate_helper", "digitalcom", "fec_conv", "fec_block", "synchronization", "rate_change", "multirate_FIR", "multirate_IIR", "upsample", "downsample",
            "cic", "config", "install"]
 
 

@@ -46,6 +46,7 @@ SYMBOLS = [
     "skdsp_ofdm_tx_rows", "skdsp_ofdm_tx_rows_dev", "skdsp_ofdm_rx_rows", "skdsp_ofdm_rx_rows_dev", "skdsp_ofdm_equalize_rows", "skdsp_ofdm_equalize_rows_dev",
     "skdsp_lag_corr_len", "skdsp_lag_corr", "skdsp_lag_corr_dev", "skdsp_sym_count_rows", "skdsp_sym_count_rows_dev",
     "skdsp_pulse_create", "skdsp_pulse_mf_out_len", "skdsp_pulse_shape_rows", "skdsp_pulse_shape_rows_dev", "skdsp_pulse_mf_rows", "skdsp_pulse_mf_rows_dev",
+    "skdsp_carrier_rows", "skdsp_carrier_rows_dev", "skdsp_time_step_rows_dev", "skdsp_phase_step_rows_dev",
     "skdsp_dist_unique_id", "skdsp_dist_init", "skdsp_dist_shutdown", "skdsp_dist_comm_count", "skdsp_dist_barrier",
     "skdsp_dist_allreduce_max", "skdsp_dist_allreduce_sum", "skdsp_dist_sendrecv", "skdsp_dist_allgather", "skdsp_dist_halo_exchange", "skdsp_fir_filter_shard_dev",
 ]
@@ -205,6 +206,12 @@ def load():
             L.skdsp_pulse_shape_rows_dev.argtypes = [vp, vp, i64, i64, i64, ci, pd, vp, i64]
             L.skdsp_pulse_mf_rows.argtypes = [vp, vp, i64, i64, i64, i64, vp]
             L.skdsp_pulse_mf_rows_dev.argtypes = [vp, vp, i64, i64, i64, i64, i64, vp, i64]
+        if hasattr(L, "skdsp_carrier_rows"):
+            dbl = ctypes.c_double
+            L.skdsp_carrier_rows.argtypes = [vp, i64, i64, i64, i64, i64, ci, ci, ci, ci, ci, dbl, dbl, vp, dbl, dbl, vp, vp, ci, vp, vp, vp, vp]
+            L.skdsp_carrier_rows_dev.argtypes = [vp, i64, i64, i64, i64, i64, ci, ci, ci, ci, ci, dbl, dbl, vp, vp, dbl, vp, vp, ci, vp, vp, vp, vp, i64]
+            L.skdsp_time_step_rows_dev.argtypes = [vp, i64, i64, i64, ci, i64, i64, i64, vp, vp, i64, i64]
+            L.skdsp_phase_step_rows_dev.argtypes = [vp, i64, i64, i64, ci, i64, i64, dbl, dbl, vp, vp, i64]
         L.skdsp_dist_unique_id.argtypes = [vp]
         L.skdsp_dist_init.argtypes = [ci, ci, vp]
         L.skdsp_dist_comm_count.argtypes = [ctypes.POINTER(ci)]
@@ -1636,6 +1643,320 @@ class PulseKernel:
         n_out = sym_count(int(n), int(start), int(step))
         check(load().skdsp_pulse_mf_rows_dev(ctypes.c_void_p(self.h), _dp(xd), int(n), int(nrow), int(n if x_stride is None else x_stride), int(start), int(step),
                                              _dp(yd), int(n_out if y_stride is None else y_stride)))
+
+
+# --------------------------------------------------------------------------
+# Carrier phase tracking and its impairment helpers over frame sets (csrc/carrier.hip): synchronization.DD_carrier_sync / phase_step / time_step
+# --------------------------------------------------------------------------
+CAR_OUTPUTS = ("z_prime", "a_hat", "e_phi", "theta_h")
+_PIO2_1, _PIO2_2, _PIO2_3 = (float.fromhex(h) for h in ("0x1.921fb54442d10p+0", "0x1.08d313198a2e0p-49", "0x1.b839a252049c1p-104"))
+_TWO_OVER_PI, _PI = float.fromhex("0x1.45f306dc9c883p-1"), float.fromhex("0x1.921fb54442d18p+1")
+_ATAN_CUTS = tuple(float.fromhex(h) for h in ("0x1.936bb8c5b2da2p-4", "0x1.36a08355c63dcp-2", "0x1.11ab7190834ecp-1", "0x1.a43002ae42850p-1"))
+_ATAN_TAB = np.array([[float.fromhex(h) for h in row] for row in (          # k pi / 16, cos and sin of it, (hi, lo) each: symmap_core.hpp's atan2_rn
+    ("0x0p+0", "0x0p+0", "0x1p+0", "0x0p+0", "0x0p+0", "0x0p+0"),
+    ("0x1.921fb54442d18p-3", "0x1.1a62633145c07p-57", "0x1.f6297cff75cb0p-1", "0x1.562172a361fd3p-56", "0x1.8f8b83c69a60bp-3", "-0x1.26d19b9ff8d82p-57"),
+    ("0x1.921fb54442d18p-2", "0x1.1a62633145c07p-56", "0x1.d906bcf328d46p-1", "0x1.457e610231ac2p-56", "0x1.87de2a6aea963p-2", "-0x1.72cedd3d5a610p-57"),
+    ("0x1.2d97c7f3321d2p-1", "0x1.a79394c9e8a0ap-56", "0x1.a9b66290ea1a3p-1", "0x1.9f630e8b6dac8p-60", "0x1.1c73b39ae68c8p-1", "0x1.b25dd267f6600p-55"),
+    ("0x1.921fb54442d18p-1", "0x1.1a62633145c07p-55", "0x1.6a09e667f3bcdp-1", "-0x1.bdd3413b26456p-55", "0x1.6a09e667f3bcdp-1", "-0x1.bdd3413b26456p-55"))])
+_PIO2_DD = (float.fromhex("0x1.921fb54442d18p+0"), float.fromhex("0x1.1a62633145c07p-54"))
+_PI_DD = (float.fromhex("0x1.921fb54442d18p+1"), float.fromhex("0x1.1a62633145c07p-53"))
+
+
+def _sincos_octant_host(x):
+    """(sin, cos) of x in [0, pi / 4]: channel_core.hpp's sincos_octant, operation by operation"""
+    z = x * x
+    ps = np.full(z.shape, 1.0 / 355687428096000.0)
+    for c in (-1.0 / 1307674368000.0, 1.0 / 6227020800.0, -1.0 / 39916800.0, 1.0 / 362880.0, -1.0 / 5040.0, 1.0 / 120.0, -1.0 / 6.0):
+        ps = c + z * ps
+    pc = np.full(z.shape, -1.0 / 6402373705728000.0)
+    for c in (1.0 / 20922789888000.0, -1.0 / 87178291200.0, 1.0 / 479001600.0, -1.0 / 3628800.0, 1.0 / 40320.0, -1.0 / 720.0, 1.0 / 24.0):
+        pc = c + z * pc
+    return x + x * (z * ps), 1.0 - (0.5 * z - (z * z) * pc)
+
+
+def sincos_rad_host(x):
+    """(sin, cos) of float64 radians, |x| <= 8 (NaN beyond): carrier_core.hpp's sincos_rad, operation by operation"""
+    x = np.asarray(x, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        ax = np.where(x < 0.0, -x, x)
+        ok = ax <= 8.0
+        axs = np.where(ok, ax, 0.0)
+        k = (axs * _TWO_OVER_PI + 0.5).astype(np.int64)
+        dk = k.astype(np.float64)
+        t1 = axs - dk * _PIO2_1
+        p2 = dk * _PIO2_2
+        h0 = t1 - p2
+        bb = h0 - t1
+        l0 = (t1 - (h0 - bb)) + (-p2 - bb)
+        l1 = l0 - dk * _PIO2_3
+        h = h0 + l1
+        lo = l1 - (h - h0)
+        sh, ch = _sincos_octant_host(np.where(h < 0.0, -h, h))
+        sh = np.where(h < 0.0, -sh, sh)
+        sr, cr = sh + lo * ch, ch - lo * sh
+        q = k & 3
+        sa, ca = np.where(q & 1, cr, sr), np.where(q & 1, sr, cr)
+        sa = np.where(q & 2, -sa, sa)
+        ca = np.where((q == 1) | (q == 2), -ca, ca)
+        bad = (x - x) / (x - x)
+        return np.where(ok, np.where(x < 0.0, -sa, sa), bad), np.where(ok, ca, bad)
+
+
+def wrap_2pi_host(a):
+    """np.mod(a, 2 pi) spelled out as carrier_core.hpp's wrap_2pi computes it: the exact remainder, plus 2 pi when negative, +0 when zero"""
+    with np.errstate(invalid="ignore"):
+        m = np.fmod(np.asarray(a, dtype=np.float64), _TWO_PI)
+        return np.where(m != 0.0, np.where(m < 0.0, m + _TWO_PI, m), 0.0)
+
+
+def _two_sum(a, b):
+    s = a + b
+    bb = s - a
+    return s, (a - (s - bb)) + (b - bb)
+
+
+def _two_prod(a, b):
+    """(p, a b - p): the second word is what fma(a, b, -p) returns, from Dekker's split (no overflow or underflow in the partial products)"""
+    p = a * b
+    ca, cb = a * 134217729.0, b * 134217729.0
+    ah, bh = ca - (ca - a), cb - (cb - b)
+    al, bl = a - ah, b - bh
+    return p, ((ah * bh - p) + ah * bl + al * bh) + al * bl
+
+
+def _dd_dot(a, ch, cl, b, dh, dl, sign):
+    ph, pl = _two_prod(a, ch)
+    qh, ql = _two_prod(b, dh)
+    sh, sl = _two_sum(ph, sign * qh)
+    return _two_sum(sh, sl + (pl + sign * ql) + (a * cl + sign * (b * dl)))
+
+
+def _dd_sub(ah, al, bh, bl):
+    sh, sl = _two_sum(ah, -bh)
+    return _two_sum(sh, sl + (al - bl))
+
+
+def atan2_rn_host(y, x):
+    """symmap_core.hpp's atan2_rn, operation by operation (its fused multiply-adds are exact error terms, formed here by Dekker's product: for
+    operands between 2^-400 and 2^400 in magnitude)"""
+    y, x = (np.array(v, dtype=np.float64) for v in np.broadcast_arrays(y, x))
+    with np.errstate(all="ignore"):
+        ax, ay = np.abs(x), np.abs(y)
+        swap = ay > ax
+        hi, lo = np.where(swap, ay, ax), np.where(swap, ax, ay)
+        f = np.where(hi > 2.0 ** 1000, 2.0 ** -200, np.where(hi < 2.0 ** -900, 2.0 ** 200, 1.0))
+        hi, lo = hi * f, lo * f
+        q = lo / hi
+        k = 4 - sum((q < c).astype(np.int64) for c in _ATAN_CUTS)
+        ah, al, ch, cl, sh, sl = (_ATAN_TAB[k, i] for i in range(6))
+        nh, nl = _dd_dot(lo, ch, cl, hi, sh, sl, -1.0)
+        dh, dl = _dd_dot(hi, ch, cl, lo, sh, sl, 1.0)
+        u = nh / dh
+        ph, pl = _two_prod(u, dh)
+        rem = (nh - ph) - pl
+        u2 = u * u
+        ul = ((rem + nl) - u * dl) / dh / (1.0 + u2)
+        t = np.full(u.shape, -1.0 / 19.0)
+        for c in (1.0 / 17.0, -1.0 / 15.0, 1.0 / 13.0, -1.0 / 11.0, 1.0 / 9.0, -1.0 / 7.0, 1.0 / 5.0, -1.0 / 3.0):
+            t = t * u2 + c
+        tail = t * u2 * u
+        s1h, s1l = _two_sum(ah, u)
+        gh, gl = _two_sum(s1h, s1l + (al + ul + tail))
+        wh, wl = _dd_sub(_PIO2_DD[0], _PIO2_DD[1], gh, gl)
+        gh, gl = np.where(swap, wh, gh), np.where(swap, wl, gl)
+        wh, wl = _dd_sub(_PI_DD[0], _PI_DD[1], gh, gl)
+        gh = np.where(np.signbit(x), wh, gh)
+        out = np.copysign(gh, y)
+        out = np.where(x == 0.0, np.copysign(0.5 * _PI, y), out)
+        return np.where(y == 0.0, np.copysign(np.where(np.signbit(x), _PI, 0.0), y), out)
+
+
+def carrier_family(mod_type):
+    if mod_type == "MPSK":
+        return MPSK
+    if mod_type == "MQAM":
+        return QAM
+    raise ValueError("mod_type must be 'MPSK' or 'MQAM'")
+
+
+def carrier_gains(BnTs, zeta):
+    """(K1, K2) of one loop bandwidth, in the reference's statements (synchronization.py:207-211) on Python floats"""
+    BnTs, zeta = float(BnTs), float(zeta)
+    Ns, Kp, K0 = 1, 1, 1
+    K1 = 4 * zeta / (zeta + 1 / (4 * zeta)) * BnTs / Ns / Kp / K0
+    K2 = 4 / (zeta + 1 / (4 * zeta)) ** 2 * (BnTs / Ns) ** 2 / Kp / K0
+    return K1, K2
+
+
+def carrier_gains_rows(BnTs, zeta, nrow):
+    """(k1, k2, gains): the scalars and None for one bandwidth, else (0, 0, float64 (nrow, 2)) for one per row"""
+    b = np.asarray(BnTs, dtype=np.float64)
+    if b.ndim == 0:
+        return carrier_gains(b, zeta) + (None,)
+    if b.shape != (nrow,):
+        raise ValueError("BnTs: a scalar, or one value per row")
+    return 0.0, 0.0, np.ascontiguousarray([carrier_gains(v, zeta) for v in b], dtype=np.float64).reshape(nrow, 2)
+
+
+def carrier_table(fam, mod):
+    """(inv_sqrt2, tab_re, tab_im): 1 / np.sqrt(2) (what NumPy's complex quotient by np.sqrt(2) multiplies with) and, for MPSK above 4, the decision
+    points np.exp(1j 2 pi a / M) in the reference's own operations; (None, None) otherwise"""
+    inv = float(1.0 / np.sqrt(2))
+    if fam == MPSK and mod > 4:
+        pts = np.array([np.exp(1j * 2 * np.pi * np.complex128(a) / mod) for a in range(mod)], dtype=np.complex128)
+        return inv, np.ascontiguousarray(pts.real), np.ascontiguousarray(pts.imag)
+    return inv, None, None
+
+
+def carrier_step_host(fam, mod, type, open_loop, k1, k2, r, back, theta, vi, xr, xi, table):
+    """One symbol of every row: carrier_core.hpp's step in NumPy, operation by operation.  k1, k2, r, back, theta, vi, xr, xi: float64 arrays, one
+    entry per row; table: carrier_table's.  Returns (zr, zi, ar, ai, e, theta_h, theta, vi), zr / zi before the MQAM factor `back`."""
+    inv_sqrt2, tab_re, tab_im = table
+    with np.errstate(all="ignore"):
+        if fam == QAM:
+            xr, xi = xr * r, xi * r
+        s, c = sincos_rad_host(theta)
+        d = -s
+        zr, zi = xr * c - xi * d, xr * d + xi * c
+        if fam == MPSK:
+            if mod == 2:
+                ar, ai = np.sign(zr) + 0.0, np.zeros_like(zr)
+            elif mod == 4:
+                ar, ai = np.sign(zr) * inv_sqrt2, np.sign(zi) * inv_sqrt2
+            else:
+                kk = np.rint(atan2_rn_host(zi, zr) * float(mod) / 2.0 / _PI)
+                idx = np.where(kk == kk, kk, 0.0).astype(np.int64) & (mod - 1)
+                ar, ai = tab_re[idx], tab_im[idx]
+        else:
+            x_m = 1 if mod == 2 else (1 << (sym_bits(QAM, mod) // 2)) - 1
+
+            def level(v):
+                k = np.rint((v + float(x_m)) * 0.5)
+                return np.where(k > 0.0, np.minimum(k, float(x_m)), 0.0)
+            ar, ai = 2.0 * level(zr) - x_m, 2.0 * level(zi) - x_m
+        if type == 0:
+            e = zi * ar - zr * ai
+        elif type == 1:
+            se, ce = sincos_rad_host(atan2_rn_host(zi, zr) - atan2_rn_host(ai, ar))
+            e = atan2_rn_host(se, ce)
+        else:
+            abr, abi = np.abs(ar), np.abs(ai)
+            first = abr >= abi
+            rat1, rat2 = ai / ar, ar / ai
+            e1 = (zi - zr * rat1) * (1.0 / (ar + ai * rat1))
+            e2 = (zi * rat2 - zr) * (1.0 / (ai + ar * rat2))
+            e = np.where(first, np.where((abr == 0.0) & (abi == 0.0), zi / abr, e1), e2)
+        vp = k1 * e
+        vi = vi + k2 * e
+        th = wrap_2pi_host(theta + (vp + vi))
+    return zr, zi, ar, ai, e, th, (np.zeros_like(th) if open_loop else th), vi
+
+
+def _car_outputs(outputs):
+    outputs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+    if not outputs or any(o not in CAR_OUTPUTS for o in outputs) or len(set(outputs)) != len(outputs):
+        raise ValueError("outputs: a non-empty selection of %r" % (CAR_OUTPUTS,))
+    return outputs, sum(1 << CAR_OUTPUTS.index(o) for o in outputs)
+
+
+def _car_args(x2d, fam, mod, type, start, step):
+    sym_bits(fam, mod)
+    if type not in (0, 1, 2):
+        raise ValueError("type must be 0, 1 or 2")
+    x = np.asarray(x2d)
+    if x.ndim != 2:
+        raise ValueError("DD_carrier_sync_rows: a 2-D array, one frame per row")
+    if x.dtype not in (np.complex64, np.complex128):
+        raise TypeError("DD_carrier_sync: z must be complex64 or complex128 (got %s)" % x.dtype)
+    return np.ascontiguousarray(x), sym_count(x.shape[1], int(start), int(step))
+
+
+def qam_scale_rows_np(x2d, mod, start=0, step=1):
+    """r = 1 / (np.std(row[start::step]) c) per row with NumPy's own np.std: what the host restatement of the carrier loop scales MQAM rows with where
+    it is not handed the device's deterministic merge (qam_scale_rows), within that merge's documented accuracy of np.std"""
+    x = np.asarray(x2d)[:, int(start)::int(step)].astype(np.complex128)
+    with np.errstate(all="ignore"):
+        return 1.0 / (np.std(x, axis=1) * qam_scale_const(mod)) if x.shape[1] else np.ones(x.shape[0])
+
+
+def dd_carrier_rows_host(x2d, fam, mod, BnTs, zeta=0.707, type=0, open_loop=False, start=0, step=1, outputs=CAR_OUTPUTS, r=None):
+    """dd_carrier_rows in NumPy (no GPU), the kernel's arithmetic operation for operation: vectorised over rows, sequential over symbols.  r: the
+    MQAM rows' 1 / scale (default qam_scale_rows_np; pass qam_scale_rows' to restate a device call bit for bit).  Returns the selected arrays."""
+    outputs, _ = _car_outputs(outputs)
+    x, n = _car_args(x2d, fam, mod, type, start, step)
+    nrow = x.shape[0]
+    k1, k2, gains = carrier_gains_rows(BnTs, zeta, nrow)
+    k1, k2 = (np.full(nrow, k1), np.full(nrow, k2)) if gains is None else (gains[:, 0].copy(), gains[:, 1].copy())
+    if fam == QAM:
+        r = qam_scale_rows_np(x, mod, start, step) if r is None else np.ascontiguousarray(r, dtype=np.float64).reshape(nrow)
+        with np.errstate(all="ignore"):
+            back = 1.0 / r
+    else:
+        r = back = np.ones(nrow)
+    table = carrier_table(fam, mod)
+    xs = x[:, int(start)::int(step)].astype(np.complex128)
+    z, a = np.zeros((nrow, n), dtype=np.complex128), np.zeros((nrow, n), dtype=np.complex128)
+    e, t = np.zeros((nrow, n)), np.zeros((nrow, n))
+    theta, vi = np.zeros(nrow), np.zeros(nrow)
+    for k in range(n if nrow else 0):
+        zr, zi, ar, ai, e[:, k], t[:, k], theta, vi = carrier_step_host(fam, mod, type, open_loop, k1, k2, r, back, theta, vi, xs[:, k].real.copy(), xs[:, k].imag.copy(), table)
+        with np.errstate(all="ignore"):
+            z[:, k].real, z[:, k].imag = (zr * back, zi * back) if fam == QAM else (zr, zi)
+        a[:, k].real, a[:, k].imag = ar, ai
+    full = dict(z_prime=z.astype(x.dtype), a_hat=a.astype(x.dtype), e_phi=e, theta_h=t)
+    return tuple(full[o] for o in outputs)
+
+
+def dd_carrier_rows(x2d, fam, mod, BnTs, zeta=0.707, type=0, open_loop=False, start=0, step=1, outputs=CAR_OUTPUTS):
+    """(nrow, width) complex -> the selected of z_prime, a_hat (x's dtype), e_phi, theta_h (float64), (nrow, n) each with n = len(row[start::step])
+    (csrc/carrier.hip: carrier_rows_kernel, behind the MQAM rows' scales by symscale_kernel).  Host arrays, one staged call."""
+    outputs, mask = _car_outputs(outputs)
+    x, n = _car_args(x2d, fam, mod, type, start, step)
+    nrow = x.shape[0]
+    k1, k2, gains = carrier_gains_rows(BnTs, zeta, nrow)
+    inv, tre, tim = carrier_table(fam, mod)
+    full = dict(z_prime=np.zeros((nrow, n), dtype=x.dtype), a_hat=np.zeros((nrow, n), dtype=x.dtype), e_phi=np.zeros((nrow, n)), theta_h=np.zeros((nrow, n)))
+    p = {o: (_ptr(full[o]) if o in outputs else None) for o in CAR_OUTPUTS}
+    check(load().skdsp_carrier_rows(_ptr(x), n, nrow, x.shape[1], int(start), int(step), code_of(x.dtype), fam, mod, type, int(bool(open_loop)), k1, k2,
+                                    None if gains is None else _ptr(gains), qam_scale_const(mod) if fam == QAM else 0.0, inv, None if tre is None else _ptr(tre),
+                                    None if tim is None else _ptr(tim), mask, p["z_prime"], p["a_hat"], p["e_phi"], p["theta_h"]))
+    return tuple(full[o] for o in outputs)
+
+
+def dd_carrier_rows_dev(xd, n, nrow, fam, mod, type, open_loop, k1, k2, zd=None, ad=None, ed=None, td=None, gd=None, rd=None, x_stride=None, y_stride=None, start=0, step=1,
+                        dtype=None):
+    """Device pointers (DeviceArrays or addresses): n symbols per row read at start + k step; strides in elements (default: the window a row is read from, and
+    n); zd / ad / ed / td: the outputs to produce (None: not produced); gd: (nrow, 2) float64 gains or None for k1, k2; rd: MQAM, what qam_scale_rows_dev wrote."""
+    dt = xd.dtype if dtype is None else dtype
+    inv, tre, tim = carrier_table(fam, mod)
+    mask = sum(1 << i for i, d in enumerate((zd, ad, ed, td)) if d is not None)
+    xs = int(start) + (int(n) - 1) * int(step) + 1 if n else 0
+    check(load().skdsp_carrier_rows_dev(_dp(xd), int(n), int(nrow), int(xs if x_stride is None else x_stride), int(start), int(step), code_of(dt), fam, mod, type,
+                                        int(bool(open_loop)), float(k1), float(k2), _dp(gd), _dp(rd), inv, None if tre is None else _ptr(tre),
+                                        None if tim is None else _ptr(tim), mask, _dp(zd), _dp(ad), _dp(ed), _dp(td), int(n if y_stride is None else y_stride)))
+
+
+def time_step_len(n, ns, t_step, n_step):
+    """len(np.hstack((z[:ns n_step], z[ns n_step + t_step:], np.zeros(t_step)))) for len(z) = n"""
+    edge = min(n, ns * n_step)
+    return edge + max(0, n - ns * n_step - t_step) + t_step
+
+
+def time_step_rows_dev(xd, yd, n, nrow, ns, n_step, t_step=0, td=None, n_out=None, x_stride=None, y_stride=None, dtype=None):
+    """yd[r, j] = xd[r, j] in front of sample ns n_step, xd[r, j + t_step] behind it, zeros where that leaves the row (csrc/carrier.hip:
+    impair_rows_kernel); td: nrow int64 t_steps on the device, else the scalar; n_out: the output row length (default n); strides in elements"""
+    n_out = int(n if n_out is None else n_out)
+    check(load().skdsp_time_step_rows_dev(_dp(xd), int(n), int(nrow), int(n if x_stride is None else x_stride), code_of(xd.dtype if dtype is None else dtype), int(ns),
+                                          int(n_step), int(t_step), _dp(td), _dp(yd), n_out, int(n_out if y_stride is None else y_stride)))
+
+
+def phase_step_rows_dev(xd, yd, n, nrow, ns, n_step, factor=1.0, fd=None, x_stride=None, y_stride=None, dtype=None):
+    """yd[r, j] = xd[r, j ns] f, j < ceil(n / ns): f = 1 + 0j before symbol n_step, `factor` (the caller's np.exp(1j p_step)) or row r of fd ((nrow, 2)
+    float64 (re, im) on the device) from there on"""
+    n_out = -(-int(n) // int(ns)) if ns >= 1 else 0
+    f = complex(factor)
+    check(load().skdsp_phase_step_rows_dev(_dp(xd), int(n), int(nrow), int(n if x_stride is None else x_stride), code_of(xd.dtype if dtype is None else dtype), int(ns),
+                                           int(n_step), f.real, f.imag, _dp(fd), _dp(yd), int(n_out if y_stride is None else y_stride)))
 
 
 def device_bytes_of(a):
