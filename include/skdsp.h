@@ -434,6 +434,21 @@ int skdsp_time_step_rows_dev(const void *x_dev, int64_t n, int64_t nrow, int64_t
 int skdsp_phase_step_rows_dev(const void *x_dev, int64_t n, int64_t nrow, int64_t x_stride, int dtype, int64_t ns, int64_t n_step, double f_re, double f_im,
                               const double *factors_dev, void *y_dev, int64_t y_stride);
 
+/* Non-data-aided symbol timing recovery over the rows of a frame set (csrc/timing.hip, csrc/timing_core.hpp): synchronization.NDA_symb_sync per row, every row a
+ * frame from rest.  dtype: complex64 or complex128 (complex64 is storage only: the loop runs in float64).  A row's frame is x[r, start ... start + n - 1]; strides in
+ * elements; no handle.  ns: samples per symbol, 2 ... 16; L: the detector is smoothed over 2L + 1 symbols, 0 ... 8; iord: the Farrow interpolator's order, 1, 2 or 3;
+ * (k1, k2) or gains (nrow pairs): the loop filter's gains; rot: ns real parts, then ns imaginary parts, of exp(-1j 2 pi k / ns) on the HOST; inv_ns = 1 / ns,
+ * inv_len = 1 / (2L + 1), k_eps = -1 / (2 pi) as the caller's arithmetic rounds them.  outputs: bit 0 zz (of dtype), 1 e_tau (float64): only the selected ones are
+ * written.  counts[r] is the reference's output length of row r; a row's outputs take min(counts[r], cap) elements and nothing behind them is written by the device
+ * form (the host form returns zeros there).  counts[r] > cap tells the caller that the row was cut.  normalize: zz /= np.std(zz) per row.  For ns = 2 with
+ * iord >= 2 a frame of odd length >= 3 is refused: the reference's own slices run past its array there.
+ * The device, the host emulation (tests/host/nda_emul.cpp) and the NumPy restatement (_ffi.nda_rows_host) give the same bits. */
+int skdsp_nda_rows(const void *x, int64_t n, int64_t nrow, int64_t x_stride, int64_t start, int dtype, int ns, int L, int iord, double k1, double k2, const double *gains,
+                   const double *rot, double inv_ns, double inv_len, double k_eps, int outputs, int normalize, int64_t cap, void *zz, double *e_tau, int64_t *counts);
+int skdsp_nda_rows_dev(const void *x_dev, int64_t n, int64_t nrow, int64_t x_stride, int64_t start, int dtype, int ns, int L, int iord, double k1, double k2,
+                       const double *gains_dev, const double *rot, double inv_ns, double inv_len, double k_eps, int outputs, int normalize, int64_t cap, void *zz_dev,
+                       double *e_tau_dev, int64_t *counts_dev, int64_t y_stride);
+
 /* Host-pointer entry points of a float32/complex64 handle deliver y as float64/complex128 (the
  * reference's result dtype, multirate_helper.py:108 etc.): widened on the device before the copy
  * back, so y must hold twice the bytes.  Device-pointer (_dev) entry points are not affected. */

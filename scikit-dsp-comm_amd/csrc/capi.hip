@@ -442,6 +442,33 @@ static int impair_call(bool host, int mode, const void *x, int64_t n, int64_t nr
                                          factors ? (const double *)p.dev(iff) : nullptr, p.dev(iy), n_out, y_stride, ctx().stream));
 }
 
+// ---------------------------------------------------------------- symbol timing recovery over rows (timing.hip): synchronization.NDA_symb_sync_rows
+// host form: rows x_stride apart in x, contiguous (cap each) in the selected outputs, which come back zero behind a row's count; gains: null or nrow pairs on the HOST;
+// counts: nrow int64 on the host.  The float64 symbols that complex64 rows are normalised from live in workspace 3 of the calling slot, in both forms.
+static int nda_call(bool host, const void *x, int64_t n, int64_t nrow, int64_t x_stride, int64_t start, int dtype, int ns, int L, int iord, double k1, double k2,
+                    const double *gains, const double *rot, double inv_ns, double inv_len, double k_eps, int outputs, int normalize, int64_t cap, void *z, double *e,
+                    int64_t *counts, int64_t y_stride)
+{
+    int rc = nda_check(ns, L, iord, dtype, outputs, n, nrow, start, x_stride, y_stride, cap);
+    if (rc || nrow == 0) return rc;
+    SK_CHECK((x || n == 0) && counts && rot, SKDSP_ERR_BADARG, "nda_rows: null pointer");
+    SK_CHECK(cap == 0 || ((!(outputs & 1) || z) && (!(outputs & 2) || e)), SKDSP_ERR_BADARG, "nda_rows: a selected output is null");
+    API_BEGIN;
+    StagePlan p(host);
+    p.input(x, n ? (size_t)((nrow - 1) * x_stride + start + n) * dtype_size(dtype) : 0);
+    const size_t rows = (size_t)y_stride * (size_t)nrow, zb = (outputs & 1) ? rows * dtype_size(dtype) : 0, eb = (outputs & 2) ? rows * sizeof(double) : 0;
+    const int ig = p.add_in(gains, gains ? (size_t)nrow * 2 * sizeof(double) : 0);
+    const int iz = p.add_out((outputs & 1) ? z : nullptr, zb), ie = p.add_out((outputs & 2) ? e : nullptr, eb), ic = p.add_out(counts, (size_t)nrow * sizeof(int64_t));
+    p.scratch_bytes = nda_scratch_bytes(dtype, outputs, normalize, nrow, cap);
+    if ((rc = stage_begin(p))) return rc;
+    if (host) {
+        if (zb) SK_HIP(hipMemsetAsync(p.dev(iz), 0, zb, ctx().stream));
+        if (eb) SK_HIP(hipMemsetAsync(p.dev(ie), 0, eb, ctx().stream));
+    }
+    return stage_finish(p, nda_launch(p.in_dev(), n, nrow, x_stride, start, dtype, ns, L, iord, k1, k2, gains ? (const double *)p.dev(ig) : nullptr, rot, inv_ns, inv_len, k_eps,
+                                      outputs, normalize, cap, p.scratch, p.dev(iz), (double *)p.dev(ie), (int64_t *)p.dev(ic), y_stride, ctx().stream));
+}
+
 extern "C" {
 
 // FIR bank (fir_bank.hip): argument errors need no device
@@ -797,6 +824,20 @@ int skdsp_phase_step_rows_dev(const void *x_dev, int64_t n, int64_t nrow, int64_
                               const double *factors_dev, void *y_dev, int64_t y_stride)
 {
     return impair_call(false, 1, x_dev, n, nrow, x_stride, dtype, ns, n_step, 0, nullptr, f_re, f_im, factors_dev, y_dev, ns >= 1 ? (n + ns - 1) / ns : 0, y_stride);
+}
+
+// ---------------------------------------------------------------- symbol timing recovery over rows
+int skdsp_nda_rows_dev(const void *x_dev, int64_t n, int64_t nrow, int64_t x_stride, int64_t start, int dtype, int ns, int L, int iord, double k1, double k2,
+                       const double *gains_dev, const double *rot, double inv_ns, double inv_len, double k_eps, int outputs, int normalize, int64_t cap, void *zz_dev,
+                       double *e_tau_dev, int64_t *counts_dev, int64_t y_stride)
+{
+    return nda_call(false, x_dev, n, nrow, x_stride, start, dtype, ns, L, iord, k1, k2, gains_dev, rot, inv_ns, inv_len, k_eps, outputs, normalize, cap, zz_dev, e_tau_dev, counts_dev,
+                    y_stride);
+}
+int skdsp_nda_rows(const void *x, int64_t n, int64_t nrow, int64_t x_stride, int64_t start, int dtype, int ns, int L, int iord, double k1, double k2, const double *gains,
+                   const double *rot, double inv_ns, double inv_len, double k_eps, int outputs, int normalize, int64_t cap, void *zz, double *e_tau, int64_t *counts)
+{
+    return nda_call(true, x, n, nrow, x_stride, start, dtype, ns, L, iord, k1, k2, gains, rot, inv_ns, inv_len, k_eps, outputs, normalize, cap, zz, e_tau, counts, cap);
 }
 
 }  // extern "C"

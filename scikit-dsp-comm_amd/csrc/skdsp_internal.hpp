@@ -437,4 +437,16 @@ int impair_check(int mode, int dtype, int64_t n, int64_t n_out, int64_t nrow, in
 int impair_launch(int mode, const void *x_dev, int64_t n, int64_t nrow, int64_t x_stride, int dtype, int64_t ns, int64_t n_step, int64_t shift, const int64_t *shifts_dev,
                   double c, double d, const double *factors_dev, void *y_dev, int64_t n_out, int64_t y_stride, hipStream_t s);
 
+// ---- symbol timing recovery over rows (timing.hip): synchronization.NDA_symb_sync; the recipe, the plans and the per-thread functions are timing_core.hpp ----
+// n: the samples of a row's frame, x[row, start ... start + n - 1]; outputs: bit 0 zz, 1 e_tau (an output that is not selected is not touched and may be null); cap: the
+// elements a row's outputs may take (y_stride >= cap apart); counts_dev[row]: the reference's output length, also where it exceeds cap.  Nothing behind
+// min(counts[row], cap) elements of a row is written.  gains_dev: null (k1, k2 serve every row) or [nrow][2].  rot_host: Ns real parts, then Ns imaginary parts, of
+// the host's np.exp(-1j 2 pi / Ns kk); inv_ns, inv_len, k_eps: the host's 1 / float(Ns), 1.0 / (2L + 1), -1 / (2 np.pi).  normalize: zz /= np.std(zz) per row, by a second
+// kernel; for complex64 samples that one reads the raw symbols from scratch_dev (nda_scratch_bytes, 16-byte aligned), in float64.  No handle.
+int nda_check(int ns, int L, int iord, int dtype, int outputs, int64_t n, int64_t nrow, int64_t start, int64_t x_stride, int64_t y_stride, int64_t cap);   // host-only
+size_t nda_scratch_bytes(int dtype, int outputs, int normalize, int64_t nrow, int64_t cap);                                                               // host-only
+int nda_launch(const void *x_dev, int64_t n, int64_t nrow, int64_t x_stride, int64_t start, int dtype, int ns, int L, int iord, double k1, double k2, const double *gains_dev,
+               const double *rot_host, double inv_ns, double inv_len, double k_eps, int outputs, int normalize, int64_t cap, void *scratch_dev, void *z_dev, double *e_dev,
+               int64_t *counts_dev, int64_t y_stride, hipStream_t s);
+
 }  // namespace skdsp

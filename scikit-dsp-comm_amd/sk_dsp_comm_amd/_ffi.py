@@ -46,7 +46,7 @@ SYMBOLS = [
     "skdsp_ofdm_tx_rows", "skdsp_ofdm_tx_rows_dev", "skdsp_ofdm_rx_rows", "skdsp_ofdm_rx_rows_dev", "skdsp_ofdm_equalize_rows", "skdsp_ofdm_equalize_rows_dev",
     "skdsp_lag_corr_len", "skdsp_lag_corr", "skdsp_lag_corr_dev", "skdsp_sym_count_rows", "skdsp_sym_count_rows_dev",
     "skdsp_pulse_create", "skdsp_pulse_mf_out_len", "skdsp_pulse_shape_rows", "skdsp_pulse_shape_rows_dev", "skdsp_pulse_mf_rows", "skdsp_pulse_mf_rows_dev",
-    "skdsp_carrier_rows", "skdsp_carrier_rows_dev", "skdsp_time_step_rows_dev", "skdsp_phase_step_rows_dev",
+    "skdsp_carrier_rows", "skdsp_carrier_rows_dev", "skdsp_time_step_rows_dev", "skdsp_phase_step_rows_dev", "skdsp_nda_rows", "skdsp_nda_rows_dev",
     "skdsp_dist_unique_id", "skdsp_dist_init", "skdsp_dist_shutdown", "skdsp_dist_comm_count", "skdsp_dist_barrier",
     "skdsp_dist_allreduce_max", "skdsp_dist_allreduce_sum", "skdsp_dist_sendrecv", "skdsp_dist_allgather", "skdsp_dist_halo_exchange", "skdsp_fir_filter_shard_dev",
 ]
@@ -212,6 +212,10 @@ def load():
             L.skdsp_carrier_rows_dev.argtypes = [vp, i64, i64, i64, i64, i64, ci, ci, ci, ci, ci, dbl, dbl, vp, vp, dbl, vp, vp, ci, vp, vp, vp, vp, i64]
             L.skdsp_time_step_rows_dev.argtypes = [vp, i64, i64, i64, ci, i64, i64, i64, vp, vp, i64, i64]
             L.skdsp_phase_step_rows_dev.argtypes = [vp, i64, i64, i64, ci, i64, i64, dbl, dbl, vp, vp, i64]
+        if hasattr(L, "skdsp_nda_rows"):
+            dbl = ctypes.c_double
+            L.skdsp_nda_rows.argtypes = [vp, i64, i64, i64, i64, ci, ci, ci, ci, dbl, dbl, vp, vp, dbl, dbl, dbl, ci, ci, i64, vp, vp, vp]
+            L.skdsp_nda_rows_dev.argtypes = [vp, i64, i64, i64, i64, ci, ci, ci, ci, dbl, dbl, vp, vp, dbl, dbl, dbl, ci, ci, i64, vp, vp, vp, i64]
         L.skdsp_dist_unique_id.argtypes = [vp]
         L.skdsp_dist_init.argtypes = [ci, ci, vp]
         L.skdsp_dist_comm_count.argtypes = [ctypes.POINTER(ci)]
@@ -1957,6 +1961,265 @@ def phase_step_rows_dev(xd, yd, n, nrow, ns, n_step, factor=1.0, fd=None, x_stri
     f = complex(factor)
     check(load().skdsp_phase_step_rows_dev(_dp(xd), int(n), int(nrow), int(n if x_stride is None else x_stride), code_of(xd.dtype if dtype is None else dtype), int(ns),
                                            int(n_step), f.real, f.imag, _dp(fd), _dp(yd), int(n_out if y_stride is None else y_stride)))
+
+
+# --------------------------------------------------------------------------
+# Symbol timing recovery over frame sets (csrc/timing.hip): synchronization.NDA_symb_sync
+# --------------------------------------------------------------------------
+NDA_OUTPUTS = ("zz", "e_tau")
+NDA_NORM_THREADS = 256          # timing_core.hpp's kNormThreads: the partial sums of the rows' standard deviation
+
+
+def nda_gains(BnTs, zeta, Ns):
+    """(K1, K2) of one loop bandwidth, in the reference's statements (synchronization.py:67-70) on Python floats"""
+    BnTs, zeta = float(BnTs), float(zeta)
+    K0 = -1.0
+    Kp = 1.0
+    K1 = 4 * zeta / (zeta + 1 / (4 * zeta)) * BnTs / Ns / Kp / K0
+    K2 = 4 / (zeta + 1 / (4 * zeta)) ** 2 * (BnTs / Ns) ** 2 / Kp / K0
+    return K1, K2
+
+
+def nda_gains_rows(BnTs, zeta, Ns, nrow):
+    """(k1, k2, gains): the scalars and None for one bandwidth, else (0, 0, float64 (nrow, 2)) for one per row"""
+    b = np.asarray(BnTs, dtype=np.float64)
+    if b.ndim == 0:
+        return nda_gains(b, zeta, Ns) + (None,)
+    if b.shape != (nrow,):
+        raise ValueError("BnTs: a scalar, or one value per row")
+    return 0.0, 0.0, np.ascontiguousarray([nda_gains(v, zeta, Ns) for v in b], dtype=np.float64).reshape(nrow, 2)
+
+
+def nda_consts(Ns, L):
+    """(rot, inv_ns, inv_len, k_eps): the detector's rotation constants np.exp(-1j 2 pi / Ns kk) as the reference forms them (Ns real parts, then Ns
+    imaginary parts), and 1 / float(Ns), 1.0 / (2L + 1), -1 / (2 pi): what NumPy's complex quotients by Ns and 2L + 1 multiply with, and the
+    reference's factor in front of np.angle"""
+    pts = np.array([np.exp(-1j * 2 * np.pi / Ns * kk) for kk in range(Ns)], dtype=np.complex128)
+    return np.ascontiguousarray(np.concatenate([pts.real, pts.imag])), 1 / float(Ns), 1.0 / (2 * L + 1), -1 / (2 * np.pi)
+
+
+def nda_loop_end(n, Ns):
+    """N of the reference for len(z) = n: its loop is range(1, N)"""
+    return max(0, Ns * ((n + 1) // Ns - (Ns - 1)))
+
+
+def nda_iters(n, Ns):
+    """the reference's loop iterations for len(z) = n: an exact upper bound of its output length"""
+    return max(0, nda_loop_end(n, Ns) - 1)
+
+
+def np_csum_host(vals):
+    """np.sum of complex values in NumPy's order (timing_core.hpp's np_csum): vals a list of (re, im) pairs of arrays"""
+    n = len(vals)
+    if n < 4:
+        sr, si = vals[0]
+        for xr, xi in vals[1:]:
+            sr, si = sr + xr, si + xi
+        return sr, si
+    rr, ri = [v[0] for v in vals[:4]], [v[1] for v in vals[:4]]
+    i = 4
+    while i < n - (n % 4):
+        for k in range(4):
+            rr[k], ri[k] = rr[k] + vals[i + k][0], ri[k] + vals[i + k][1]
+        i += 4
+    sr, si = (rr[0] + rr[1]) + (rr[2] + rr[3]), (ri[0] + ri[1]) + (ri[2] + ri[3])
+    for xr, xi in vals[i:]:
+        sr, si = sr + xr, si + xi
+    return sr, si
+
+
+def _farrow_sum_host(a, c):
+    t0, t1, t2, t3 = a[3] * c[0], a[2] * c[1], a[1] * c[2], a[0] * c[3]
+    return (t0 + t1) + (t2 + t3)
+
+
+def nda_interp_host(I_ord, mu, a):
+    """one component of the interpolant: timing_core.hpp's interp; a = (z[nn - 1], z[nn], z[nn + 1], z[nn + 2])"""
+    if I_ord == 1:
+        return mu * a[1] + (1.0 - mu) * a[0]
+    if I_ord == 2:
+        v2, v1 = 0.5 * _farrow_sum_host(a, (1.0, -1.0, -1.0, 1.0)), 0.5 * _farrow_sum_host(a, (-1.0, 3.0, -1.0, -1.0))
+        return (mu * v2 + v1) * mu + a[1]
+    v3, v2 = _farrow_sum_host(a, (1 / 6., -1 / 2., 1 / 2., -1 / 6.)), _farrow_sum_host(a, (0.0, 1 / 2., -1.0, 1 / 2.))
+    v1 = _farrow_sum_host(a, (-1 / 6., 1.0, -1 / 2., -1 / 3.))
+    return ((mu * v3 + v2) * mu + v1) * mu + a[1]
+
+
+def _nda_outputs(outputs):
+    outputs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+    if not outputs or any(o not in NDA_OUTPUTS for o in outputs) or len(set(outputs)) != len(outputs):
+        raise ValueError("outputs: a non-empty selection of %r" % (NDA_OUTPUTS,))
+    return outputs, sum(1 << NDA_OUTPUTS.index(o) for o in outputs)
+
+
+def nda_refused_length(n, Ns, I_ord):
+    """True where the reference's own slices run past its array (Ns = 2, I_ord >= 2, an odd length from 3 on: tests/golden/g28_conventions.json)"""
+    N = nda_loop_end(n, Ns)
+    return N > 1 and I_ord > 1 and N + Ns > n
+
+
+def _nda_args(x2d, Ns, L, I_ord, start, max_symbols):
+    """(x, n, iters, cap): the rows as complex64 / complex128, the frame length behind start, the loop's iterations, the outputs' row length"""
+    for v, lo, hi, what in ((Ns, 2, 16, "Ns must be an integer in 2 ... 16"), (L, 0, 8, "L must be an integer in 0 ... 8"), (I_ord, 1, 3, "I_ord must be 1, 2 or 3")):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError("NDA_symb_sync: " + what)
+    x = np.asarray(x2d)
+    if x.ndim != 2:
+        raise ValueError("NDA_symb_sync_rows: a 2-D array, one frame per row")
+    if x.dtype in (np.float32, np.float64):
+        x = x.astype(np.complex64 if x.dtype == np.float32 else np.complex128)      # exact
+    if x.dtype not in (np.complex64, np.complex128):
+        raise TypeError("NDA_symb_sync: z must be complex64, complex128, float32 or float64 (got %s)" % x.dtype)
+    if isinstance(start, (bool, np.bool_)) or not isinstance(start, (int, np.integer)) or not 0 <= start <= x.shape[1]:
+        raise ValueError("NDA_symb_sync_rows: start must be an integer inside the rows")
+    n = x.shape[1] - int(start)
+    if nda_refused_length(n, Ns, I_ord):
+        raise ValueError("NDA_symb_sync: with Ns = 2 and I_ord >= 2 a frame of odd length makes the reference's slices run past its array (len(z) = %d)" % n)
+    iters = nda_iters(n, int(Ns))
+    if max_symbols is None:
+        cap = iters
+    else:
+        if isinstance(max_symbols, (bool, np.bool_)) or not isinstance(max_symbols, (int, np.integer)) or max_symbols < 0:
+            raise ValueError("NDA_symb_sync_rows: max_symbols must be a non-negative integer")
+        cap = min(int(max_symbols), iters)
+    return np.ascontiguousarray(x), n, iters, cap
+
+
+def _nda_overflow(counts, cap):
+    over = np.nonzero(counts > cap)[0]
+    if over.size:
+        raise ValueError("NDA_symb_sync_rows: rows %s produce more than max_symbols = %d outputs (up to %d)" % (over[:8].tolist() + (["..."] if over.size > 8 else []), cap,
+                                                                                                            int(counts.max())))
+
+
+def nda_std_rows_host(raw, counts):
+    """(nrow,) the rows' standard deviations over raw[row, :counts[row]] as nda_norm_kernel forms them: np.std's two passes, each sum as NDA_NORM_THREADS
+    strided partial sums (thread t: elements t, t + 256, ... in order) and a tree over them (slot t += slot t + off, off = 128 ... 1)"""
+    raw = np.asarray(raw, dtype=np.complex128)
+    nrow, cap = raw.shape
+    counts = np.asarray(counts, dtype=np.int64)
+    T = NDA_NORM_THREADS
+    K = -(-max(cap, 1) // T)
+    valid = (np.arange(K * T)[None, :] < counts[:, None]).reshape(nrow, K, T)
+    pad = np.zeros((nrow, K * T), dtype=np.complex128)
+    pad[:, :cap] = raw
+    pad = pad.reshape(nrow, K, T)
+
+    def tree(parts):
+        parts = parts.copy()
+        off = T // 2
+        while off >= 1:
+            parts[:, :off] = parts[:, :off] + parts[:, off:2 * off]
+            off //= 2
+        return parts[:, 0]
+
+    def strided(vals):
+        acc = np.zeros((nrow, T))
+        for k in range(K):
+            acc = np.where(valid[:, k], acc + vals[:, k], acc)
+        return tree(acc)
+    with np.errstate(all="ignore"):
+        nf = counts.astype(np.float64)
+        mr, mi = strided(pad.real) / nf, strided(pad.imag) / nf
+        dr, di = pad.real - mr[:, None, None], pad.imag - mi[:, None, None]
+        return np.sqrt(strided(dr * dr + di * di) / nf)
+
+
+def nda_rows_host(x2d, Ns, L, BnTs, zeta=0.707, I_ord=3, start=0, normalize=True, max_symbols=None, outputs=NDA_OUTPUTS, underflows=False):
+    """nda_rows in NumPy (no GPU), the kernel's arithmetic operation for operation: vectorised over rows, sequential over samples.  Returns the selected
+    arrays and counts; underflows=True appends, per row, the sample indices nn at which the counter underflowed."""
+    outputs, _ = _nda_outputs(outputs)
+    x, n, iters, cap = _nda_args(x2d, Ns, L, I_ord, start, max_symbols)
+    nrow = x.shape[0]
+    k1, k2, gains = nda_gains_rows(BnTs, zeta, Ns, nrow)
+    k1, k2 = (np.full(nrow, k1), np.full(nrow, k2)) if gains is None else (gains[:, 0].copy(), gains[:, 1].copy())
+    rot, inv_ns, inv_len, k_eps = nda_consts(Ns, L)
+    ln = 2 * L + 1
+    zp = np.zeros((nrow, n + 1), dtype=np.complex128)
+    zp[:, 1:] = x[:, int(start):]
+    zpr, zpi = np.ascontiguousarray(zp.real), np.ascontiguousarray(zp.imag)
+    zr, zi, et = np.zeros((nrow, iters + 1)), np.zeros((nrow, iters + 1)), np.zeros((nrow, iters + 1))
+    cnt, mu, eps, vi = np.zeros(nrow), np.zeros(nrow), np.zeros(nrow), np.zeros(nrow)
+    under, mm = np.zeros(nrow, dtype=bool), np.ones(nrow, dtype=np.int64)
+    bufr, bufi = np.zeros((nrow, ln)), np.zeros((nrow, ln))
+    marks = [[] for _ in range(nrow)]
+    with np.errstate(all="ignore"):
+        for nn in range(1, iters + 1 if nrow else 1):
+            idx = np.nonzero(under)[0]
+            if idx.size:
+                m = mu[idx]
+                cr, ci = np.zeros(idx.size), np.zeros(idx.size)
+                for kk in range(Ns):
+                    lo = nn + kk - 1
+                    ar = [zpr[idx, lo + j] if lo + j <= n else None for j in range(4)]
+                    ai = [zpi[idx, lo + j] if lo + j <= n else None for j in range(4)]
+                    ir, ii = nda_interp_host(I_ord, m, ar), nda_interp_host(I_ord, m, ai)
+                    if kk == 0:
+                        zr[idx, mm[idx]], zi[idx, mm[idx]] = ir, ii
+                    m2 = ir * ir + ii * ii
+                    cr, ci = cr + m2 * rot[kk], ci + m2 * rot[Ns + kk]
+                cr, ci = cr * inv_ns, ci * inv_ns
+                bufr[idx, 1:], bufi[idx, 1:] = bufr[idx, :-1], bufi[idx, :-1]
+                bufr[idx, 0], bufi[idx, 0] = cr, ci
+                sr, si = np_csum_host([(bufr[idx, j], bufi[idx, j]) for j in range(ln)])
+                eps[idx] = k_eps * atan2_rn_host(si * inv_len, sr * inv_len)
+                et[idx, mm[idx]] = eps[idx]
+                mm[idx] += 1
+            vp = k1 * eps
+            vi = vi + k2 * eps
+            W = inv_ns + (vp + vi)
+            nxt = cnt - W
+            under = nxt < 0.0
+            if underflows:
+                for r in np.nonzero(under)[0]:
+                    marks[r].append(nn)
+            mu = np.where(under, cnt / W, mu)
+            cnt = np.where(under, 1.0 + nxt, nxt)
+    counts = mm - 1
+    _nda_overflow(counts, cap)
+    keep = np.arange(cap)[None, :] < counts[:, None]
+    raw = np.zeros((nrow, cap), dtype=np.complex128)
+    raw.real, raw.imag = np.where(keep, zr[:, :cap], 0.0), np.where(keep, zi[:, :cap], 0.0)
+    e = np.where(keep, et[:, :cap], 0.0)
+    if normalize and "zz" in outputs and cap:
+        with np.errstate(all="ignore"):
+            rcp = 1.0 / nda_std_rows_host(raw, counts)
+            zz = np.zeros_like(raw)
+            zz.real, zz.imag = np.where(keep, raw.real * rcp[:, None], 0.0), np.where(keep, raw.imag * rcp[:, None], 0.0)
+    else:
+        zz = raw
+    full = dict(zz=zz.astype(x.dtype), e_tau=e)
+    out = tuple(full[o] for o in outputs) + (counts,)
+    return out + (marks,) if underflows else out
+
+
+def nda_rows(x2d, Ns, L, BnTs, zeta=0.707, I_ord=3, start=0, normalize=True, max_symbols=None, outputs=NDA_OUTPUTS):
+    """(nrow, width) -> the selected of zz (x's complex dtype), e_tau (float64), (nrow, cap) each and zero behind counts[row], then counts (int64)
+    (csrc/timing.hip: nda_rows_kernel, then nda_norm_kernel where normalize).  Host arrays, one staged call."""
+    outputs, mask = _nda_outputs(outputs)
+    x, n, iters, cap = _nda_args(x2d, Ns, L, I_ord, start, max_symbols)
+    nrow = x.shape[0]
+    k1, k2, gains = nda_gains_rows(BnTs, zeta, Ns, nrow)
+    rot, inv_ns, inv_len, k_eps = nda_consts(Ns, L)
+    full = dict(zz=np.zeros((nrow, cap), dtype=x.dtype), e_tau=np.zeros((nrow, cap)))
+    counts = np.zeros(nrow, dtype=np.int64)
+    p = {o: (_ptr(full[o]) if o in outputs else None) for o in NDA_OUTPUTS}
+    check(load().skdsp_nda_rows(_ptr(x), n, nrow, x.shape[1], int(start), code_of(x.dtype), int(Ns), int(L), int(I_ord), k1, k2, None if gains is None else _ptr(gains),
+                                _ptr(rot), inv_ns, inv_len, k_eps, mask, int(bool(normalize)), cap, p["zz"], p["e_tau"], _ptr(counts)))
+    _nda_overflow(counts, cap)
+    return tuple(full[o] for o in outputs) + (counts,)
+
+
+def nda_rows_dev(xd, n, nrow, Ns, L, I_ord, k1, k2, cap, countsd, zd=None, ed=None, gd=None, x_stride=None, y_stride=None, start=0, normalize=True, dtype=None):
+    """Device pointers (DeviceArrays or addresses): a row's frame is n samples from `start`; strides in elements (default start + n, and cap); zd / ed: the
+    outputs to produce (None: not produced), min(counts[row], cap) elements per row and nothing behind them; countsd: nrow int64; gd: (nrow, 2) float64 gains
+    or None for k1, k2.  The caller compares the counts with cap (a row that outgrew it was cut)."""
+    dt = xd.dtype if dtype is None else dtype
+    rot, inv_ns, inv_len, k_eps = nda_consts(Ns, L)
+    mask = sum(1 << i for i, d in enumerate((zd, ed)) if d is not None)
+    check(load().skdsp_nda_rows_dev(_dp(xd), int(n), int(nrow), int(int(start) + int(n) if x_stride is None else x_stride), int(start), code_of(dt), int(Ns), int(L), int(I_ord),
+                                    float(k1), float(k2), _dp(gd), _ptr(rot), inv_ns, inv_len, k_eps, mask, int(bool(normalize)), int(cap), _dp(zd), _dp(ed), _dp(countsd),
+                                    int(cap if y_stride is None else y_stride)))
 
 
 def device_bytes_of(a):

@@ -1,5 +1,9 @@
-"""Carrier synchronization on the GPU: the decision-directed carrier phase tracking loop of sk_dsp_comm.synchronization and the two impairment
-helpers that exercise it (synchronization.py:169-313 of the reference), over frame sets (csrc/carrier.hip).
+"""Synchronization on the GPU: the non-data-aided symbol timing loop, the decision-directed carrier phase tracking loop of
+sk_dsp_comm.synchronization and the two impairment helpers that exercise them (synchronization.py:43-313 of the reference), over frame sets
+(csrc/timing.hip; csrc/carrier.hip).
+
+    NDA_symb_sync(z, Ns, L, BnTs, zeta=0.707, I_ord=3)                                      the reference's call: one row of the kernel
+    NDA_symb_sync_rows(z2d, ...)                                                            beyond the reference: every row a frame from rest
 
     DD_carrier_sync(z, M, BnTs, zeta=0.707, mod_type='MPSK', type=0, open_loop=False)      the reference's call: one row of the kernel
     DD_carrier_sync_rows(z2d, ...)                                                          beyond the reference: every row a frame from rest
@@ -23,12 +27,21 @@ Deliberate differences (tests/golden/g27_conventions.json):
   * the MQAM scale is the deterministic moment merge of qam_gray_decode_rows; z / z_scale is the product with r = 1 / z_scale per component (as NumPy
     divides a complex array by a real scalar) and z_prime is multiplied back by 1 / r: one rounding from the reference's z_scale.
   * phase_step / time_step of a complex64 signal return complex64 (the reference widens to complex128); negative steps are refused.
+
+NDA_symb_sync keeps the reference's conventions (tests/golden/g28_conventions.json): the zero sample in front, its loop range, zz[0] = e_tau[0] = 0, the
+last stored symbol dropped, epsilon held while the loop coasts, zz /= np.std(zz) over the trimmed output (one output: 0 / 0 = nan).  It differs in this:
+  * |z|^2 in the detector is re re + im im (the reference squares hypot); the angle is the project's atan2, rounded to nearest.
+  * Ns outside 2 ... 16, L outside 0 ... 8 or I_ord outside 1, 2, 3 raise ValueError (the reference logs and fails on an unbound name).
+  * Ns = 2 with I_ord >= 2 and an odd len(z) >= 3 raises ValueError: there the reference's slices run past its array when the counter underflows on the
+    last sample, and it raises; here the length alone decides.
+  * complex64 is storage, as above; a real z is widened exactly.
+  * the rows' np.std is np.std's two passes with sums in a fixed order (within 3e-15 of np.std, relative, for rows up to 8192 symbols).
 """
 import numpy as np
 
 from . import _ffi
 
-__all__ = ["DD_carrier_sync", "DD_carrier_sync_host", "DD_carrier_sync_rows", "DD_carrier_sync_rows_host", "phase_step", "phase_step_host", "phase_step_rows",
+__all__ = ["NDA_symb_sync", "NDA_symb_sync_host", "NDA_symb_sync_rows", "NDA_symb_sync_rows_host", "DD_carrier_sync", "DD_carrier_sync_host", "DD_carrier_sync_rows", "DD_carrier_sync_rows_host", "phase_step", "phase_step_host", "phase_step_rows",
            "phase_step_rows_host", "time_step", "time_step_host", "time_step_rows", "time_step_rows_host"]
 
 _OUTPUTS = _ffi.CAR_OUTPUTS
@@ -41,6 +54,45 @@ def _one_row(z, name):
     if z.dtype not in (np.complex64, np.complex128):
         raise TypeError("%s: z must be complex64 or complex128 (got %s)" % (name, z.dtype))
     return z.reshape(1, -1)
+
+
+def _one_row_nda(z):
+    z = np.asarray(z)
+    if z.ndim != 1:
+        raise ValueError("NDA_symb_sync: z must be one-dimensional (got shape %r)" % (z.shape,))
+    return z.reshape(1, -1)
+
+
+def NDA_symb_sync_rows(z2d, Ns, L, BnTs, zeta=0.707, I_ord=3, start=0, normalize=True, max_symbols=None, outputs=_ffi.NDA_OUTPUTS):
+    """Beyond the reference: NDA_symb_sync of every row's z2d[row, start:] in one launch, every row a frame from rest.  BnTs: a scalar, or one value per
+    row.  Returns the selected of zz (z2d's complex dtype) and e_tau (float64), nrow x cap each and zero behind counts[row], then counts (int64): the
+    reference's output length per row.  cap is the number of loop iterations, an exact upper bound, or max_symbols where that is lower; a row that
+    produces more raises ValueError (the kernel keeps counting and stops storing).  normalize=False returns the raw interpolants, for a caller whose
+    next stage scales by itself (DD_carrier_sync_rows for MQAM does).  One lane of the GPU per row (csrc/timing.hip)."""
+    return _ffi.nda_rows(z2d, Ns, L, BnTs, zeta, I_ord, start, normalize, max_symbols, outputs)
+
+
+def NDA_symb_sync_rows_host(z2d, Ns, L, BnTs, zeta=0.707, I_ord=3, start=0, normalize=True, max_symbols=None, outputs=_ffi.NDA_OUTPUTS):
+    """NDA_symb_sync_rows in NumPy (no GPU): the kernel's operations one by one, vectorised over rows, with the device's bits"""
+    return _ffi.nda_rows_host(z2d, Ns, L, BnTs, zeta, I_ord, start, normalize, max_symbols, outputs)
+
+
+def _trim(res):
+    zz, e_tau, counts = res
+    return zz[0, :counts[0]], e_tau[0, :counts[0]]
+
+
+def NDA_symb_sync(z, Ns, L, BnTs, zeta=0.707, I_ord=3):
+    """zz, e_tau = NDA_symb_sync(z, Ns, L, BnTs, zeta=0.707, I_ord=3), synchronization.py:43-166: non-data-aided symbol timing recovery of a complex
+    baseband signal at nominally Ns samples per symbol.  L: the timing error detector is smoothed over 2L + 1 symbols; BnTs: loop bandwidth times symbol
+    period; I_ord: the Farrow interpolator's order, 1, 2 or 3.  zz: the interpolants at the symbol rate, scaled to unit standard deviation; e_tau: the
+    timing error.  One row of the kernel behind NDA_symb_sync_rows; the module docstring lists what is kept and what differs."""
+    return _trim(NDA_symb_sync_rows(_one_row_nda(z), Ns, L, BnTs, zeta, I_ord))
+
+
+def NDA_symb_sync_host(z, Ns, L, BnTs, zeta=0.707, I_ord=3):
+    """NDA_symb_sync in NumPy (no GPU): one row of NDA_symb_sync_rows_host"""
+    return _trim(NDA_symb_sync_rows_host(_one_row_nda(z), Ns, L, BnTs, zeta, I_ord))
 
 
 def DD_carrier_sync_rows(z2d, M, BnTs, zeta=0.707, mod_type='MPSK', type=0, open_loop=False, start=0, step=1, outputs=_OUTPUTS):
